@@ -191,10 +191,43 @@ def parse():
     ap.add_argument('--raw-u16', action='store_true',
                     help='feed the 12-bit frames as uint16 containers (2 B/px ingest, normalised in-kernel; '
                          'SURVEY.md section 8f) instead of float32: a separate variant, not the headline config')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0): '
+                         'the output and every parameter gradient (parametrized), the output (static), the loss and the '
+                         f'processor\'s parameter gradients (e2e-*).  Arrays of more than {DUMP_SAMPLE} elements are cut '
+                         'to a fixed seeded sample (see dump_outputs), so that two builds can be compared output for output')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.quick:
         args.no_cpu_baseline = args.no_static_c3 = args.no_small_shapes = True
     return args
+
+
+DUMP_SAMPLE = 1 << 22            # --dump-outputs: elements kept of a larger array (16 MiB in float32, 32 MiB in float64)
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # and never more than this in all
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: `arrays` ({name: tensor}) as directory/<name>.npy, float64 where the path computes in float64, float32
+    otherwise.  An array of more than DUMP_SAMPLE elements is written as the 1-D run of its elements at the sorted, distinct flat
+    indices drawn by np.random.default_rng(0) -- the same indices for every run with the same arguments."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    out = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.to(torch.float32)
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        out[name] = t.cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})')
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + '.npy'), a)
 
 
 def cpu_baseline_parametrized(size, seconds=8.0):
@@ -603,11 +636,19 @@ def main_static(args):
     raw = u.to(torch.uint16) if args.raw_u16 else u.to(torch.float32) / 4095.0
     chain = (args.debayer, args.sharpening, args.denoising)
     norm = [0.35, 0.36, 0.35, 0.12, 0.11, 0.12] if args.normalize else None      # train.py:157-158 (Drone)
+    last = {} if args.dump_outputs else None         # (only then is a step's output kept beyond the step)
 
     def step():
-        return F_.static_pipeline(raw, cameras.DRONE, *chain, bits=12, mean_std=norm)
+        out = F_.static_pipeline(raw, cameras.DRONE, *chain, bits=12, mean_std=norm)
+        if last is not None:
+            last['output'] = out
+        return out
 
     dt = clock.time_steps(step, args.steps, args.warmup)
+    if last is not None:
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last)
+        last = None
     px = world * B * S * S
     k = kernel_times(lib, clock, step, args.steps) if not args.no_roofline else {}
     roofline = None
@@ -688,6 +729,7 @@ def main_e2e(args):
         else:
             net = torch.nn.parallel.DistributedDataParallel(clf)
     opt = torch.optim.Adam(isp_params + list(clf.parameters()), lr=1e-4)
+    last = {} if args.dump_outputs else None
 
     def step():
         opt.zero_grad(set_to_none=True)
@@ -696,9 +738,16 @@ def main_e2e(args):
         if world > 1:            # one flat asynchronous all-reduce of the ISP gradient (mean, like DDP), awaited before Adam
             F_.GradAllReduce(isp_params, dist.group.WORLD, average=True).wait()
         opt.step()
+        if last is not None:
+            last['loss'] = loss
         return loss
 
     dt = clock.time_steps(step, args.steps, args.warmup)
+    if last is not None:
+        if rank == 0:
+            dump_outputs(args.dump_outputs, dict(last, **{'grad.' + n: p.grad for n, p in proc.named_parameters()
+                                                          if p.grad is not None}))
+        last = None
     kernels = kernel_times(lib, clock, step, args.steps) if not args.no_roofline else {}
     isp_us = sum(v['launches'] * v['avg_us'] for v in kernels.values()) / max(args.steps, 1)
     loss = float(step().item())
@@ -776,6 +825,7 @@ def main():
         graph_step = StepGraph(model, raw, cot, process_group=dist.group.WORLD if group_on else None)
 
     pending = []
+    last = {} if args.dump_outputs else None         # (only then is a step's output kept beyond the step)
 
     def finish():                                    # the gradient all-reduce of the previous step lands here:
         while pending:                               # nothing needs the sum before the optimiser / the next forward
@@ -784,12 +834,16 @@ def main():
     def step(eager=False):
         finish()
         if args.graph and not eager:                 # the whole step as ONE HIP graph (raw2logit_amd/graphs.py)
-            graph_step.replay()
+            out = graph_step.replay()
+            if last is not None:
+                last['output'] = out
             return
         for p in params:
             p.grad = None
         y = fwd(raw)
         y.backward(cot)
+        if last is not None:
+            last['output'] = y
         if group_on:                                 # data-parallel sum of the 132-float ISP gradient, asynchronous
             pending.append(F_.GradAllReduce(params, dist.group.WORLD))
 
@@ -801,6 +855,13 @@ def main():
 
     # the contract's measurement: W untimed warm-up steps, then exactly K steps between barrier + synchronize
     dt = clock.time_steps(step, args.steps, args.warmup, finish)
+    if last is not None:
+        # the last timed step's output and gradients (its all-reduce has landed: time_steps ends with finish()).  Not the
+        # BatchNorm running statistics: they depend on how many untimed pre-roll steps a wall-clock budget allowed
+        if rank == 0:
+            dump_outputs(args.dump_outputs, dict(last, **{'grad.' + n: p.grad for n, p in model.named_parameters()
+                                                          if p.grad is not None}))
+        last = None
     px_per_step = world * B * S * S
     value = px_per_step * args.steps / dt / 1e6
 

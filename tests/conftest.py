@@ -77,6 +77,30 @@ def build_host_check():
     return HOST_CHECK
 
 
+NO_GPU_SRC = os.path.join(REPO, 'tests', 'emul', 'r2l_no_gpu.c')
+NO_GPU_LIB = os.path.join(REPO, 'tests', '_build', 'libr2l_no_gpu.so')
+
+
+def build_no_gpu():
+    """gcc build of tests/emul/r2l_no_gpu.c: preloaded into a child process, it fails the opens of the GPU's device files, so that
+    the process sees no GPU (see the source for why the CPU-only multi-rank tests need it)."""
+    if os.path.exists(NO_GPU_LIB) and os.path.getmtime(NO_GPU_LIB) >= os.path.getmtime(NO_GPU_SRC):
+        return NO_GPU_LIB
+    os.makedirs(os.path.dirname(NO_GPU_LIB), exist_ok=True)
+    tmp = NO_GPU_LIB + f'.{os.getpid()}.tmp'
+    subprocess.run(['gcc', '-O2', '-Wall', '-Wextra', '-Werror', '-shared', '-fPIC', NO_GPU_SRC, '-o', tmp, '-ldl'], check=True)
+    os.replace(tmp, NO_GPU_LIB)
+    return NO_GPU_LIB
+
+
+def cpu_only_env(env):
+    """`env` (a dict, changed in place and returned) for the child processes of a CPU-only test: they cannot open the GPU, on a
+    machine that has one as on one that has none"""
+    pre = env.get('LD_PRELOAD')
+    env['LD_PRELOAD'] = (pre + ' ' if pre else '') + build_no_gpu()
+    return env
+
+
 HOOKS_LIB = os.path.join(REPO, 'tests', '_build', 'libr2l_isp_hooks.so')
 
 

@@ -12,7 +12,9 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _run(extra_args, extra_env, timeout=600):
-    env = dict(os.environ, R2L_BENCH_BACKEND='gloo', R2L_BENCH_DEVICE='emulation')
+    import conftest
+    # (the launcher and its ranks see no GPU, wherever the test runs: conftest.cpu_only_env)
+    env = conftest.cpu_only_env(dict(os.environ, R2L_BENCH_BACKEND='gloo', R2L_BENCH_DEVICE='emulation'))
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
     env.update(extra_env)

@@ -26,18 +26,28 @@ def _free_port():
 def _spawn_ranks(fn, world, emul_path, out_dir):
     """mp.spawn over a free port; started over ONCE if the rendezvous itself failed (the port probed free was taken before rank 0
     bound it -- seen once in this round's CPU runs while another process was opening sockets -- or a peer could not connect):
-    never on an assertion of a worker"""
-    for attempt in (0, 1):
-        try:
-            return mp.spawn(fn, args=(world, _free_port(), emul_path, out_dir), nprocs=world, join=True)
-        except Exception as e:                       # noqa: BLE001
-            text = str(e)
-            rendezvous = any(k in text for k in ('Address already in use', 'EADDRINUSE', 'Connection refused', 'Connection reset',
-                                                 'connect() timed out', 'failed to connect', 'The server socket has failed',
-                                                 'DistNetworkError', 'DistStoreError', 'Broken pipe'))
-            if attempt == 1 or not rendezvous or 'AssertionError' in text:
-                raise
-            print(f'test_distributed: rendezvous failed ({text[-300:]!r}); starting the {world} ranks over on another port')
+    never on an assertion of a worker.  The ranks see no GPU (conftest.cpu_only_env), wherever the test runs."""
+    import conftest
+    saved = os.environ.get('LD_PRELOAD')
+    conftest.cpu_only_env(os.environ)                # (the spawned interpreters start with this process's environment)
+    try:
+        for attempt in (0, 1):
+            try:
+                return mp.spawn(fn, args=(world, _free_port(), emul_path, out_dir), nprocs=world, join=True)
+            except Exception as e:                   # noqa: BLE001
+                text = str(e)
+                rendezvous = any(k in text for k in ('Address already in use', 'EADDRINUSE', 'Connection refused',
+                                                     'Connection reset', 'connect() timed out', 'failed to connect',
+                                                     'The server socket has failed', 'DistNetworkError', 'DistStoreError',
+                                                     'Broken pipe'))
+                if attempt == 1 or not rendezvous or 'AssertionError' in text:
+                    raise
+                print(f'test_distributed: rendezvous failed ({text[-300:]!r}); starting the {world} ranks over on another port')
+    finally:
+        if saved is None:
+            os.environ.pop('LD_PRELOAD', None)
+        else:
+            os.environ['LD_PRELOAD'] = saved
 
 
 def _worker(rank, world, port, emul_path, out_dir):

@@ -36,8 +36,10 @@ def lockstep_lib():
 
 @pytest.mark.parametrize('groups', GROUPS, ids=['+'.join(g) for g in GROUPS])
 def test_kernels_in_lock_step_under_address_sanitizer(groups, lockstep_lib):
-    env = dict(os.environ, LD_PRELOAD=_asan_runtime(), ASAN_OPTIONS='detect_leaks=0:abort_on_error=0',
-               UBSAN_OPTIONS='print_stacktrace=1:halt_on_error=1', OMP_NUM_THREADS='1')
+    # (no GPU for the checks, wherever they run -- conftest.cpu_only_env: on a GPU machine torch would initialise HIP in them, and
+    # the C++ exceptions thrown inside that initialisation trip ASan's __cxa_throw interceptor)
+    env = conftest.cpu_only_env(dict(os.environ, LD_PRELOAD=_asan_runtime(), ASAN_OPTIONS='detect_leaks=0:abort_on_error=0',
+                                     UBSAN_OPTIONS='print_stacktrace=1:halt_on_error=1', OMP_NUM_THREADS='1'))
     if os.environ.get('R2L_LOCKSTEP_FULL') != '1':
         env['R2L_LOCKSTEP_QUICK'] = '1'
     r = subprocess.run([sys.executable, os.path.join(HERE, 'lockstep_checks.py'), lockstep_lib, *groups],
@@ -63,8 +65,8 @@ def test_two_gloo_ranks_on_the_lock_step_emulation(lockstep_lib, emulation, tmp_
     from oracle import isp_oracle as orc
     from raw2logit_amd.processing.pipeline_torch import ParametrizedProcessing
     world = 2
-    add = dict(LD_PRELOAD=_asan_runtime(), ASAN_OPTIONS='detect_leaks=0', UBSAN_OPTIONS='print_stacktrace=1:halt_on_error=1',
-               R2L_BWD_PLANES='1', OMP_NUM_THREADS='1')
+    add = conftest.cpu_only_env(dict(LD_PRELOAD=_asan_runtime(), ASAN_OPTIONS='detect_leaks=0',
+                                     UBSAN_OPTIONS='print_stacktrace=1:halt_on_error=1', R2L_BWD_PLANES='1', OMP_NUM_THREADS='1'))
     old = {k: os.environ.get(k) for k in add}
     os.environ.update(add)
     try:
