@@ -330,6 +330,24 @@ int r2l_add_noise(const float *x, const float *noise, float std, float *y, size_
 int r2l_add_noise_philox(const float *x, float *y, float std, unsigned long long seed, unsigned long long offset,
                          size_t n, void *stream);
 
+/* ---- strong augmentation (utils/augmentation.py:77-84: flips, RandomRotation(90) NEAREST, AddGaussianNoise,
+ * RandomAdjustSharpness(0.5), torchvision 0.10 semantics).  x, y: N planes of H x W float32, C channels per image
+ * (N % C == 0).  One forward launch:
+ *   v(q) = x[flip(src(q))] or `fill` outside the frame, src = the nearest sample of torchvision's rotation grid
+ *          (txx, txy, tyx, tyy: theta^T / [W/2, H/2] in float32, as _gen_affine_grid computes it; rotate = 0: identity),
+ *          + noise_std * n(key, noise_offset, q) when noise_key (device int64[1]) is non-null -- the deviates of
+ *          r2l_add_noise_philox at the flat output index;
+ *   y(q) = clamp(r v + (1 - r) D(v), 0, 1), r = sharpness, when sharpness >= 0 (C in {1, 3}; frames with H or W <= 2
+ *          come back unsharpened); clamp_mask (N*H*W bytes, may be null) then receives 0 <= pre-clamp <= 1.
+ * The backward (at most two launches, no atomics) takes the same geometry and sharpness, the forward's clamp mask and
+ * an N*H*W float work plane when the sharpness was on.  Results do not depend on the launch shape.            */
+int r2l_augment_strong_fwd(const float *x, float *y, unsigned char *clamp_mask, int N, int C, int H, int W, int hflip,
+                           int vflip, int rotate, float txx, float txy, float tyx, float tyy, float fill, float noise_std,
+                           const long long *noise_key, unsigned long long noise_offset, double sharpness, void *stream);
+int r2l_augment_strong_bwd(const float *grad_y, float *grad_x, const unsigned char *clamp_mask, float *work, int N, int C,
+                           int H, int W, int hflip, int vflip, int rotate, float txx, float txy, float tyx, float tyy,
+                           double sharpness, void *stream);
+
 /* ---- adversarial auxiliary losses between the outputs of two processors (SURVEY.md section 8f rank 2;
  * AuxLoss, utils/base.py:346-358: img1 = the default processor's output, img2 = the adversarial processor's).
  *   r2l_ssim_fwd   mean of the SSIM map, window_size 11, sigma 1.5, zero padding, per channel

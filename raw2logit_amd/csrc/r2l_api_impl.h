@@ -23,6 +23,7 @@
 #include "r2l_static_menon.h"
 #include "r2l_staged_kernels.h"
 #include "r2l_aux_kernels.h"
+#include "r2l_augment_strong.h"
 
 static thread_local std::string r2l_err;
 static int r2l_fail(int code, const std::string& msg) {
@@ -482,6 +483,10 @@ R2L_KERNEL(r2l_launch_aug, R2LAugArgs, r2l_aug_block, 4)
 R2L_KERNEL(r2l_launch_aug_tiled, R2LAugTiledArgs, r2l_aug_tiled_block, R2L_AUG_LDS_FLOATS)
 R2L_KERNEL(r2l_launch_axpy, R2LAxpyArgs, r2l_axpy_block, 4)
 R2L_KERNEL(r2l_launch_philox_noise, R2LPhiloxArgs, r2l_philox_noise_block, 4)
+R2L_KERNEL(r2l_launch_strong_fwd_flat, R2LStrongArgs, r2l_strong_fwd_flat_block, 4)
+R2L_KERNEL(r2l_launch_strong_fwd_sharp, R2LStrongArgs, r2l_strong_fwd_sharp_block, R2L_AUGS_LDS_FLOATS)
+R2L_KERNEL(r2l_launch_strong_bwd_sharp, R2LStrongBwdArgs, r2l_strong_bwd_sharp_block, 4)
+R2L_KERNEL(r2l_launch_strong_bwd_rot, R2LStrongBwdArgs, r2l_strong_bwd_rot_block, 4)
 R2L_KERNEL(r2l_launch_ssim, R2LSsimArgs, r2l_ssim_block, R2L_SSIM_LDS_FLOATS)
 R2L_KERNEL(r2l_launch_ssim_bwd, R2LSsimBwdArgs, r2l_ssim_bwd_block, R2L_SSIM_BWD_LDS_FLOATS)
 R2L_KERNEL(r2l_launch_l2, R2LL2Args, r2l_l2_block, R2L_RED_FLOATS_N(1))
@@ -2080,6 +2085,80 @@ int r2l_add_noise_philox(const float* x, float* y, float std, unsigned long long
   size_t g = ((n + 3) / 4 + R2L_NT - 1) / R2L_NT;
   if (g > 8192) g = 8192;
   return r2l_launch_philox_noise(a, (int)g, stream);
+}
+
+// ---- strong augmentation (utils/augmentation.py:77-84; r2l_augment_strong.h) ------------------------------------
+static_assert(R2L_NT == (R2L_AUGS_TW / 4) * R2L_AUGS_TH, "one lane per 4 output pixels of the sharpness tile");
+static int r2l_strong_geom(const char* who, int N, int C, int H, int W, int hflip, int vflip, int rotate, float txx,
+                           float txy, float tyx, float tyy, R2LStrongGeom& g) {
+  if (N < 1 || C < 1 || H < 1 || W < 1 || N % C || (size_t)N > ((size_t)1 << 24) || (size_t)H * W > ((size_t)1 << 29))
+    return r2l_fail(-1, std::string(who) + ": bad dimensions (N planes, a multiple of C, of H x W)");
+  if (rotate && !(isfinite(txx) && isfinite(txy) && isfinite(tyx) && isfinite(tyy)))
+    return r2l_fail(-1, std::string(who) + ": non-finite rotation coefficients");
+  g = R2LStrongGeom{N, H, W, hflip != 0, vflip != 0, rotate != 0, txx, txy, tyx, tyy};
+  return 0;
+}
+// sharpness in effect?  (adjust_sharpness: C in {1, 3} is checked first, frames of H or W <= 2 come back unchanged)
+static int r2l_strong_sharp(const char* who, double sharpness, int C, int H, int W, bool& on) {
+  on = false;
+  if (sharpness != sharpness) return r2l_fail(-1, std::string(who) + ": sharpness factor is NaN");
+  if (sharpness < 0) return 0;
+  if (C != 1 && C != 3) return r2l_fail(-1, std::string(who) + ": the sharpness adjustment needs 1 or 3 channels");
+  on = H > 2 && W > 2;
+  return 0;
+}
+static int r2l_strong_flat_grid(const R2LStrongGeom& g) {
+  const size_t nch = (size_t)g.N * g.H * ((g.W + 3) / 4);
+  size_t n = (nch + R2L_NT - 1) / R2L_NT;
+  if (n > 8192) n = 8192;
+  return r2l_env_int("R2L_GRID_AUGS", (int)n);
+}
+int r2l_augment_strong_fwd(const float* x, float* y, unsigned char* clamp_mask, int N, int C, int H, int W, int hflip,
+                           int vflip, int rotate, float txx, float txy, float tyx, float tyy, float fill, float noise_std,
+                           const long long* noise_key, unsigned long long noise_offset, double sharpness, void* stream) {
+  const char* who = "r2l_augment_strong_fwd";
+  if (!x || !y) return r2l_fail(-1, std::string(who) + ": null pointer");
+  R2LStrongArgs a;
+  if (int e = r2l_strong_geom(who, N, C, H, W, hflip, vflip, rotate, txx, txy, tyx, tyy, a.g)) return e;
+  bool sharp;
+  if (int e = r2l_strong_sharp(who, sharpness, C, H, W, sharp)) return e;
+  if (!isfinite(fill) || (noise_key && !isfinite(noise_std)))
+    return r2l_fail(-1, std::string(who) + ": non-finite fill / noise std");
+  a.x = x;
+  a.y = y;
+  a.mask = sharp ? clamp_mask : nullptr;
+  a.key = noise_key;
+  a.fill = fill;
+  a.std = noise_std;
+  a.r = (float)sharpness;
+  a.s = (float)(1.0 - sharpness);
+  a.offset = noise_offset;
+  if (!sharp) return r2l_launch_strong_fwd_flat(a, r2l_strong_flat_grid(a.g), stream);
+  const long ntiles = (long)N * ((H + R2L_AUGS_TH - 1) / R2L_AUGS_TH) * ((W + R2L_AUGS_TW - 1) / R2L_AUGS_TW);
+  return r2l_launch_strong_fwd_sharp(a, r2l_env_int("R2L_GRID_AUGS", (int)(ntiles < R2L_MAX_BLOCKS ? ntiles : R2L_MAX_BLOCKS)),
+                                     stream);
+}
+int r2l_augment_strong_bwd(const float* grad_y, float* grad_x, const unsigned char* clamp_mask, float* work, int N, int C,
+                           int H, int W, int hflip, int vflip, int rotate, float txx, float txy, float tyx, float tyy,
+                           double sharpness, void* stream) {
+  const char* who = "r2l_augment_strong_bwd";
+  if (!grad_y || !grad_x) return r2l_fail(-1, std::string(who) + ": null pointer");
+  R2LStrongBwdArgs a;
+  if (int e = r2l_strong_geom(who, N, C, H, W, hflip, vflip, rotate, txx, txy, tyx, tyy, a.g)) return e;
+  bool sharp;
+  if (int e = r2l_strong_sharp(who, sharpness, C, H, W, sharp)) return e;
+  if (sharp && (!clamp_mask || !work))
+    return r2l_fail(-1, std::string(who) + ": the sharpness adjoint needs the forward's clamp mask and an N*H*W work plane");
+  a.gy = grad_y;
+  a.mask = clamp_mask;
+  a.gv = sharp ? work : (float*)grad_y;
+  a.gx = grad_x;
+  a.r = (float)sharpness;
+  a.s = (float)(1.0 - sharpness);
+  const int grid = r2l_strong_flat_grid(a.g);
+  if (sharp)
+    if (int e = r2l_launch_strong_bwd_sharp(a, grid, stream)) return e;
+  return r2l_launch_strong_bwd_rot(a, grid, stream);
 }
 
 // ---- adversarial auxiliary losses (utils/ssim.py, utils/base.py:342-358) -------------------------------
