@@ -97,46 +97,6 @@ static void r2l_time_end(hipStream_t s, R2LTimedLaunch& t) {
   std::lock_guard<std::mutex> g(r2l_timing_mutex);
   r2l_timed.push_back(t);
 }
-// Diagnostic builds (-DR2L_TEST_HOOKS) can put something in front of a launch whose name contains one of the comma-separated
-// substrings of an environment variable, outside the launch's timing events (tests/experiments/mall_xcd_probe.py):
-//   R2L_EXP_FLUSH  a pass that reads and re-writes a 768 MB scratch allocation (evicts the L2s and the 256 MB memory-side
-//                  cache: what the kernel costs when its predecessor left it nothing);
-//   R2L_EXP_TWICE  an untimed launch of the same kernel (what it costs when everything it touches was touched just now).
-#ifdef R2L_TEST_HOOKS
-__global__ __launch_bounds__(256) void r2l_exp_flush_kernel(float4* p, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-    float4 v = p[i];
-    v.x += 1.f;
-    p[i] = v;
-  }
-}
-static bool r2l_exp_match(const char* env, const char* name) {
-  const char* s = getenv(env);
-  if (!s || !*s) return false;
-  std::string list(s), nm(name);
-  size_t pos = 0;
-  while (pos <= list.size()) {
-    size_t c = list.find(',', pos);
-    if (c == std::string::npos) c = list.size();
-    const std::string tok = list.substr(pos, c - pos);
-    if (!tok.empty() && (tok == "all" || nm.find(tok) != std::string::npos)) return true;
-    pos = c + 1;
-  }
-  return false;
-}
-static void r2l_exp_pre_launch(const char* name, hipStream_t s) {
-  if (!r2l_exp_match("R2L_EXP_FLUSH", name)) return;
-  static float4* buf = nullptr;
-  const size_t n = ((size_t)768 << 20) / sizeof(float4);
-  if (!buf && hipMalloc((void**)&buf, n * sizeof(float4)) != hipSuccess) return;
-  hipLaunchKernelGGL(r2l_exp_flush_kernel, dim3(4096), dim3(256), 0, s, buf, n);
-}
-#define R2L_PRE_LAUNCH(name, stream) r2l_exp_pre_launch(name, (hipStream_t)(stream))
-#define R2L_TWICE(name) r2l_exp_match("R2L_EXP_TWICE", name)
-#else
-#define R2L_PRE_LAUNCH(name, stream)
-#define R2L_TWICE(name) false
-#endif
 #define R2L_KERNEL(name, ArgsT, blockfn, LDS_FLOATS) R2L_KERNEL_OCC(name, ArgsT, blockfn, LDS_FLOATS, 1)
 // LDS-free kernels with their own workgroup size (independent wavefronts)
 #define R2L_KERNEL_NT(name, ArgsT, blockfn, NT, WAVES_PER_SIMD)                                 \
@@ -146,8 +106,6 @@ static void r2l_exp_pre_launch(const char* name, hipStream_t s) {
   static int name(const ArgsT& a, int grid, void* stream) {                                    \
     R2LTimedLaunch t_;                                                                         \
     const bool timed_ = r2l_timing_on;                                                         \
-    if (R2L_TWICE(#name)) hipLaunchKernelGGL(name##_kernel, dim3(grid), dim3(NT), 0, (hipStream_t)stream, a); \
-    R2L_PRE_LAUNCH(#name, stream);                                                             \
     if (timed_) r2l_time_begin(#name "_kernel", (hipStream_t)stream, t_);                      \
     hipLaunchKernelGGL(name##_kernel, dim3(grid), dim3(NT), 0, (hipStream_t)stream, a);       \
     if (timed_) r2l_time_end((hipStream_t)stream, t_);                                         \
@@ -164,8 +122,6 @@ static void r2l_exp_pre_launch(const char* name, hipStream_t s) {
   static int name(const ArgsT& a, int grid, void* stream) {                                    \
     R2LTimedLaunch t_;                                                                         \
     const bool timed_ = r2l_timing_on;                                                         \
-    if (R2L_TWICE(#name)) hipLaunchKernelGGL(name##_kernel, dim3(grid), dim3(NT), 0, (hipStream_t)stream, a); \
-    R2L_PRE_LAUNCH(#name, stream);                                                             \
     if (timed_) r2l_time_begin(#name "_kernel", (hipStream_t)stream, t_);                      \
     hipLaunchKernelGGL(name##_kernel, dim3(grid), dim3(NT), 0, (hipStream_t)stream, a);       \
     if (timed_) r2l_time_end((hipStream_t)stream, t_);                                         \
@@ -181,8 +137,6 @@ static void r2l_exp_pre_launch(const char* name, hipStream_t s) {
   static int name(const ArgsT& a, int grid, void* stream) {                                    \
     R2LTimedLaunch t_;                                                                         \
     const bool timed_ = r2l_timing_on;                                                         \
-    if (R2L_TWICE(#name)) hipLaunchKernelGGL(name##_kernel, dim3(grid), dim3(R2L_NT), 0, (hipStream_t)stream, a); \
-    R2L_PRE_LAUNCH(#name, stream);                                                             \
     if (timed_) r2l_time_begin(#name "_kernel", (hipStream_t)stream, t_);                      \
     hipLaunchKernelGGL(name##_kernel, dim3(grid), dim3(R2L_NT), 0, (hipStream_t)stream, a);   \
     if (timed_) r2l_time_end((hipStream_t)stream, t_);                                         \
@@ -198,8 +152,6 @@ static void r2l_exp_pre_launch(const char* name, hipStream_t s) {
   static int name(const ArgsT& a, int grid, void* stream) {                                    \
     R2LTimedLaunch t_;                                                                         \
     const bool timed_ = r2l_timing_on;                                                         \
-    if (R2L_TWICE(#name)) hipLaunchKernelGGL(name##_kernel, dim3(grid), dim3(R2L_NT), 0, (hipStream_t)stream, a); \
-    R2L_PRE_LAUNCH(#name, stream);                                                             \
     if (timed_) r2l_time_begin(#name "_kernel", (hipStream_t)stream, t_);                      \
     hipLaunchKernelGGL(name##_kernel, dim3(grid), dim3(R2L_NT), 0, (hipStream_t)stream, a);   \
     if (timed_) r2l_time_end((hipStream_t)stream, t_);                                         \
@@ -232,23 +184,16 @@ R2L_KERNEL(r2l_launch_reduce_rows, R2LReduceRowsArgs, r2l_reduce_rows_block, 2 *
 #ifndef R2L_OCC_BWD2
 #define R2L_OCC_BWD2 4
 #endif
-#if R2L_OCC_BWD2 >= 4 && R2L_B2_PREFETCH
-#error "bwd2 at two workgroups per CU needs -DR2L_B2_PREFETCH=0 -DR2L_RPI_ADJ=3 (128 VGPRs)"
-#endif
 // hot instantiation (frames that tile exactly, no additive layer) + the general ones; each again for 16-bit
 // container frames (compile-time, so that the float32 kernels carry no decode code)
 R2L_KERNEL_V(r2l_launch_fwd, R2LFwdArgs, R2L_LDS3(GFwd), R2L_OCC_FWD, r2l_fwd_block<GFwd, false, false, false>)
 R2L_KERNEL_V(r2l_launch_fwd_ragged, R2LFwdArgs, R2L_LDS3(GFwd), 2, r2l_fwd_block<GFwd, false, true, false>)
-R2L_KERNEL_V(r2l_launch_fwd_add, R2LFwdArgs, R2L_LDS3(GFwd), 2, r2l_fwd_block<GFwd, true, true, false>)
 // the additive layer on frames that tile exactly -- the reference's only case: its layer is 256 x 256 (pipeline_torch.py:130)
 R2L_KERNEL_V(r2l_launch_fwd_add_exact, R2LFwdArgs, R2L_LDS3(GFwd), R2L_OCC_FWD, r2l_fwd_block<GFwd, true, false, false>)
 #ifndef R2L_SERIAL
 // the forward as a row-streaming kernel (r2l_param_stream.h): NW wavefronts side by side cover 256 * NW columns
 #ifndef R2L_FS_OCC
 #define R2L_FS_OCC 3
-#endif
-#ifndef R2L_FS_STATS_KERNEL
-#define R2L_FS_STATS_KERNEL 1
 #endif
 #ifndef R2L_FS_MINBAND
 #define R2L_FS_MINBAND 16  // rows: shortest band of the row-streaming forward (7 halo rows of luma per band)
@@ -329,7 +274,6 @@ R2L_KERNEL_V(r2l_launch_bwd1_saved, R2LBwd1Args, R2L_LDS3(GBwd1) + GBwd1::PAD + 
 R2L_KERNEL_V(r2l_launch_bwd1_saved_u16, R2LBwd1Args, R2L_LDS3(GBwd1) + GBwd1::PAD + R2L_B1_FRAME_FLOATS, R2L_OCC_BWD1S, r2l_bwd1_block<GBwd1, false, false, true, true>)
 // (frames that do not tile by 64 below 4 Mi px take r2l_launch_bwd1_ragged -- Y' recomputed in LDS -- also when the forward kept
 // Y': the kept-plane form of the general instantiation needed 76 B of scratch per lane, round 6)
-R2L_KERNEL_V(r2l_launch_bwd1_add, R2LBwd1Args, R2L_LDS3(GBwd1), 2, r2l_bwd1_block<GBwd1, true, true, false>)
 R2L_KERNEL_V(r2l_launch_bwd1_add_exact, R2LBwd1Args, R2L_LDS3(GBwd1), 2, r2l_bwd1_block<GBwd1, true, false, false>)
 #ifndef R2L_SERIAL
 // kernel B1 as two passes over planes (r2l_param_plane_bwd.h): where the forward kept Y' and no epilogue / additive layer
@@ -359,11 +303,9 @@ R2L_BNR_KERNEL(r2l_launch_bnr_planes_epi_u16, true, true)
 R2L_KERNEL_V(r2l_launch_bwd2, R2LBwd2Args, R2L_LDS3(GBwd2), R2L_OCC_BWD2, r2l_bwd2_block<GBwd2, false>)
 R2L_KERNEL_V(r2l_launch_fwd_u16, R2LFwdArgs, R2L_LDS3(GFwd), R2L_OCC_FWD, r2l_fwd_block<GFwd, false, false, true>)
 R2L_KERNEL_V(r2l_launch_fwd_ragged_u16, R2LFwdArgs, R2L_LDS3(GFwd), 2, r2l_fwd_block<GFwd, false, true, true>)
-R2L_KERNEL_V(r2l_launch_fwd_add_u16, R2LFwdArgs, R2L_LDS3(GFwd), 2, r2l_fwd_block<GFwd, true, true, true>)
 R2L_KERNEL_V(r2l_launch_fwd_add_exact_u16, R2LFwdArgs, R2L_LDS3(GFwd), R2L_OCC_FWD, r2l_fwd_block<GFwd, true, false, true>)
 R2L_KERNEL_V(r2l_launch_bwd1_u16, R2LBwd1Args, R2L_LDS3(GBwd1), R2L_OCC_BWD1, r2l_bwd1_block<GBwd1, false, false, true>)
 R2L_KERNEL_V(r2l_launch_bwd1_ragged_u16, R2LBwd1Args, R2L_LDS3(GBwd1), 2, r2l_bwd1_block<GBwd1, false, true, true>)
-R2L_KERNEL_V(r2l_launch_bwd1_add_u16, R2LBwd1Args, R2L_LDS3(GBwd1), 2, r2l_bwd1_block<GBwd1, true, true, true>)
 R2L_KERNEL_V(r2l_launch_bwd1_add_exact_u16, R2LBwd1Args, R2L_LDS3(GBwd1), 2, r2l_bwd1_block<GBwd1, true, false, true>)
 R2L_KERNEL_V(r2l_launch_bwd2_u16, R2LBwd2Args, R2L_LDS3(GBwd2), R2L_OCC_BWD2, r2l_bwd2_block<GBwd2, true>)
 // 14 KB of LDS instead of 68 KB: 8 workgroups' worth of loads in flight per CU instead of 2
@@ -536,32 +478,6 @@ static int r2l_band_rows(int B, int H, int W, long slots, const char* env) {
     }
   }
   return (r2l_env_int(env, bh) + 5) / 6 * 6;
-}
-
-// XCD windows of the band passes (r2l_xcd_window): neighbouring workgroups per XCD; measured per pass (profiles/r05_mall_xcd.txt)
-#ifndef R2L_XCDM_FS
-#define R2L_XCDM_FS 0   // statistics pass (row-streaming forward)
-#endif
-#ifndef R2L_XCDM_FA
-#define R2L_XCDM_FA 0   // apply pass / luma pass / statistics from the plane
-#endif
-#ifndef R2L_XCDM_BP
-#define R2L_XCDM_BP 0   // kernel B1's plane pass
-#endif
-#ifndef R2L_XCDM_HB
-#define R2L_XCDM_HB 0   // blur sums + blur adjoint
-#endif
-#ifndef R2L_XCDM_B2S
-#define R2L_XCDM_B2S 0  // kernel B2's sums pass
-#endif
-static int r2l_xcdm(const char* env, int dflt) {
-#ifdef R2L_TEST_HOOKS
-  const char* s = getenv(env);
-  if (s && *s) dflt = atoi(s);
-#else
-  (void)env;
-#endif
-  return (dflt > 0 && (dflt & (dflt - 1)) == 0) ? dflt : 0;  // a power of two, or off
 }
 
 // ---- workspace ----------------------------------------------------------------------------------
@@ -773,8 +689,7 @@ static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float*
     const long resident = 256L * (12 / nwv);
     long nband = r2l_env_int("R2L_FS_BAND", 0) ? (H + r2l_env_int("R2L_FS_BAND", 32) - 1) / r2l_env_int("R2L_FS_BAND", 32)
                                                : resident / B;
-    const int minband = r2l_env_int("R2L_FS_MINBAND", R2L_FS_MINBAND);
-    if (nband > H / minband) nband = H / minband;
+    if (nband > H / R2L_FS_MINBAND) nband = H / R2L_FS_MINBAND;
     if (nband < 1) nband = 1;
     fa.band_h = (int)((H + nband - 1) / nband);
     fa.band_h += fa.band_h & 1;
@@ -785,7 +700,7 @@ static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float*
     long cap = r2l_env_int("R2L_GRID_FWD", (int)(resident < R2L_MAX_BLOCKS ? resident : R2L_MAX_BLOCKS));
     if (cap > R2L_MAX_BLOCKS) cap = R2L_MAX_BLOCKS;
     const int sgrid = (int)(nitems < cap ? nitems : cap);
-    fa.tree = R2LTree{ws.part_small, nullptr, ws.gpartial, (stats && !(r2l_env_int("R2L_EXP_NO_TREE", 0) & 1)) ? ws.counters : nullptr, 12, 0};
+    fa.tree = R2LTree{ws.part_small, nullptr, ws.gpartial, stats ? ws.counters : nullptr, 12, 0};
     fa.stats_out = stats;
     if (fin)
       fa.fin = *fin;
@@ -803,7 +718,6 @@ static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float*
           r2l_launch_fwd_stream_epi_w8_u16}}};
     const bool epi = ep && ep->on && out;
     fa.ep = epi ? *ep : R2LEpi{0, 0, 0, 0};
-    fa.xcdm = r2l_xcdm("R2L_XCD_FS", R2L_XCDM_FS);
     // The passes on the kept luma plane (r2l_param_stream.h: r2l_fwd_luma_block, r2l_fwd_apply_block): independent
     // wavefronts, one per (image, band, 256-column strip); band heights: r2l_band_rows
     const long nstrip = (W + 255) / 256;
@@ -817,7 +731,6 @@ static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float*
     if (!out && stats && (flags & R2L_F_SPLIT_STATS) && kept_ok && split) {
       R2LFwdStreamArgs la = fa;
       la.stat_partial = nullptr;
-      la.xcdm = fa.xcdm = r2l_xcdm("R2L_XCD_FA", R2L_XCDM_FA);
 #ifdef R2L_EXP_STAMPS
       la.tl = (unsigned long long*)ws.debug;
       fa.tl = (unsigned long long*)ws.debug + 8192;
@@ -850,7 +763,6 @@ static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float*
       fa.yp_in = ws.yp;
       fa.yp_out = nullptr;
       fa.stat_partial = nullptr;
-      fa.xcdm = r2l_xcdm("R2L_XCD_FA", R2L_XCDM_FA);
       fa.band_h = band_rows(256L * 4 * R2L_FA_OCC, "R2L_FA_BAND");
       fa.nband = (H + fa.band_h - 1) / fa.band_h;
       const long grid = (long)B * fa.nband * nstrip;
@@ -860,7 +772,6 @@ static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float*
                                             {r2l_launch_fwd_apply_epi, r2l_launch_fwd_apply_epi_u16}};
       return atable[epi ? 1 : 0][raw.u16 ? 1 : 0](fa, (int)((grid + R2L_FA_NWV - 1) / R2L_FA_NWV), stream);
     }
-#if R2L_FS_STATS_KERNEL
     if (!out && stats) {  // the statistics pass: its own instantiation (no output code, fewer live scalars)
       static const launch_t stable[2][4] = {
           {r2l_launch_fwd_stream_stats_w1, r2l_launch_fwd_stream_stats_w2, r2l_launch_fwd_stream_stats_w4,
@@ -869,7 +780,6 @@ static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float*
            r2l_launch_fwd_stream_stats_w8_u16}};
       return stable[raw.u16 ? 1 : 0][nw](fa, sgrid, stream);
     }
-#endif
     return table[epi ? 1 : 0][raw.u16 ? 1 : 0][nw](fa, sgrid, stream);
   }
 #endif
@@ -898,11 +808,11 @@ static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float*
   a.ep = (ep && ep->on && out) ? *ep : R2LEpi{0, 0, 0, 0};
   const bool exact = (H % GFwd::TH == 0) && (W % GFwd::TW == 0);
   int e;
-  if (raw.u16)
-    e = additive ? (exact ? r2l_launch_fwd_add_exact_u16(a, grid, stream) : r2l_launch_fwd_add_u16(a, grid, stream))
+  if (raw.u16)   // (an additive layer means 256 x 256 frames: they tile exactly)
+    e = additive ? r2l_launch_fwd_add_exact_u16(a, grid, stream)
                  : (exact ? r2l_launch_fwd_u16(a, grid, stream) : r2l_launch_fwd_ragged_u16(a, grid, stream));
   else
-    e = additive ? (exact ? r2l_launch_fwd_add_exact(a, grid, stream) : r2l_launch_fwd_add(a, grid, stream))
+    e = additive ? r2l_launch_fwd_add_exact(a, grid, stream)
                  : (exact ? r2l_launch_fwd(a, grid, stream) : r2l_launch_fwd_ragged(a, grid, stream));
   if (e) return e;
   return 0;
@@ -940,10 +850,10 @@ int r2l_bn_bwd_reduce(const float* grad_out, const float* out, const double* tot
   int grid = nitems < (size_t)cap ? (int)nitems : cap;
   // a workspace that went through r2l_isp_fwd / r2l_isp_bwd has valid arrival counters: the last workgroups
   // of the launch finish the reduction; otherwise a second, tiny launch does
-  const bool in_kernel = (flags & R2L_F_FOLDED_VALID) != 0 && !(r2l_env_int("R2L_EXP_NO_TREE", 0) & 2);
+  const bool in_kernel = (flags & R2L_F_FOLDED_VALID) != 0;
   R2LBnReduceArgs a{grad_out, out, ws.part_small, B, H, W,
                     R2LTree{ws.part_small, nullptr, ws.gpartial, in_kernel ? ws.counters : nullptr, 6, 0},
-                    sums, totals, bn_bwd, r2l_env_int("R2L_BNR_ORDER", 0)};
+                    sums, totals, bn_bwd};
   if (int e = r2l_launch_bn_reduce(a, grid, stream)) return e;
   if (in_kernel) return 0;
   R2LReduceRowsArgs r{ws.part_small, sums, grid, 1.0, bn_bwd, nullptr, 0.0, bn_bwd ? totals + 6 : nullptr};
@@ -990,8 +900,6 @@ static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float*
   a1.band_h = 0;
   a1.hp = nullptr;
   a1.band_hb = 0;
-  a1.xcdm = r2l_xcdm("R2L_XCD_BP", R2L_XCDM_BP);
-  a1.xcdm_hb = r2l_xcdm("R2L_XCD_HB", R2L_XCDM_HB);
   if (a1.ep.on && additive) return r2l_fail(-3, "r2l_isp_bwd: no output epilogue with an additive layer");
   const bool exact = (H % GBwd1::TH == 0) && (W % GBwd1::TW == 0);
   int g1p = 0;  // workgroups of the plane passes, when they run
@@ -1032,10 +940,10 @@ static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float*
   } else if (saved && exact)
     e1 = raw.u16 ? r2l_launch_bwd1_saved_u16(a1, g1, stream) : r2l_launch_bwd1_saved(a1, g1, stream);
   else if (raw.u16)   // (frames that do not tile by 64: Y' recomputed in LDS, kept or not -- a1.yp is not read)
-    e1 = additive ? (exact ? r2l_launch_bwd1_add_exact_u16(a1, g1, stream) : r2l_launch_bwd1_add_u16(a1, g1, stream))
+    e1 = additive ? r2l_launch_bwd1_add_exact_u16(a1, g1, stream)   // (additive: 256 x 256 frames, which tile exactly)
                   : (exact ? r2l_launch_bwd1_u16(a1, g1, stream) : r2l_launch_bwd1_ragged_u16(a1, g1, stream));
   else
-    e1 = additive ? (exact ? r2l_launch_bwd1_add_exact(a1, g1, stream) : r2l_launch_bwd1_add(a1, g1, stream))
+    e1 = additive ? r2l_launch_bwd1_add_exact(a1, g1, stream)
                   : (exact ? r2l_launch_bwd1(a1, g1, stream) : r2l_launch_bwd1_ragged(a1, g1, stream));
   if (e1) return e1;
   const int ntiles2 = B * ((H + GBwd2::TH - 1) / GBwd2::TH) * ((W + GBwd2::TW - 1) / GBwd2::TW);
@@ -1043,7 +951,6 @@ static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float*
   const int g2 = r2l_tile_grid(ntiles2, r2l_env_int("R2L_GRID_BWD2", R2L_OCC_BWD2 >= 4 ? 512 : 256));
   R2LBwd2Args a2;
   a2.nmain = 0;
-  a2.xcdm = r2l_xcdm("R2L_XCD_B2S", R2L_XCDM_B2S);
   a2.b1_partial = nullptr;
   a2.b1_n = 0;
   a2.b1_tot = nullptr;
@@ -1071,7 +978,6 @@ static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float*
     a2.tree = R2LTree{nullptr, nullptr, nullptr, nullptr, 0, 0};
     a2.params = nullptr;
     a2.grad_params = nullptr;
-    a2.asym = 0;
     if (!blur_hp)
       if (int e = r2l_launch_bwd2_hp(a2, (int)((hitems + R2L_BP_NWV - 1) / R2L_BP_NWV), stream)) return e;
     a2.band_h = band_rows(256L * 4 * 3, "R2L_B2S_BAND");
@@ -1082,39 +988,22 @@ static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float*
     if (gs > R2L_MAX_BLOCKS) gs = R2L_MAX_BLOCKS;
     // its last workgroups reduce B2's partials; R2L_B2S_HELPERS more workgroups (the grid leaves room for them beside one
     // round of the others) add B1's meanwhile; the last arrival of all unfolds the 155 totals into the 132 gradients
-    const bool tree = !(r2l_env_int("R2L_EXP_NO_TREE", 0) & 4);
-    a2.tree = R2LTree{nullptr, ws.part_b2, ws.gpartial, tree ? ws.counters : nullptr, 0, 0};
+    a2.tree = R2LTree{nullptr, ws.part_b2, ws.gpartial, ws.counters, 0, 0};
     a2.nmain = (int)gs;
     a2.b1_partial = ws.part_b1;
     a2.b1_n = g1w;
     a2.b1_tot = ws.sums;
     a2.params = params;
     a2.grad_params = grad_params;
-    const int grid = (int)gs + (tree ? R2L_B2S_HELPERS : 0);
-    if (int e = raw.u16 ? r2l_launch_bwd2_sums_u16(a2, grid, stream) : r2l_launch_bwd2_sums(a2, grid, stream)) return e;
-    if (tree) return 0;
-    // (diagnostic builds with the in-kernel tree switched off: the three tiny launches of the tile kernels' fallback finish
-    // the sums, so that grad_params is never returned uninitialised)
-    R2LReduceRowsArgs r1{ws.part_b1, ws.sums, g1w, 1.0, nullptr};
-    if (int e = r2l_launch_reduce_rows(r1, R2L_B1_NACC, stream)) return e;
-    R2LReduceRowsArgs r2{ws.part_b2, ws.sums + R2L_B1_NACC, (int)gs, 1.0, nullptr};
-    if (int e = r2l_launch_reduce_rows(r2, R2L_B2_NACC, stream)) return e;
-    R2LUnfoldArgs ua{params, ws.sums, grad_params, 1.0f};
-    return r2l_launch_unfold(ua, 1, stream);
+    const int grid = (int)gs + R2L_B2S_HELPERS;
+    return raw.u16 ? r2l_launch_bwd2_sums_u16(a2, grid, stream) : r2l_launch_bwd2_sums(a2, grid, stream);
   }
 #endif
   const bool in_kernel = g1w <= g2;
   a2.tree = R2LTree{ws.part_b1, ws.part_b2, ws.gpartial, in_kernel ? ws.counters : nullptr, R2L_B1_NACC, g1w};
   a2.params = params;
   a2.grad_params = grad_params;
-  // uneven tile shares for the two workgroups of a CU (r2l_walk_init): measured, no gain -- the younger workgroup is
-  // starved while the older one runs and catches up afterwards, the CU finishes its 16 tiles at the same time whatever the
-  // split (profiles/r03_bwd2_tile_shares.txt).  Even shares (0) are the default; diagnostic builds can sweep it.
-#ifndef R2L_B2_ASYM
-#define R2L_B2_ASYM 0
-#endif
-  a2.asym = (R2L_OCC_BWD2 >= 4 && g2 == 512 && ntiles2 >= 4 * g2) ? r2l_env_int("R2L_B2_ASYM", R2L_B2_ASYM) : 0;
-  if (a2.asym == 1) a2.asym = 0;
+  // (even tile shares: uneven ones for the two workgroups of a CU measured no gain, profiles/r03_bwd2_tile_shares.txt)
   if (int e = raw.u16 ? r2l_launch_bwd2_u16(a2, g2, stream) : r2l_launch_bwd2(a2, g2, stream)) return e;
   if (in_kernel) return 0;
   R2LReduceRowsArgs r1{ws.part_b1, ws.sums, g1w, 1.0, nullptr};
@@ -1249,9 +1138,7 @@ static int r2l_bn_bwd_reduce_planes(const R2LRaw& raw, const float* additive, co
   // (from 6 Mi px: at 64x256x256 = 4 Mi px the whole step, output included, lives in the memory-side cache and reading the output back
   //  is cheaper than recomputing it -- bn_reduce 22.4-23.8 us against 27.1; at 128x256x256 37.2 against 37.5, the step 2 % faster)
   const bool planes = r2l_env_int("R2L_BWD_PLANES", 0) || (size_t)B * H * W >= ((size_t)6 << 20);
-  if (!keep || !r2l_fwd_streams(additive, W) || !planes || r2l_env_int("R2L_BNR_READ_OUT", 0) ||
-      (r2l_env_int("R2L_EXP_NO_TREE", 0) & 2))
-    return 1;
+  if (!keep || !r2l_fwd_streams(additive, W) || !planes) return 1;
   R2LBnrArgs a;
   a.s.raw = raw;
   a.s.F = ws.folded;
@@ -1277,7 +1164,6 @@ static int r2l_bn_bwd_reduce_planes(const R2LRaw& raw, const float* additive, co
   a.s.stats_out = nullptr;
   a.s.fin.bn = nullptr;
   a.s.ep = ep.on ? ep : R2LEpi{0, 0, 0, 0};
-  a.s.xcdm = 0;
   a.gout = grad_out;
   a.sums = ws.bsums;
   a.totals = ws.moments;
@@ -2271,7 +2157,7 @@ size_t r2l_test_debug_offset(int B, int H, int W) {
 #ifdef R2L_EMUL
 // the tile walk of the persistent kernels, replayed on the host: owner[tile] = workgroup id that visits it (or -1), and
 // the number of visits per tile in visits[tile]; returns the largest number of tiles any workgroup takes
-int r2l_test_walk(int B, int H, int W, int nblk, int asym, int* owner, int* visits) {
+int r2l_test_tile_walk(int B, int H, int W, int nblk, int* owner, int* visits) {
   const int ntx = (W + 63) / 64, nty = (H + 63) / 64, ntiles = B * ntx * nty;
   for (int i = 0; i < ntiles; ++i) {
     owner[i] = -1;
@@ -2279,7 +2165,7 @@ int r2l_test_walk(int B, int H, int W, int nblk, int asym, int* owner, int* visi
   }
   int most = 0;
   for (int bid = 0; bid < nblk; ++bid) {
-    R2LTileWalk w = r2l_walk_init(B, H, W, 64, 64, bid, nblk, asym);
+    R2LTileWalk w = r2l_walk_init(B, H, W, 64, 64, bid, nblk);
     R2LTile t;
     int n = 0;
     while (r2l_walk_next(w, H, W, 64, 64, t)) {

@@ -40,14 +40,6 @@
 #else
 #define R2L_LANE_RETIRES()
 #endif
-// DIAGNOSTIC BUILDS, TIMING ONLY (-DR2L_EXP_NO_HALO; results are wrong): the band passes fetch their halo rows from inside the band
-// (the row clamped to [y0, y1 - 1]: a line the wavefront itself touched a few steps ago), i.e. every plane is fetched exactly once --
-// the upper bound of what bands that share their halo rows in time (odd bands walking bottom-up) could gain
-#ifdef R2L_EXP_NO_HALO
-#define R2L_NH(r) ((r) < y0 ? y0 : ((r) > y1 - 1 ? y1 - 1 : (r)))
-#else
-#define R2L_NH(r) (r)
-#endif
 // workgroup barrier that orders LDS traffic only (see R2L_PHASE_END)
 #if defined(R2L_LOCKSTEP)
 #define R2L_LDS_BARRIER() r2l_ls::wg_barrier()
@@ -124,21 +116,11 @@ typedef float4 r2l_f4;
 typedef float2 r2l_f2;
 // v_log_f32 / v_exp_f32 are base-2 and 1 ULP; inputs here are >= 1e-5 (or exactly 0) so the
 // denormal pre-scaling of logf()/expf() is not needed.  v_rcp_f32 is 1 ULP.
-#ifdef R2L_EXP_NO_TRANS  // DIAGNOSTIC BUILDS, TIMING ONLY (results are wrong): one multiply instead of each transcendental
-R2L_HD float r2l_log2(float x) { return x * 1.0001f; }
-R2L_HD float r2l_exp2(float x) { return x * 0.9999f; }
-R2L_HD float r2l_rcp(float x) { return x * 1.0002f; }
-#else
 R2L_HD float r2l_log2(float x) { return __builtin_amdgcn_logf(x); }
 R2L_HD float r2l_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 R2L_HD float r2l_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-#endif
 // value of the previous / next lane of the 64-lane wavefront (DPP wave shifts; lane 0 / 63 keep their own)
-#ifdef R2L_HAVE_LANE_SHIFTS_OFF  // A/B builds: every lane loads its neighbour columns
-#define R2L_HAVE_LANE_SHIFTS false
-#else
 #define R2L_HAVE_LANE_SHIFTS true
-#endif
 #define R2L_LANE_ID ((int)(threadIdx.x & 63))
 R2L_HD float r2l_wave_shr1(float x) {
   const int i = __builtin_bit_cast(int, x);
@@ -163,22 +145,9 @@ R2L_HD float r2l_row_shl1(float x, float edge) {
 // TB/s).  Round 1's tile kernels did not (profiles/r01_e_static_ab.txt); the row-streaming kernels do, for their
 // STORES (round 5, same buffers, interleaved: bilinear 767 -> 758 us, Malvar2004 830 -> 810, default luma chain 941 -> 927,
 // Malvar2004 + median 1084 -> 1050-1073; profiles/r05_nt_stores.txt), and lose 9-22 % with nontemporal LOADS (the halo rows a
-// neighbouring band re-reads must stay cached): stores nontemporal by default (-DR2L_NT_STORES=0: plain), loads plain
-// (-DR2L_NT_LOADS: the A/B form).
+// neighbouring band re-reads must stay cached): stores nontemporal, loads plain.
 typedef float r2l_v4 __attribute__((ext_vector_type(4)));
-R2L_HD r2l_f4 r2l_stream_load_f4(const float* p) {
-#ifndef R2L_NT_LOADS
-  return *(const r2l_f4*)p;
-#else
-  const r2l_v4 v = __builtin_nontemporal_load((const r2l_v4*)p);
-  r2l_f4 o;
-  o.x = v.x;
-  o.y = v.y;
-  o.z = v.z;
-  o.w = v.w;
-  return o;
-#endif
-}
+R2L_HD r2l_f4 r2l_stream_load_f4(const float* p) { return *(const r2l_f4*)p; }
 // read-once operand of a pure reduction (nontemporal: 6.0 -> 7.0 TB/s on a read-only stream, stream_probe)
 R2L_HD r2l_f4 r2l_load_f4_nt(const float* p) {
   const r2l_v4 v = __builtin_nontemporal_load((const r2l_v4*)p);
@@ -198,21 +167,7 @@ R2L_HD void r2l_store_f4_nt(float* p, const r2l_f4& s) {
   v.w = s.w;
   __builtin_nontemporal_store(v, (r2l_v4*)p);
 }
-#ifndef R2L_NT_STORES
-#define R2L_NT_STORES 1
-#endif
-R2L_HD void r2l_stream_store_f4(float* p, const r2l_f4& s) {
-#if !R2L_NT_STORES
-  *(r2l_f4*)p = s;
-#else
-  r2l_v4 v;
-  v.x = s.x;
-  v.y = s.y;
-  v.z = s.z;
-  v.w = s.w;
-  __builtin_nontemporal_store(v, (r2l_v4*)p);
-#endif
-}
+R2L_HD void r2l_stream_store_f4(float* p, const r2l_f4& s) { r2l_store_f4_nt(p, s); }
 #define R2L_PHASE_BEGIN \
   {                     \
     const int tid = threadIdx.x;
@@ -308,9 +263,6 @@ R2L_HD void r2l_glds16(const float* base, unsigned lane_byte_off, float* lane_sl
 }
 R2L_HD void r2l_glds_wait() {}
 #else
-#ifndef R2L_GLDS_POLICY
-#define R2L_GLDS_POLICY ""  // " nt": A/B builds
-#endif
 R2L_HD void r2l_glds16(const float* base, unsigned lane_byte_off, float* lane_slot) {
   // wave-uniform LDS base = the slot of lane 0, whether or not lane 0 takes part (v_readfirstlane reads the first ACTIVE lane)
   const unsigned lbase = __builtin_amdgcn_readfirstlane(
@@ -319,7 +271,7 @@ R2L_HD void r2l_glds16(const float* base, unsigned lane_byte_off, float* lane_sl
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)gb), hi = __builtin_amdgcn_readfirstlane((unsigned)(gb >> 32));
   const unsigned long long sb = ((unsigned long long)hi << 32) | lo;
   unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" R2L_GLDS_POLICY "\n\ts_mov_b32 m0, %0"
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
                : "=&s"(keep)
                : "v"(lane_byte_off), "s"(sb), "s"(lbase)
                : "memory");
@@ -558,40 +510,6 @@ struct R2LFolded {
 typedef const R2LFolded& R2LFoldedRef;
 #define R2L_FOLDED_REF(ptr) (*(ptr))
 #define R2L_CONSTAS
-#elif defined(R2L_EXP_CONST_WEIGHTS)
-// DIAGNOSTIC BUILD, TIMING ONLY (results are wrong): every folded weight is a compile-time constant, so the kernels issue no
-// scalar loads for them at all -- the upper bound of what hiding the scalar-load waits of a row step could buy
-// (profiles/r05_const_weights.txt)
-constexpr R2LFolded r2l_exp_make_folded() {
-  R2LFolded f{};
-  float v = 0.0131f;
-  for (int i = 0; i < 4; ++i) f.bl[i] = (v += 0.0007f);
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 9; ++j) {
-      f.AY[i][j] = (v += 0.0007f);
-      f.AU[i][j] = (v += 0.0007f);
-      f.AV[i][j] = (v += 0.0007f);
-    }
-  for (int j = 0; j < 9; ++j) f.sharp[j] = (v += 0.0007f);
-  for (int j = 0; j < 25; ++j) f.blur[j] = (v += 0.0007f);
-  for (int j = 0; j < 9; ++j) f.M2[j] = (v += 0.0007f);
-  f.inv_gamma = 0.4545f;
-  f.gamma = 2.2f;
-  for (int i = 0; i < 2; ++i)
-    for (int j = 0; j < 9; ++j)
-      for (int k = 0; k < 2; ++k) {
-        f.AY2[i][j][k] = (v += 0.0007f);
-        f.AU2[i][j][k] = (v += 0.0007f);
-        f.AV2[i][j][k] = (v += 0.0007f);
-      }
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 25; ++j) f.blur_edge[i][j] = (v += 0.0007f);
-  return f;
-}
-static __device__ constexpr R2LFolded r2l_exp_folded = r2l_exp_make_folded();
-typedef const R2LFolded& R2LFoldedRef;
-#define R2L_FOLDED_REF(ptr) (((void)(ptr)), r2l_exp_folded)
-#define R2L_CONSTAS
 #else
 typedef const __attribute__((address_space(4))) R2LFolded& R2LFoldedRef;
 #define R2L_FOLDED_REF(ptr) (*(const __attribute__((address_space(4))) R2LFolded*)(ptr))
@@ -617,36 +535,6 @@ R2L_HD const R2LFolded* r2l_opaque_after(const R2LFolded* p, float dep) {
   return p;
 }
 
-// Workgroup ids are dealt round-robin over the 8 XCDs (id % 8), each with its own 4 MiB L2.  Kernels whose consecutive
-// work items share rows (the band passes: a band re-reads the halo rows of its neighbours) can walk the items through this
-// map: inside every window of 8 M consecutive ids, XCD x takes the M CONTIGUOUS virtual ids [x M, (x + 1) M) -- M
-// neighbouring bands then run on one XCD at about the same time and their shared halo rows are L2 hits instead of second
-// fetches from HBM, while the chip as a whole still works on one compact region (handing each XCD a contiguous EIGHTH of
-// the whole launch is slower than no map at all: eight regions in flight, profiles/r04_ab_static_xcd.txt).
-// R2L_XCD_REMAP = M (0: off).
-#ifndef R2L_XCD_REMAP
-#define R2L_XCD_REMAP 0
-#endif
-R2L_HD int r2l_xcd_contiguous(int bid, int nblk) {
-#if R2L_XCD_REMAP
-  constexpr int M = R2L_XCD_REMAP, G = 8 * M;
-  const int w0 = bid - bid % G;
-  return (w0 + G <= nblk) ? w0 + (bid & 7) * M + ((bid - w0) >> 3) : bid;
-#else
-  (void)nblk;
-  return bid;
-#endif
-}
-
-// The same map with the window size as a launch argument (the band passes of the parametrized step: `m` = neighbouring
-// workgroups per XCD, a power of two, 0 = off).  Only the WORK ITEMS follow the mapped id; partial-sum slots and the
-// reduction trees keep the hardware's workgroup id.
-R2L_HD int r2l_xcd_window(int bid, int nblk, int m) {
-  if (m <= 0) return bid;
-  const int G = 8 * m, w0 = bid & ~(G - 1);
-  return (w0 + G <= nblk) ? w0 + (bid & 7) * m + ((bid - w0) >> 3) : bid;
-}
-
 // Issue priority by PROGRESS.  The wavefronts of a SIMD start together (the band passes are sized for one round of resident
 // wavefronts) and the hardware favours the oldest one whenever several are ready: left alone they finish one after the
 // other, and the last one walks its rows alone with every scalar-load and memory wait exposed (the plane kernels'
@@ -654,11 +542,8 @@ R2L_HD int r2l_xcd_window(int bid, int nblk, int m) {
 // further BEHIND in its band gets the higher priority -- quarter of the band done -> s_setprio 3, 2, 1, 0 -- so the
 // wavefronts of a SIMD advance together and overlap until the end: 64x512x512 step 0.3940 -> 0.3873 ms, the sums pass of
 // the backward 54.9 -> 52.5 us (profiles/r04_progress_prio.txt).  s_setprio takes an immediate: a scalar if-chain.
-// R2L_PROGRESS_PRIO = 0: off; 1: per group of 6 rows; 2: per row step.
-#ifndef R2L_PROGRESS_PRIO_MODE
-#define R2L_PROGRESS_PRIO_MODE 1
-#endif
-#if R2L_PROGRESS_PRIO_MODE && !defined(R2L_EMUL)
+// Set once per group of 6 rows.
+#ifndef R2L_EMUL
 R2L_HD void r2l_progress_prio(int done, int total) {
   const int q4 = done * 4;
   if (q4 < total) __builtin_amdgcn_s_setprio(3);
@@ -667,14 +552,8 @@ R2L_HD void r2l_progress_prio(int done, int total) {
   else __builtin_amdgcn_s_setprio(0);
 }
 #define R2L_PROGRESS_PRIO(done, total) r2l_progress_prio((done), (total))
-#if R2L_PROGRESS_PRIO_MODE == 2
-#define R2L_PROGRESS_PRIO_STEP(done, total) r2l_progress_prio((done), (total))
-#else
-#define R2L_PROGRESS_PRIO_STEP(done, total)
-#endif
 #else
 #define R2L_PROGRESS_PRIO(done, total)
-#define R2L_PROGRESS_PRIO_STEP(done, total)
 #endif
 
 // A kernel's argument block, re-read from the kernarg segment at the point of use: arguments that only the end of a kernel

@@ -99,16 +99,9 @@ R2L_HD int r2l_div(int n, const R2LDiv& dv) { return (int)((r2l_mulhi(dv.m, (uns
 
 struct R2LTileWalk {
   int ntx, nty, ntiles, nper, group, w, k, jstep;
-  int asym;  // > 0: every asym-th round of the walk is a HALF round, served by the older half of the workgroups only
-  R2LDiv dx, dy, dj, dh;
+  R2LDiv dx, dy, dj;
 };
-// asym (experiment, off by default): two workgroups share a CU and the hardware's issue arbitration favours the waves of
-// the one dispatched first (by age): with equal shares the older workgroup of kernel B2 finishes its tiles in ~140 kcycles,
-// the younger one needs ~178.  Workgroups are dispatched in id order, so ids below nblk / 2 are the older ones: with
-// asym = n they take one tile more every n rounds (n = 4, 8 tiles per workgroup on average: 9 vs 7).  The tile ->
-// workgroup map stays a pure function of (bid, nblk): sums do not depend on the schedule.  Measured: the launch takes as
-// long as before -- the CU's throughput, not the split, sets the time (profiles/r03_bwd2_tile_shares.txt).
-R2L_HD R2LTileWalk r2l_walk_init(int B, int H, int W, int TW, int TH, int bid, int nblk, int asym = 0) {
+R2L_HD R2LTileWalk r2l_walk_init(int B, int H, int W, int TW, int TH, int bid, int nblk) {
   R2LTileWalk w;
   w.ntx = (W + TW - 1) / TW;
   w.nty = (H + TH - 1) / TH;
@@ -119,11 +112,9 @@ R2L_HD R2LTileWalk r2l_walk_init(int B, int H, int W, int TW, int TH, int bid, i
   w.w = bid / ngroups;
   w.k = 0;
   w.jstep = nblk / ngroups;
-  w.asym = (asym > 1 && (w.jstep & 1) == 0 && w.jstep >= 2) ? asym : 0;
   w.dx = r2l_div_init(w.ntx);
   w.dy = r2l_div_init(w.nty);
   w.dj = r2l_div_init(w.jstep);
-  w.dh = r2l_div_init(w.jstep > 1 ? w.jstep / 2 : 1);
   return w;
 }
 // k-th tile of a workgroup: block k of `jstep` consecutive tiles, rotated by k tile rows + k tile columns
@@ -133,24 +124,10 @@ R2L_HD R2LTileWalk r2l_walk_init(int B, int H, int W, int TW, int TH, int bid, i
 // 28 % above the mean).
 R2L_HD bool r2l_walk_next(R2LTileWalk& w, int H, int W, int TW, int TH, R2LTile& t) {
   for (;;) {
-    // first tile of round k: rounds before it hold jstep tiles each, but for the half rounds (every asym-th)
-    int base = w.k * w.jstep;
-    bool half = false;
-    if (w.asym) {
-      const int q = w.k / w.asym;
-      base -= q * (w.jstep / 2);
-      half = (w.k - q * w.asym) == w.asym - 1;
-    }
+    const int base = w.k * w.jstep;  // first tile of round k
     if (base >= w.nper) return false;
     const int rot = w.w + w.k * (w.ntx + 1);
-    int j;
-    if (half) {
-      const int hs = w.jstep / 2;
-      j = base + (rot - r2l_div(rot, w.dh) * hs);
-      if (w.w >= hs) j = w.nper;  // the younger half sits this round out
-    } else {
-      j = base + (rot - r2l_div(rot, w.dj) * w.jstep);
-    }
+    const int j = base + (rot - r2l_div(rot, w.dj) * w.jstep);
     w.k += 1;
     if (j >= w.nper) continue;
     const int tile = w.group * w.nper + j;
@@ -982,11 +959,7 @@ R2L_HD void r2l_fwd_row(const float* V, const float* YP, const R2LFwdArgs& a, in
                                 r2l_log2(fminf(fmaxf(rgb[1], 1e-5f), 1.0f)));
       const r2l_p2 e = r2l_pmul(lg, r2l_splat2(F.inv_gamma));                    // :209
       x[p] = r2l_mk2(r2l_exp2(e[0]), r2l_exp2(e[1]));
-      if (ADD) {                                                                 // :213 (H == W == 256)
-        const float a0 = (!RAGGED || gx0 + 2 * p < a.W) ? a.additive[off + 2 * p] : 0.f;
-        const float a1 = (!RAGGED || gx0 + 2 * p + 1 < a.W) ? a.additive[off + 2 * p + 1] : 0.f;
-        x[p] = r2l_padd(x[p], r2l_mk2(a0, a1));
-      }
+      if (ADD) x[p] = r2l_padd(x[p], r2l_mk2(a.additive[off + 2 * p], a.additive[off + 2 * p + 1]));  // :213 (H == W == 256)
       if (a.stat_partial) {
         if (p == 0) regs.piv[k] = (regs.npx == 0.f) ? x[0][0] : regs.piv[k];  // (pixel 0 of an active thread is inside the image)
         r2l_p2 d = r2l_padd(x[p], r2l_splat2(-regs.piv[k]));
@@ -1104,6 +1077,7 @@ R2L_HD void r2l_fwd_pixels(int tid, const float* V, const float* YP, const R2LFw
 #endif
 template <class G, bool ADD, bool MAYBE_RAGGED, bool U16>
 R2L_BLOCKFN void r2l_fwd_block(const R2LFwdArgs& a, int bid, int nblk, float* lds) {
+  static_assert(!(ADD && MAYBE_RAGGED), "an additive layer means 256 x 256 frames, which tile exactly");
   float* V = lds + R2L_FOLDED_FLOATS + G::PAD;
   R2LFoldedRef F = R2L_FOLDED_REF(a.F);
   float* Y = V + G::PLANE;
@@ -1232,7 +1206,6 @@ struct R2LBwd1Args {
   int band_h;           // r2l_bwd1_plane_block: rows per work item (a multiple of 6)
   float* hp;            // r2l_bwd1_blur_hp_block: (B,H,W) the blur's adjoint of dL/dY'' (kernel B2's plane)
   int band_hb;          // r2l_bwd1_blur_hp_block: rows per work item (a multiple of 6)
-  int xcdm, xcdm_hb;    // plane passes: neighbouring workgroups per XCD (r2l_xcd_window; 0 = off)
 };
 
 // per-thread accumulators of B1, as pairs: element h of a pair belongs to the pixels in the even (h = 0) or
@@ -1333,9 +1306,6 @@ R2L_HD void r2l_bwd1_fetch_gout(int tid, const R2LBwd1Args& a, const R2LTile& t,
 // the way (profiles/r03_b1_staging_modes.txt): grad_out and the raw frame staged the same way make the kernel and -- through
 // the chip's clocks -- every other kernel of the step slower, a nontemporal policy on these copies slows the forward.
 #define R2L_B1_FRAME_FLOATS (72 * 72 + 256)  // a 64 x 64 tile's frame + 1 KiB: dump area / overhang of the last round's wavefront
-#ifndef R2L_B1_GLDS
-#define R2L_B1_GLDS 1  // 0: A/B builds, the Y' frame prefetched into registers at the end of the pixel phase (round 2)
-#endif
 template <class G>
 R2L_HD void r2l_stage_frame(int tid, const float* gb, int oy, int ox, int H, int W, float* FSG, int only = -1) {
   constexpr int NCH = G::FH * (G::FW / 4);
@@ -1441,7 +1411,7 @@ R2L_HD void r2l_bwd1_row(const float* V, const float* YP, const R2LBwd1Args& a, 
       const r2l_p2 e = r2l_pmul(lg, r2l_splat2(F.inv_gamma));
       const r2l_p2 og = r2l_mk2(r2l_exp2(e[0]), r2l_exp2(e[1]));
       r2l_p2 x = og;
-      if (ADD) x = r2l_padd(x, r2l_mk2(valid0 ? a.additive[off + 2 * p] : 0.f, valid1 ? a.additive[off + 2 * p + 1] : 0.f));
+      if (ADD) x = r2l_padd(x, r2l_mk2(a.additive[off + 2 * p], a.additive[off + 2 * p + 1]));  // (H == W == 256: never ragged)
       const r2l_p2 xhat = r2l_pmul(r2l_padd(x, r2l_splat2(-bc.mean[k])), r2l_splat2(bc.istd[k]));
       r2l_p2 gx = r2l_bn_bwd_pair(r2l_mk2(g[2 * p], g[2 * p + 1]), xhat, bc.istd[k], bc.mg[k], bc.mgx[k]);
       if (RAGGED) gx = r2l_mk2(valid0 ? gx[0] : 0.f, valid1 ? gx[1] : 0.f);
@@ -1651,7 +1621,6 @@ R2L_HD void r2l_bwd1_pixels(int tid, const float* V, const float* YP, const R2LB
     bc.mg[k] = a.bn_bwd ? bc.istd[k] * a.bn_bwd[k] : 0.f;
     bc.mgx[k] = a.bn_bwd ? bc.istd[k] * a.bn_bwd[3 + k] : 0.f;
   }
-#ifndef R2L_B1_ROW_MAJOR
   if (!RAGGED && PRE) {
     if (py)
       r2l_bwd1_rows2<G, 1, ADD>(V, YP, a, tid, tx, row0 + 4, pix0, plane, gp, gyb, bc, regs, mid R2L_SUB_PASS_FWD);
@@ -1659,7 +1628,6 @@ R2L_HD void r2l_bwd1_pixels(int tid, const float* V, const float* YP, const R2LB
       r2l_bwd1_rows2<G, 0, ADD>(V, YP, a, tid, tx, row0 + 4, pix0, plane, gp, gyb, bc, regs, mid R2L_SUB_PASS_FWD);
     return;
   }
-#endif
   R2L_PRAGMA_UNROLL
   for (int sl = 0; sl < 16; ++sl) mid(sl);
   R2L_PRAGMA_NOUNROLL
@@ -1680,6 +1648,7 @@ R2L_HD void r2l_bwd1_pixels(int tid, const float* V, const float* YP, const R2LB
 // phases, 29 % of the kernel (profiles/r01_f_phase_stamps.txt), for 4.5 B/px more traffic.
 template <class G, bool ADD, bool MAYBE_RAGGED, bool U16, bool SAVED = false>
 R2L_BLOCKFN void r2l_bwd1_block(const R2LBwd1Args& a, int bid, int nblk, float* lds) {
+  static_assert(!(ADD && MAYBE_RAGGED), "an additive layer means 256 x 256 frames, which tile exactly");
   float* V = lds + R2L_FOLDED_FLOATS + G::PAD;
   R2LFoldedRef F = R2L_FOLDED_REF(a.F);
   float* Y = V + G::PLANE;
@@ -1690,12 +1659,9 @@ R2L_BLOCKFN void r2l_bwd1_block(const R2LBwd1Args& a, int bid, int nblk, float* 
   R2L_TREG_DECL(R2LGoutPre, gpre);
   // hot instantiations: the next tile's Y' frame travels through an LDS staging area behind the three planes
   // (r2l_stage_frame; these kernels are launched with R2L_B1_FRAME_FLOATS more LDS)
-  constexpr bool GLDS = SAVED && !MAYBE_RAGGED && !ADD && (R2L_B1_GLDS != 0);
+  constexpr bool GLDS = SAVED && !MAYBE_RAGGED && !ADD;
   static_assert(!GLDS || G::FH * G::FW + 256 == R2L_B1_FRAME_FLOATS, "staging area of a frame");
   float* YS = GLDS ? YP + G::PLANE + G::PAD : nullptr;
-  // additive layer on frames that do not tile by 64 (never the reference's: its layer is 256 x 256, pipeline_torch.py:130): no
-  // register to spare across the pixel phase -- the raw frame of a tile is fetched when the tile starts, not a tile ahead
-  constexpr bool LATE_RAW = ADD && MAYBE_RAGGED;
   R2LTileWalk w = r2l_walk_init(a.B, a.H, a.W, G::TW, G::TH, bid, nblk);
   R2LTile t, tn;
   bool have = r2l_walk_next(w, a.H, a.W, G::TW, G::TH, t);
@@ -1706,7 +1672,7 @@ R2L_BLOCKFN void r2l_bwd1_block(const R2LBwd1Args& a, int bid, int nblk, float* 
     int tx_, row_;
     G::thread_tile(tid, tx_, row_, R2L_TREG(regs).py);
   }
-  if (!LATE_RAW && have) r2l_fetch_raw_tile<G, U16>(tid, a.raw, t, a.H, a.W, R2L_TREG(pre));
+  if (have) r2l_fetch_raw_tile<G, U16>(tid, a.raw, t, a.H, a.W, R2L_TREG(pre));
   if (SAVED && !GLDS && have) r2l_fetch_tile<G, 1>(tid, a.yp, t, a.H, a.W, R2L_TREG(pre_yp));
   if (GLDS && have) {
     r2l_stage_frame<G>(tid, a.yp + (size_t)t.b * a.H * a.W, t.oy, t.ox, a.H, a.W, YS);
@@ -1716,7 +1682,6 @@ R2L_BLOCKFN void r2l_bwd1_block(const R2LBwd1Args& a, int bid, int nblk, float* 
   R2L_STAMP_DECL
   while (have) {
     R2L_PHASE_BEGIN_IF(ADD || MAYBE_RAGGED)
-    if (LATE_RAW) r2l_fetch_raw_tile<G, U16>(tid, a.raw, t, a.H, a.W, R2L_TREG(pre));  // (no prefetch: see LATE_RAW)
     r2l_store_v<G, U16>(tid, V, F, R2L_TREG(pre), a.raw);
     if (GLDS)
       r2l_store_plane_s2_staged<G>(tid, YP, YS, t.oy, t.ox, a.H, a.W);
@@ -1757,7 +1722,7 @@ R2L_BLOCKFN void r2l_bwd1_block(const R2LBwd1Args& a, int bid, int nblk, float* 
     R2L_STAMP(3)
     }
     R2L_PHASE_BEGIN_IF(ADD || MAYBE_RAGGED)
-    if (!LATE_RAW && haven) r2l_fetch_raw_tile<G, U16>(tid, a.raw, tn, a.H, a.W, R2L_TREG(pre));
+    if (haven) r2l_fetch_raw_tile<G, U16>(tid, a.raw, tn, a.H, a.W, R2L_TREG(pre));
     if (GLDS) {
       // the next tile's Y' frame: one copy per lane behind each of the first window rows of the blur-weight correlation
       // (as a burst all 8 wavefronts would reach them together and queue in the texture-address path).  After the last
@@ -1802,7 +1767,6 @@ struct R2LBwd2Args {
   R2LTree tree;         // in-kernel final reduction of B1's and B2's partials + unfold -> grad_params
   const float* params;  // packed parameters (for the unfold)
   float* grad_params;   // [R2L_P_NTRAIN]
-  int asym;             // r2l_walk_init: uneven tile shares for the two workgroups of a CU (0 = even)
   float* hp;            // plane passes (r2l_param_plane_bwd.h): (B,H,W) the blur's adjoint of dL/dY''
   int band_h;           // plane passes: rows per work item (a multiple of 6)
   // the sums pass (r2l_bwd2_sums_block) with helper workgroups: workgroups [0, nmain) walk the work items and reduce B2's
@@ -1812,7 +1776,6 @@ struct R2LBwd2Args {
   const float* b1_partial;
   int b1_n;
   double* b1_tot;  // [R2L_B1_NACC]
-  int xcdm;        // the sums pass: neighbouring workgroups per XCD (r2l_xcd_window; 0 = off)
 };
 
 enum { R2L_L2_GSHARP = 0, R2L_L2_GAY = 9, R2L_L2_SY = 27, R2L_L2_NACC = 29 };
@@ -2048,9 +2011,6 @@ R2L_HD void r2l_bwd2_pixels(int tid, const float* V, const float* Y, const float
 // (i) no software prefetch of the next tile (24 registers; the other workgroup's phases hide the HBM round trip),
 // (ii) 3-row items in the adjoint blur, (iii) one register window at a time in the pixel phase, (iv) R2L_PHASE_BEGIN_L.
 // profiles/r02_c_bwd2_ab.txt: 109 us (round 1) -> 116 us with (iii)+(iv) alone at one workgroup per CU -> 97 us.
-#ifndef R2L_B2_PREFETCH
-#define R2L_B2_PREFETCH 0
-#endif
 
 template <class G, bool U16>
 R2L_BLOCKFN void r2l_bwd2_block(const R2LBwd2Args& a, int bid, int nblk, float* lds) {
@@ -2062,7 +2022,7 @@ R2L_BLOCKFN void r2l_bwd2_block(const R2LBwd2Args& a, int bid, int nblk, float* 
   R2L_TREG_DECL(R2LBwd2Regs, regs);
   R2L_TREG_DECL(R2LPrefetch<G>, pre_v);
   R2L_TREG_DECL(R2LPrefetch<G>, pre_g);
-  R2LTileWalk w = r2l_walk_init(a.B, a.H, a.W, G::TW, G::TH, bid, nblk, a.asym);
+  R2LTileWalk w = r2l_walk_init(a.B, a.H, a.W, G::TW, G::TH, bid, nblk);
   R2LTile t, tn;
   bool have = r2l_walk_next(w, a.H, a.W, G::TW, G::TH, t);
   R2L_PHASE_BEGIN
@@ -2072,22 +2032,14 @@ R2L_BLOCKFN void r2l_bwd2_block(const R2LBwd2Args& a, int bid, int nblk, float* 
     int tx_, row_;
     G::thread_tile(tid, tx_, row_, R2L_TREG(regs).py);
   }
-#if R2L_B2_PREFETCH
-  if (have) {
-    r2l_fetch_raw_tile<G, U16>(tid, a.raw, t, a.H, a.W, R2L_TREG(pre_v));
-    r2l_fetch_tile<G, 1>(tid, a.gypp, t, a.H, a.W, R2L_TREG(pre_g));
-  }
-#endif
   R2L_PHASE_END
   R2L_STAMP_DECL
   while (have) {
     R2L_PHASE_BEGIN_L
-#if !R2L_B2_PREFETCH
     // two workgroups per CU: the other workgroup's phases hide this tile's HBM round trip, and the 24 registers
     // of a software prefetch are what keeps the kernel above 128 VGPRs
     r2l_fetch_raw_tile<G, U16>(tid, a.raw, t, a.H, a.W, R2L_TREG(pre_v));
     r2l_fetch_tile<G, 1>(tid, a.gypp, t, a.H, a.W, R2L_TREG(pre_g));
-#endif
     r2l_store_v<G, U16>(tid, V, F, R2L_TREG(pre_v), a.raw);
     r2l_store_plane_s2<G>(tid, G2, R2L_TREG(pre_g));
     R2L_PHASE_END
@@ -2112,12 +2064,6 @@ R2L_BLOCKFN void r2l_bwd2_block(const R2LBwd2Args& a, int bid, int nblk, float* 
     R2L_PHASE_END
     R2L_STAMP(2)
     R2L_PHASE_BEGIN_L
-#if R2L_B2_PREFETCH
-    if (haven) {
-      r2l_fetch_raw_tile<G, U16>(tid, a.raw, tn, a.H, a.W, R2L_TREG(pre_v));
-      r2l_fetch_tile<G, 1>(tid, a.gypp, tn, a.H, a.W, R2L_TREG(pre_g));
-    }
-#endif
     if (t.border)
       r2l_bwd2_pixels<G, true>(tid, V, Y, HP, a, t, R2L_TREG(regs));
     else

@@ -49,27 +49,8 @@ struct R2LBpStage {  // grad_out of one row in flight: 3 channels x the lane's 4
 // The LAST reader of a kept plane may take it around the caches (nontemporal loads), so that what it leaves in the 256 MiB memory-side
 // cache is what the next passes want (profiles/r05_nt_stores.txt, 64x512x512, alternating processes):
 //   HP in the sums pass (the step's last kernel): the NEXT step's apply pass 63.5 -> 60.1 us, blur pass 43.3 -> 41.5, statistics -0.9
-//     -- 67 MB less dead weight in the cache when the forward starts.  ADOPTED (R2L_B2S_HP_NT 1).
-//   dL/dY'' in the blur pass, Y' in the blur pass, the raw frames in the sums pass: nothing, nothing, +1 us.  Switches kept for A/B runs.
-#ifndef R2L_B2S_HP_NT
-#define R2L_B2S_HP_NT 1
-#endif
-#ifdef R2L_EXP_HB_GY_NT
-#define R2L_HB_GY_LOAD(p) r2l_load_f4_nt(p)
-#else
-#define R2L_HB_GY_LOAD(p) r2l_stream_load_f4(p)
-#endif
-#ifndef R2L_HB_YP_NT
-#define R2L_HB_YP_NT false   // Y' in the blur pass (its last reader)
-#endif
-#ifndef R2L_B2S_RAW_NT
-#define R2L_B2S_RAW_NT false  // the raw frames in the sums pass (their last reader in the step)
-#endif
-#if R2L_B2S_HP_NT
-#define R2L_B2S_HP_LOAD(p) r2l_load_f4_nt(p)
-#else
-#define R2L_B2S_HP_LOAD(p) r2l_stream_load_f4(p)
-#endif
+//     -- 67 MB less dead weight in the cache when the forward starts.  Adopted.
+//   dL/dY'' in the blur pass, Y' in the blur pass, the raw frames in the sums pass: nothing, nothing, +1 us.  Plain loads.
 template <bool EPI>
 R2L_HD void r2l_bp_fetch_g(const float* gimg, unsigned plane, int y, int H, int W, int x0, const R2LEpi& ep,
                            R2LBpStage& s) {
@@ -82,11 +63,7 @@ R2L_HD void r2l_bp_fetch_g(const float* gimg, unsigned plane, int y, int H, int 
   }
   const float* p = gimg + (size_t)yc * W + x0;
   R2L_PRAGMA_UNROLL
-#ifdef R2L_BP_GOUT_PLAIN  // A/B builds
-  for (int k = 0; k < 3; ++k) s.g[k] = *(const r2l_f4*)(p + (size_t)k * plane);
-#else
   for (int k = 0; k < 3; ++k) s.g[k] = r2l_load_f4_nt(p + (size_t)k * plane);  // read once: nontemporal (as kernel B1)
-#endif
 }
 
 // ================================================================================================
@@ -104,7 +81,7 @@ R2L_HD void r2l_bp_fetch_g(const float* gimg, unsigned plane, int y, int H, int 
 #define R2L_BNR_PF 2  // rows in flight per stream (raw, Y', grad_out): 3 takes the kernel past 168 registers
 #endif
 struct R2LBnrArgs {
-  R2LFwdStreamArgs s;    // raw, F, bn (mean, 1/std), yp_in, B, H, W, nband, band_h, nitems, stat_partial, tree, ep, xcdm
+  R2LFwdStreamArgs s;    // raw, F, bn (mean, 1/std), yp_in, B, H, W, nband, band_h, nitems, stat_partial, tree, ep
   const float* gout;
   double* sums;          // [6]
   const double* totals;  // optional: totals[6] = pixel count n of the global batch
@@ -152,15 +129,15 @@ R2L_HD void r2l_bnr_item(const R2LBnrArgs& ba, int item, int lane, const float m
   R2LBpStage pfg[PF];  // grad_out row q
   R2L_PRAGMA_UNROLL
   for (int i = 0; i < PF; ++i) {
-    r2l_fa_fetch_raw<U16>(a, img, r2l_mirror(R2L_NH(y0 - 3 + i), a.H), x0, le, re, lane, pf[(2 + i) % PF]);
-    r2l_fa_fetch(ypimg, R2L_NH(y0 - 2 + i), a.H, a.W, x0, le, re, lane, pfy[(2 + i) % PF]);
+    r2l_fa_fetch_raw<U16>(a, img, r2l_mirror(y0 - 3 + i, a.H), x0, le, re, lane, pf[(2 + i) % PF]);
+    r2l_fa_fetch(ypimg, y0 - 2 + i, a.H, a.W, x0, le, re, lane, pfy[(2 + i) % PF]);
   }
 #define R2L_BNR_LOAD_STEP(K, q)                                                                          \
   {                                                                                                      \
     r2l_fs_convert<U16>(a, F, pf[(K) % PF], le, re, st.v[((K) + 1) % 3]);                                \
     r2l_fa_build(pfy[(K) % PF], (unsigned)((q) + 2) < (unsigned)a.H, le, re, st.yp[((K) + 2) % 6]);      \
-    r2l_fa_fetch_raw<U16>(a, img, r2l_mirror(R2L_NH((q) + 1 + PF), a.H), x0, le, re, lane, pf[(K) % PF]); \
-    r2l_fa_fetch(ypimg, R2L_NH((q) + 2 + PF), a.H, a.W, x0, le, re, lane, pfy[(K) % PF]);                \
+    r2l_fa_fetch_raw<U16>(a, img, r2l_mirror((q) + 1 + PF, a.H), x0, le, re, lane, pf[(K) % PF]); \
+    r2l_fa_fetch(ypimg, (q) + 2 + PF, a.H, a.W, x0, le, re, lane, pfy[(K) % PF]);                \
   }
   R2L_BNR_LOAD_STEP(2, y0 - 4)
   R2L_BNR_LOAD_STEP(3, y0 - 3)
@@ -211,7 +188,7 @@ R2L_BLOCKFN void r2l_bnr_planes_block(const R2LBnrArgs& ba, int bid, int nblk, f
   double* tots = (double*)(lds + 16 + R2L_FS_RED_FLOATS(NWV)) + wave * 6;
   if (lane < 6) tots[lane] = 0.0;
   R2L_PRAGMA_NOUNROLL
-  for (int item = r2l_xcd_window(bid, nblk, a.xcdm) * NWV + wave; item < a.nitems; item += nblk * NWV)
+  for (int item = bid * NWV + wave; item < a.nitems; item += nblk * NWV)
     r2l_bnr_item<U16, EPI>(ba, item, lane, mean, istd, tots);
   // ---- the wavefronts' float64 totals -> (high, low) float32 halves per workgroup -> the shared tree (as r2l_fs_stats_finish)
   R2L_LDS_BARRIER();
@@ -294,13 +271,8 @@ R2L_HD void r2l_bp_step(const R2LBwd1Args& a, R2LBpState& st, R2LBpAcc& A, const
   {
     R2LFoldedRef F = R2L_FOLDED_REF(r2l_opaque_after(a.F, yw[2][2]));
     const int set = (y < 2) ? y : (y - (H - 2)) + 2;
-#ifdef R2L_EXP_CONST_WEIGHTS
-    const float* w25 = &F.blur[0];  // (timing only: no border sets)
-    (void)set;
-#else
     const R2L_CONSTAS float* w25 =
         (y >= 2 && y < H - 2) ? &F.blur[0] : &F.blur_edge[0][0] + 25 * set;
-#endif
     r2l_blur_row2w(yw, w25, ypp);
   }
   const float* vu = st.v[(K + 2) % 3];  // V(y-1)
@@ -355,11 +327,7 @@ R2L_HD void r2l_bp_step(const R2LBwd1Args& a, R2LBpState& st, R2LBpAcc& A, const
     s4.y = gy2[0][1];
     s4.z = gy2[1][0];
     s4.w = gy2[1][1];
-#ifdef R2L_EXP_GY_NT
-    r2l_store_f4_nt(gyb + (unsigned)y * (unsigned)a.W + (unsigned)x0, s4);
-#else
     *(r2l_f4*)(gyb + (unsigned)y * (unsigned)a.W + (unsigned)x0) = s4;
-#endif
   }
   // ---- folded chroma stencils of this row's parity ----------------------------------------------------------------------
   const float* rows[3] = {vu, vm, vl};
@@ -477,7 +445,7 @@ R2L_BLOCKFN void r2l_bwd1_plane_block(const R2LBwd1Args& a, int bid, int nblk, f
   static_assert(6 % PF == 0 && 6 % PFG == 0, "the prefetch rings are indexed by the unroll position");
   // the registers hold the bank of EVEN rows between items (every band starts on an even row, at K = 0)
   R2L_PRAGMA_NOUNROLL
-  for (int item = r2l_xcd_window(bid, nblk, a.xcdm) * NWV + wave; item < nitems; item += nblk * NWV) {
+  for (int item = bid * NWV + wave; item < nitems; item += nblk * NWV) {
     const int strip = item % nstrip, ib = item / nstrip;
     const int band = ib % nband, b = ib / nband;
     const int xs = strip * 256 + 4 * lane;
@@ -496,16 +464,16 @@ R2L_BLOCKFN void r2l_bwd1_plane_block(const R2LBwd1Args& a, int bid, int nblk, f
     R2LBpStage pfg[PFG];  // grad_out row q
     R2L_PRAGMA_UNROLL
     for (int i = 0; i < PF; ++i) {
-      r2l_fa_fetch_raw<U16>(sa, img, r2l_mirror(R2L_NH(y0 - 3 + i), a.H), x0, le, re, lane, pf[(2 + i) % PF]);
-      r2l_fa_fetch(ypimg, R2L_NH(y0 - 2 + i), a.H, a.W, x0, le, re, lane, pfy[(2 + i) % PF]);
+      r2l_fa_fetch_raw<U16>(sa, img, r2l_mirror(y0 - 3 + i, a.H), x0, le, re, lane, pf[(2 + i) % PF]);
+      r2l_fa_fetch(ypimg, y0 - 2 + i, a.H, a.W, x0, le, re, lane, pfy[(2 + i) % PF]);
     }
     R2L_PRAGMA_UNROLL
     for (int i = 0; i < PFG; ++i) r2l_bp_fetch_g<EPI>(gimg, plane, y0 + i, a.H, a.W, x0, a.ep, pfg[i % PFG]);  // (first used at K = 0)
 #define R2L_BP_LOAD_STEP(K, q)                                                                          \
   r2l_fs_convert<U16>(sa, F, pf[(K) % PF], le, re, st.v[((K) + 1) % 3]);                                \
   r2l_fa_build(pfy[(K) % PF], (unsigned)((q) + 2) < (unsigned)a.H, le, re, st.yp[((K) + 2) % 6]);       \
-  r2l_fa_fetch_raw<U16>(sa, img, r2l_mirror(R2L_NH((q) + 1 + PF), a.H), x0, le, re, lane, pf[(K) % PF]);        \
-  r2l_fa_fetch(ypimg, R2L_NH((q) + 2 + PF), a.H, a.W, x0, le, re, lane, pfy[(K) % PF]);
+  r2l_fa_fetch_raw<U16>(sa, img, r2l_mirror((q) + 1 + PF, a.H), x0, le, re, lane, pf[(K) % PF]);        \
+  r2l_fa_fetch(ypimg, (q) + 2 + PF, a.H, a.W, x0, le, re, lane, pfy[(K) % PF]);
     R2L_BP_LOAD_STEP(2, y0 - 4)
     R2L_BP_LOAD_STEP(3, y0 - 3)
     R2L_BP_LOAD_STEP(4, y0 - 2)
@@ -517,7 +485,6 @@ R2L_BLOCKFN void r2l_bwd1_plane_block(const R2LBwd1Args& a, int bid, int nblk, f
 #define R2L_BP_STEP(K)                                                                                  \
   {                                                                                                     \
     const int q = qb + K;                                                                               \
-    R2L_PROGRESS_PRIO_STEP(q - y0, y1 - y0);                                                            \
     R2L_BP_LOAD_STEP(K, q)                                                                              \
     const R2LBpStage g_ = pfg[(K) % PFG];                                                               \
     r2l_bp_fetch_g<EPI>(gimg, plane, q + PFG, a.H, a.W, x0, a.ep, pfg[(K) % PFG]);                      \
@@ -628,7 +595,7 @@ R2L_BLOCKFN void r2l_bwd1_blur_block(const R2LBwd1Args& a, int bid, int nblk, fl
   constexpr int PF = R2L_BB_PF;
   static_assert(6 % PF == 0, "the prefetch ring is indexed by the unroll position");
   R2L_PRAGMA_NOUNROLL
-  for (int item = r2l_xcd_window(bid, nblk, a.xcdm_hb) * NWV + wave; item < nitems; item += nblk * NWV) {
+  for (int item = bid * NWV + wave; item < nitems; item += nblk * NWV) {
     const int strip = item % nstrip, ib = item / nstrip;
     const int band = ib % nband, b = ib / nband;
     const int xs = strip * 256 + 4 * lane;
@@ -645,13 +612,13 @@ R2L_BLOCKFN void r2l_bwd1_blur_block(const R2LBwd1Args& a, int bid, int nblk, fl
     R2LBbStage pfg[PF];  // dL/dY'' row q
     R2L_PRAGMA_UNROLL
     for (int i = 0; i < PF; ++i) {
-      r2l_fa_fetch<R2L_HB_YP_NT>(ypimg, R2L_NH(y0 - 2 + i), a.H, a.W, x0, le, re, lane, pfy[(2 + i) % PF]);
+      r2l_fa_fetch(ypimg, y0 - 2 + i, a.H, a.W, x0, le, re, lane, pfy[(2 + i) % PF]);
       const int yc = (y0 + i < a.H) ? y0 + i : a.H - 1;
-      pfg[i % PF].g = R2L_HB_GY_LOAD(gimg + (size_t)yc * a.W + x0);
+      pfg[i % PF].g = r2l_stream_load_f4(gimg + (size_t)yc * a.W + x0);
     }
 #define R2L_BB_LOAD_STEP(K, q)                                                                          \
   r2l_fa_build(pfy[(K) % PF], (unsigned)((q) + 2) < (unsigned)a.H, le, re, yp[((K) + 2) % 6]);          \
-  r2l_fa_fetch<R2L_HB_YP_NT>(ypimg, R2L_NH((q) + 2 + PF), a.H, a.W, x0, le, re, lane, pfy[(K) % PF]);
+  r2l_fa_fetch(ypimg, (q) + 2 + PF, a.H, a.W, x0, le, re, lane, pfy[(K) % PF]);
     R2L_BB_LOAD_STEP(2, y0 - 4)
     R2L_BB_LOAD_STEP(3, y0 - 3)
     R2L_BB_LOAD_STEP(4, y0 - 2)
@@ -661,12 +628,11 @@ R2L_BLOCKFN void r2l_bwd1_blur_block(const R2LBwd1Args& a, int bid, int nblk, fl
 #define R2L_BB_STEP(K)                                                                                  \
   {                                                                                                     \
     const int q = qb + K;                                                                               \
-    R2L_PROGRESS_PRIO_STEP(q - y0, y1 - y0);                                                            \
     R2L_BB_LOAD_STEP(K, q)                                                                              \
     const R2LBbStage g_ = pfg[(K) % PF];                                                                \
     {                                                                                                   \
       const int yc = (q + PF < a.H) ? q + PF : a.H - 1;                                                 \
-      pfg[(K) % PF].g = R2L_HB_GY_LOAD(gimg + (size_t)yc * a.W + x0);                               \
+      pfg[(K) % PF].g = r2l_stream_load_f4(gimg + (size_t)yc * a.W + x0);                               \
     }                                                                                                   \
     if (r2l_opaque_true()) r2l_bb_step<K>(a, yp, blur, g_, q, in_w && q < y1);                          \
   }
@@ -772,11 +738,7 @@ R2L_HD void r2l_hp_step(const ArgsT& a, const float gw[6][8], int q, bool le, bo
     s4.y = h1;
     s4.z = h2;
     s4.w = h3;
-#ifdef R2L_EXP_HP_NT
-    r2l_store_f4_nt(hpb + (unsigned)q * (unsigned)a.W + (unsigned)x0, s4);
-#else
     *(r2l_f4*)(hpb + (unsigned)q * (unsigned)a.W + (unsigned)x0) = s4;
-#endif
   }
 }
 #ifndef R2L_HP_PF
@@ -807,10 +769,10 @@ R2L_BLOCKFN void r2l_bwd2_hp_block(const R2LBwd2Args& a, int bid, int nblk, floa
   static_assert(6 % PF == 0, "the prefetch ring is indexed by the unroll position");
   R2LFaStage pf[PF];  // g row q + 2
   R2L_PRAGMA_UNROLL
-  for (int i = 0; i < PF; ++i) r2l_fa_fetch(gimg, R2L_NH(y0 - 2 + i), a.H, a.W, x0, le, re, lane, pf[(2 + i) % PF]);
+  for (int i = 0; i < PF; ++i) r2l_fa_fetch(gimg, y0 - 2 + i, a.H, a.W, x0, le, re, lane, pf[(2 + i) % PF]);
 #define R2L_HP_LOAD_STEP(K, q)                                                                          \
   r2l_hp_build(pf[(K) % PF], (unsigned)((q) + 2) < (unsigned)a.H, le, re, gw[((K) + 2) % 6]);           \
-  r2l_fa_fetch(gimg, R2L_NH((q) + 2 + PF), a.H, a.W, x0, le, re, lane, pf[(K) % PF]);
+  r2l_fa_fetch(gimg, (q) + 2 + PF, a.H, a.W, x0, le, re, lane, pf[(K) % PF]);
   R2L_HP_LOAD_STEP(2, y0 - 4)
   R2L_HP_LOAD_STEP(3, y0 - 3)
   R2L_HP_LOAD_STEP(4, y0 - 2)
@@ -820,7 +782,6 @@ R2L_BLOCKFN void r2l_bwd2_hp_block(const R2LBwd2Args& a, int bid, int nblk, floa
 #define R2L_HP_STEP(K)                                                                                  \
   {                                                                                                     \
     const int q = qb + K;                                                                               \
-    R2L_PROGRESS_PRIO_STEP(q - y0, y1 - y0);                                                            \
     R2L_HP_LOAD_STEP(K, q)                                                                              \
     r2l_hp_step<K>(a, gw, q, le, re, in_w && q < y1, hpb, x0);                                          \
   }
@@ -934,11 +895,7 @@ R2L_HD void r2l_hb_step(const R2LBwd1Args& a, const float gw[6][8], r2l_p2 blur[
     s4.y = h1;
     s4.z = h2;
     s4.w = h3;
-#ifdef R2L_EXP_HP_NT
-    r2l_store_f4_nt(hpb + (unsigned)q * (unsigned)a.W + (unsigned)x0, s4);
-#else
     *(r2l_f4*)(hpb + (unsigned)q * (unsigned)a.W + (unsigned)x0) = s4;
-#endif
   }
 }
 #ifndef R2L_HB_OCC
@@ -956,7 +913,7 @@ R2L_BLOCKFN void r2l_bwd1_blur_hp_block(const R2LBwd1Args& a, int bid, int nblk,
   constexpr int PF = R2L_BB_PF;
   static_assert(6 % PF == 0, "the prefetch ring is indexed by the unroll position");
   R2L_PRAGMA_NOUNROLL
-  for (int item = r2l_xcd_window(bid, nblk, a.xcdm_hb) * NWV + wave; item < nitems; item += nblk * NWV) {
+  for (int item = bid * NWV + wave; item < nitems; item += nblk * NWV) {
     const int strip = item % nstrip, ib = item / nstrip;
     const int band = ib % nband, b = ib / nband;
     const int xs = strip * 256 + 4 * lane;
@@ -974,13 +931,13 @@ R2L_BLOCKFN void r2l_bwd1_blur_hp_block(const R2LBwd1Args& a, int bid, int nblk,
     r2l_f4 pfy[PF];      // Y' row q
     R2L_PRAGMA_UNROLL
     for (int i = 0; i < PF; ++i) {
-      r2l_fa_fetch(gimg, R2L_NH(y0 - 2 + i), a.H, a.W, x0, le, re, lane, pfg[(2 + i) % PF]);
+      r2l_fa_fetch(gimg, y0 - 2 + i, a.H, a.W, x0, le, re, lane, pfg[(2 + i) % PF]);
       const int yc = (y0 + i < a.H) ? y0 + i : a.H - 1;
       pfy[i % PF] = r2l_stream_load_f4(ypimg + (size_t)yc * a.W + x0);
     }
 #define R2L_BH_LOAD_STEP(K, q)                                                                          \
   r2l_hp_build(pfg[(K) % PF], (unsigned)((q) + 2) < (unsigned)a.H, le, re, gw[((K) + 2) % 6]);          \
-  r2l_fa_fetch(gimg, R2L_NH((q) + 2 + PF), a.H, a.W, x0, le, re, lane, pfg[(K) % PF]);
+  r2l_fa_fetch(gimg, (q) + 2 + PF, a.H, a.W, x0, le, re, lane, pfg[(K) % PF]);
     R2L_BH_LOAD_STEP(2, y0 - 4)
     R2L_BH_LOAD_STEP(3, y0 - 3)
     R2L_BH_LOAD_STEP(4, y0 - 2)
@@ -990,7 +947,6 @@ R2L_BLOCKFN void r2l_bwd1_blur_hp_block(const R2LBwd1Args& a, int bid, int nblk,
 #define R2L_BH_STEP(K)                                                                                  \
   {                                                                                                     \
     const int q = qb + K;                                                                               \
-    R2L_PROGRESS_PRIO_STEP(q - y0, y1 - y0);                                                            \
     R2L_BH_LOAD_STEP(K, q)                                                                              \
     const r2l_f4 y_ = pfy[(K) % PF];                                                                    \
     {                                                                                                   \
@@ -1029,7 +985,7 @@ R2L_HD void r2l_b2s_fetch_hp(const float* hpimg, int r, int H, int W, int x0, bo
   const int rc = r < 0 ? 0 : (r >= H ? H - 1 : r);
   const float* p = hpimg + (size_t)rc * W + x0;
   const int eo = (lane < 32) ? (le ? 0 : -1) : (re ? 3 : 4);
-  s.c = R2L_B2S_HP_LOAD(p);
+  s.c = r2l_load_f4_nt(p);
   s.e = p[eo];
 }
 // staged row -> 6 values, columns x0-1 .. x0+4, zero outside the image (the sharpen's zero padding has no adjoint there)
@@ -1248,7 +1204,7 @@ R2L_BLOCKFN void r2l_bwd2_sums_block(const R2LBwd2Args& a, int bid, int nblk_lau
   static_assert(6 % PF == 0, "the prefetch ring is indexed by the unroll position");
   // the registers hold the bank of EVEN rows between items (bands start on even rows, at K = 0)
   R2L_PRAGMA_NOUNROLL
-  for (int item = r2l_xcd_window(bid, nblk, a.xcdm) * NWV + wave; item < nitems; item += nblk * NWV) {
+  for (int item = bid * NWV + wave; item < nitems; item += nblk * NWV) {
     const int strip = item % nstrip, ib = item / nstrip;
     const int band = ib % nband, b = ib / nband;
     const int xs = strip * 256 + 4 * lane;
@@ -1269,14 +1225,14 @@ R2L_BLOCKFN void r2l_bwd2_sums_block(const R2LBwd2Args& a, int bid, int nblk_lau
     // row finishes the sharpen-weight sums of that row.
     R2L_PRAGMA_UNROLL
     for (int i = 0; i < PF; ++i) {
-      r2l_fl_fetch<U16, R2L_B2S_RAW_NT>(sa, img, r2l_mirror(R2L_NH(y0 - 2 + i), a.H), x0, le, re, lane, pf[(3 + i) % PF]);
-      r2l_b2s_fetch_hp(hpimg, R2L_NH(y0 - 2 + i), a.H, a.W, x0, le, re, lane, pfh[(3 + i) % PF]);
+      r2l_fl_fetch<U16>(sa, img, r2l_mirror(y0 - 2 + i, a.H), x0, le, re, lane, pf[(3 + i) % PF]);
+      r2l_b2s_fetch_hp(hpimg, y0 - 2 + i, a.H, a.W, x0, le, re, lane, pfh[(3 + i) % PF]);
     }
 #define R2L_B2S_LOAD_STEP(K, t)                                                                               \
   r2l_fl_convert<U16>(sa, F, pf[(K) % PF], le, re, st.v[((K) + 1) % 3], st.xp[((K) + 1) % 3]);                \
   r2l_b2s_build_hp(pfh[(K) % PF], (unsigned)((t) + 1) < (unsigned)a.H, le, re, st.hp[((K) + 1) % 3]);         \
-  r2l_fl_fetch<U16, R2L_B2S_RAW_NT>(sa, img, r2l_mirror(R2L_NH((t) + 1 + PF), a.H), x0, le, re, lane, pf[(K) % PF]);                  \
-  r2l_b2s_fetch_hp(hpimg, R2L_NH((t) + 1 + PF), a.H, a.W, x0, le, re, lane, pfh[(K) % PF]);
+  r2l_fl_fetch<U16>(sa, img, r2l_mirror((t) + 1 + PF, a.H), x0, le, re, lane, pf[(K) % PF]);                  \
+  r2l_b2s_fetch_hp(hpimg, (t) + 1 + PF, a.H, a.W, x0, le, re, lane, pfh[(K) % PF]);
     R2L_B2S_LOAD_STEP(3, y0 - 3)
     R2L_B2S_LOAD_STEP(4, y0 - 2)
     R2L_B2S_LOAD_STEP(5, y0 - 1)
@@ -1286,7 +1242,6 @@ R2L_BLOCKFN void r2l_bwd2_sums_block(const R2LBwd2Args& a, int bid, int nblk_lau
 #define R2L_B2S_STEP(K)                                                                                       \
   {                                                                                                           \
     const int t = qb + K;                                                                                     \
-    R2L_PROGRESS_PRIO_STEP(t - y0, y1 - y0);                                                                  \
     R2L_B2S_LOAD_STEP(K, t)                                                                                   \
     if (K) r2l_b2s_swap(A, bank); /* the bank of this row's parity into the registers */                      \
     if (r2l_opaque_true()) {                                                                                  \

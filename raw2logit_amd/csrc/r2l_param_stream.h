@@ -24,12 +24,6 @@
 #ifndef R2L_FS_PF
 #define R2L_FS_PF 2
 #endif
-#ifndef R2L_FS_BF_FETCH
-#define R2L_FS_BF_FETCH 1
-#endif
-#ifndef R2L_FS_FULL_GROUPS
-#define R2L_FS_FULL_GROUPS 1
-#endif
 
 struct R2LFwdStreamArgs {
   R2LRaw raw;
@@ -45,7 +39,6 @@ struct R2LFwdStreamArgs {
   double* stats_out;
   R2LBnFinalizeArgs fin;
   R2LEpi ep;  // EPI instantiations: where the output goes (R2LEpi)
-  int xcdm;   // neighbouring workgroups per XCD (r2l_xcd_window; 0 = off): the work items follow the mapped workgroup id
 #ifdef R2L_EXP_STAMPS
   unsigned long long* tl;  // diagnostic builds: (start, end) s_memrealtime of every workgroup's first wavefront
 #endif
@@ -101,25 +94,7 @@ struct R2LFsStage {
   float e;
   int ym;  // mirrored source row
 };
-template <bool U16>
-R2L_HD void r2l_fs_fetch(const R2LFwdStreamArgs& a, size_t img0, int ym, int x0, bool le, bool re, int lane,
-                         R2LFsStage& s) {
-  const size_t e = img0 + (size_t)ym * a.W + x0;
-  s.ym = ym;
-  s.e = 0.f;
-  if (U16) {
-    const unsigned short* r = a.raw.u16 + e;
-    const r2l_f2 b = *(const r2l_f2*)r;
-    s.c.x = b.x;
-    s.c.y = b.y;
-    if ((lane == 0 && !le) || (lane == 63 && !re)) s.e = r2l_u2f((unsigned)(lane == 0 ? r[-1] : r[4]));
-  } else {
-    const float* r = a.raw.f32 + e;
-    s.c = r2l_stream_load_f4(r);
-    if ((lane == 0 && !le) || (lane == 63 && !re)) s.e = (lane == 0) ? r[-1] : r[4];
-  }
-}
-// ... branch-free: every lane loads an edge value from an in-row address, only the strip's first / last lane use theirs
+// branch-free: every lane loads an edge value from an in-row address, only the strip's first / last lane use theirs
 // (a load under a lane-dependent or uniform condition in the row loop makes hipcc wait with vmcnt(0) in every step)
 template <bool U16>
 R2L_HD void r2l_fs_fetch_bf(const R2LFwdStreamArgs& a, size_t img0, int ym, int x0, bool le, bool re, int lane,
@@ -189,12 +164,8 @@ struct R2LFsState {
 // 3x3 stencil with per-column-parity weights on a 6-wide 3-row window -> 4 outputs as 2 pairs.  A window row is three
 // aligned pairs P0 = (w0,w1), P1 = (w2,w3), P2 = (w4,w5); the middle tap's operands straddle them: ONE v_pk_mov_b32 each
 // (r2l_straddle) -- written as r2l_mk2(row[1], row[2]) hipcc copies both halves with a v_mov_b32 each, at every use.
-#ifndef R2L_STENCIL_STRADDLE
-#define R2L_STENCIL_STRADDLE 1
-#endif
 // the pairs of a 6-wide window row at column offsets 0, 1, 2: x[j][p] = (row[2p + j], row[2p + j + 1])
 R2L_HD void r2l_row_pairs(const float* row, r2l_p2 x[3][2]) {
-#if R2L_STENCIL_STRADDLE
   const r2l_p2 P0 = r2l_mk2(row[0], row[1]), P1 = r2l_mk2(row[2], row[3]), P2 = r2l_mk2(row[4], row[5]);
   x[0][0] = P0;
   x[0][1] = P1;
@@ -202,18 +173,11 @@ R2L_HD void r2l_row_pairs(const float* row, r2l_p2 x[3][2]) {
   x[1][1] = r2l_straddle(P1, P2);
   x[2][0] = P1;
   x[2][1] = P2;
-#else
-  R2L_PRAGMA_UNROLL
-  for (int j = 0; j < 3; ++j)
-    R2L_PRAGMA_UNROLL
-  for (int p = 0; p < 2; ++p) x[j][p] = r2l_mk2(row[2 * p + j], row[2 * p + j + 1]);
-#endif
 }
 template <class WT>
 R2L_HD void r2l_fs_stencil_parity(const float* r0, const float* r1, const float* r2, WT w /* [9][2] */, r2l_p2 o[2]) {
   o[0] = o[1] = r2l_splat2(0.f);
   const float* rows[3] = {r0, r1, r2};
-#if R2L_STENCIL_STRADDLE
   R2L_PRAGMA_UNROLL
   for (int i = 0; i < 3; ++i) {
     const r2l_p2 P0 = r2l_mk2(rows[i][0], rows[i][1]), P1 = r2l_mk2(rows[i][2], rows[i][3]), P2 = r2l_mk2(rows[i][4], rows[i][5]);
@@ -226,23 +190,12 @@ R2L_HD void r2l_fs_stencil_parity(const float* r0, const float* r1, const float*
       for (int p = 0; p < 2; ++p) o[p] = r2l_pfma(wy, x[j][p], o[p]);
     }
   }
-#else
-  R2L_PRAGMA_UNROLL
-  for (int i = 0; i < 3; ++i)
-    R2L_PRAGMA_UNROLL
-  for (int j = 0; j < 3; ++j) {
-    const r2l_p2 wy = r2l_mk2(w[i * 3 + j][0], w[i * 3 + j][1]);
-    R2L_PRAGMA_UNROLL
-    for (int p = 0; p < 2; ++p) o[p] = r2l_pfma(wy, r2l_mk2(rows[i][2 * p + j], rows[i][2 * p + j + 1]), o[p]);
-  }
-#endif
 }
 // the same with ONE weight per tap for both halves (the sharpen): 3x3 cross-correlation on a 6-wide 3-row window
 template <class WT>
 R2L_HD void r2l_fs_stencil_plain(const float* r0, const float* r1, const float* r2, WT w /* [9] */, r2l_p2 o[2]) {
   o[0] = o[1] = r2l_splat2(0.f);
   const float* rows[3] = {r0, r1, r2};
-#if R2L_STENCIL_STRADDLE
   R2L_PRAGMA_UNROLL
   for (int i = 0; i < 3; ++i) {
     const r2l_p2 P0 = r2l_mk2(rows[i][0], rows[i][1]), P1 = r2l_mk2(rows[i][2], rows[i][3]), P2 = r2l_mk2(rows[i][4], rows[i][5]);
@@ -255,16 +208,6 @@ R2L_HD void r2l_fs_stencil_plain(const float* r0, const float* r1, const float* 
       for (int p = 0; p < 2; ++p) o[p] = r2l_pfma(ws, x[j][p], o[p]);
     }
   }
-#else
-  R2L_PRAGMA_UNROLL
-  for (int i = 0; i < 3; ++i)
-    R2L_PRAGMA_UNROLL
-  for (int j = 0; j < 3; ++j) {
-    const r2l_p2 ws = r2l_splat2(w[i * 3 + j]);
-    R2L_PRAGMA_UNROLL
-    for (int p = 0; p < 2; ++p) o[p] = r2l_pfma(ws, r2l_mk2(rows[i][2 * p + j], rows[i][2 * p + j + 1]), o[p]);
-  }
-#endif
 }
 
 // the colour code of one output row (:203-217): Y'', U, V of the lane's 4 pixels -> RGB, clip, gamma, [statistics about the
@@ -272,9 +215,6 @@ R2L_HD void r2l_fs_stencil_plain(const float* r0, const float* r1, const float* 
 // STATS: 0 none; 1 the streaming kernel's form (under `a.stat_partial && store_ok`); 2 branch-free, weighted with smask
 // (1 for the pixels that count, 0 for the others), the pivot taken in the band's first row (`first`); 3 the sums of BatchNorm's
 // backward over grad_out (gk: this row's grad_out as pairs)
-#ifndef R2L_OUT_NT
-#define R2L_OUT_NT 1
-#endif
 template <bool EPI, int STATS>
 R2L_HD void r2l_fs_colour(const R2LFwdStreamArgs& a, R2LFoldedRef F, r2l_p2* acc, float* piv, const r2l_p2 ypp[2],
                           const r2l_p2 u[2], const r2l_p2 v[2], int y, int y0, int x0, float* ob, unsigned plane,
@@ -329,31 +269,19 @@ R2L_HD void r2l_fs_colour(const R2LFwdStreamArgs& a, R2LFoldedRef F, r2l_p2* acc
         // the output goes AROUND the caches (nontemporal): 12 B/px that this pass never reads again would otherwise push the raw
         // frames and Y' -- which the neighbouring bands and the backward re-read -- out of the memory-side cache: apply pass
         // 72.8 -> 64.9 us at 64x512x512, bn_reduce (which reads the output later) +0.5 (profiles/r05_nt_stores.txt;
-        // -DR2L_OUT_NT=0: the plain store).  The kept planes Y', dL/dY'', HP stay cached: their readers follow at once.
-#if R2L_OUT_NT
+        // measured).  The kept planes Y', dL/dY'', HP stay cached: their readers follow at once.
         r2l_store_f4_nt(ob + (unsigned)k * plane + off0, s4);
-#else
-        *(r2l_f4*)(ob + (unsigned)k * plane + off0) = s4;
-#endif
       } else {  // the augmented position of this lane's 4 pixels (R2LEpi)
         float* o = ob + (unsigned)k * plane + (a.ep.s0 + a.ep.sr * y + a.ep.sc * x0);
         if (a.ep.sc == 1) {
-#if R2L_OUT_NT
           r2l_store_f4_nt(o, s4);
-#else
-          *(r2l_f4*)o = s4;
-#endif
         } else if (a.ep.sc == -1) {
           r2l_f4 r4;
           r4.x = s4.w;
           r4.y = s4.z;
           r4.z = s4.y;
           r4.w = s4.x;
-#if R2L_OUT_NT
           r2l_store_f4_nt(o - 3, r4);
-#else
-          *(r2l_f4*)(o - 3) = r4;
-#endif
         } else {
           o[0] = s4.x;
           o[a.ep.sc] = s4.y;
@@ -365,9 +293,9 @@ R2L_HD void r2l_fs_colour(const R2LFwdStreamArgs& a, R2LFoldedRef F, r2l_p2* acc
   }
 }
 
-// K: ring position of the step (window / chroma-ring slots); PYQ: parity of row q; FULL: the driver runs every group of 6
-// steps in full (r2l_fwd_stream_block) -- rows past the band's end are computed and neither stored nor counted
-template <int NW, bool U16, int K, bool EPI, int PYQ = (K & 1), bool FULL = false>
+// K: ring position of the step (window / chroma-ring slots); PYQ: parity of row q.  The driver runs every group of 6 steps
+// in full (r2l_fwd_stream_block) -- rows past the band's end are computed and neither stored nor counted
+template <int NW, bool U16, int K, bool EPI, int PYQ = (K & 1)>
 R2L_HD void r2l_fs_step(const R2LFwdStreamArgs& a, R2LFsState& st, int q, int y0, int y1, bool le, bool re,
                         int wave, int lane, float* ex, r2l_f4* fifo, float* ob, float* ypb, unsigned plane, int x0,
                         bool store_ok, const float mean[3], const float istd[3], float smask) {
@@ -393,11 +321,7 @@ R2L_HD void r2l_fs_step(const R2LFwdStreamArgs& a, R2LFsState& st, int q, int y0
   // ---- strip edges: Y(q) (1 column each side) and Y'(q-2) (2 columns each side) ------------------------------
   float* ypq2 = st.yp[(K + 4) % 6];  // Y'(q-2): own columns in [2..5], neighbours still missing
   float rl_y = 0.f, rl_p2 = 0.f, rl_p3 = 0.f, rr_y = 0.f, rr_p0 = 0.f, rr_p1 = 0.f;
-#ifdef R2L_EXP_NO_FS_EXCH  // (timing-only ablation: no strip-edge exchange at all)
-  constexpr bool EXCH = false;
-#else
   constexpr bool EXCH = NW > 1;
-#endif
   if (EXCH) {
     float* mine = ex + ((q & 1) * NW + wave) * R2L_FS_EX;
     if (lane == 0) {
@@ -433,9 +357,7 @@ R2L_HD void r2l_fs_step(const R2LFwdStreamArgs& a, R2LFsState& st, int q, int y0
   }
   if (EXCH) {
     float* mine = ex + ((q & 1) * NW + wave) * R2L_FS_EX;
-#ifndef R2L_EXP_NO_FS_BARRIER  // (timing-only ablation: the strip edges read whatever the neighbour wrote last)
     R2L_LDS_BARRIER();
-#endif
     if (lane == 0 && wave > 0) {
       const float* o = mine - R2L_FS_EX;
       rl_y = o[3];
@@ -485,12 +407,10 @@ R2L_HD void r2l_fs_step(const R2LFwdStreamArgs& a, R2LFsState& st, int q, int y0
   }
   // ---- output row y = q-4 ------------------------------------------------------------------------------------
   const int y = q - 4;
-  const bool row_ok = y < y1;  // FULL: rows past the band's end (the padding steps of its last group)
-  if (FULL) {
-    store_ok = store_ok && row_ok;
-    smask = row_ok ? smask : 0.f;
-  }
-  if (y >= y0 && (FULL || row_ok)) {
+  const bool row_ok = y < y1;  // rows past the band's end: the padding steps of its last group
+  store_ok = store_ok && row_ok;
+  smask = row_ok ? smask : 0.f;
+  if (y >= y0) {
     r2l_p2 ypp[2];
     {
       // window rows y-2 .. y+2 = q-6 .. q-2 sit in ring slots K .. K+4
@@ -502,13 +422,8 @@ R2L_HD void r2l_fs_step(const R2LFwdStreamArgs& a, R2LFsState& st, int q, int y0
       // the first / last two image rows take the weight sets with the mirror padding folded in (a padding row past the
       // image's last row: any finite weights)
       const int set = (y < 2) ? y : (y - (H - 2)) + 2;
-#ifdef R2L_EXP_CONST_WEIGHTS
-    const float* w25 = &Fh.blur[0];  // (timing only: no border sets)
-    (void)set;
-#else
       const R2L_CONSTAS float* w25 =
           ((y >= 2 && y < H - 2) || y >= H) ? &Fh.blur[0] : &F.blur_edge[0][0] + 25 * set;
-#endif
       r2l_blur_row2w(yw, w25, ypp);
     }
     const r2l_f4* f = fifo + ((K + 2) % R2L_FS_FIFO_ROWS) * 2 * 64 + lane;  // row q-4
@@ -530,11 +445,7 @@ R2L_HD void r2l_fs_step(const R2LFwdStreamArgs& a, R2LFsState& st, int q, int y0
       s4.y = ypy[3];
       s4.z = ypy[4];
       s4.w = ypy[5];
-#ifdef R2L_EXP_YP_NT
-      r2l_store_f4_nt(ypb + off0, s4);
-#else
       *(r2l_f4*)(ypb + off0) = s4;
-#endif
     }
   }
   // rows of Y' that lie outside the image only ever meet zero weights, but must stay finite
@@ -682,7 +593,7 @@ R2L_BLOCKFN void r2l_fwd_stream_block(const R2LFwdStreamArgs& a, int bid, int nb
   // cost no registers
   double* tots = (double*)(lds + 2 * NW * R2L_FS_EX + 16 + R2L_FS_RING_FLOATS(NW)) + wave * 6;
   if (lane < 6) tots[lane] = 0.0;
-  // the chroma ring starts out as zeros: the padding steps of a band's last group (R2L_FS_FULL_GROUPS) read ring rows this item
+  // the chroma ring starts out as zeros: the padding steps of a band's last group read ring rows this item
   // never wrote -- harmless garbage only as long as fmin(fmax(NaN, 1e-5), 1) clamps a NaN before the 0 / 1 mask multiplies it;
   // with defined contents nothing depends on that (12 LDS stores per lane, once per kernel; later items see earlier items' rows)
   {
@@ -698,7 +609,7 @@ R2L_BLOCKFN void r2l_fwd_stream_block(const R2LFwdStreamArgs& a, int bid, int nb
   // behind it, and behind the statistics' tail -- 4 records per workgroup at tl[4 * bid]
   const unsigned long long tls1_ = __builtin_amdgcn_s_memrealtime();
 #endif
-  for (int item = r2l_xcd_window(bid, nblk, a.xcdm); item < a.nitems; item += nblk) {
+  for (int item = bid; item < a.nitems; item += nblk) {
     const int band = item % a.nband, b = item / a.nband;
     const int y0 = band * a.band_h;
     const int y1 = (y0 + a.band_h < a.H) ? y0 + a.band_h : a.H;
@@ -716,7 +627,6 @@ R2L_BLOCKFN void r2l_fwd_stream_block(const R2LFwdStreamArgs& a, int bid, int nb
     for (int i = 0; i < 6; ++i)
       R2L_PRAGMA_UNROLL
     for (int j = 0; j < 8; ++j) st.yp[i][j] = 0.f;
-#if R2L_FS_FULL_GROUPS
     // first luma row computed: qf = y0 - 3 (Y'(y0-2) needs Y(y0-3)); steps s = 0, 1, ... with q = qf + s, unrolled 6-fold:
     // the ring position of a step is s mod 6 (every window slot a compile-time index), the parity of its row (s + 1) mod 2
     // (bands start on even rows).  EVERY group of 6 runs in full and every fetch is unconditional (r2l_fs_fetch_bf, rows
@@ -728,8 +638,8 @@ R2L_BLOCKFN void r2l_fwd_stream_block(const R2LFwdStreamArgs& a, int bid, int nb
       const int qf = y0 - 3, q1 = y1 + 4;  // q1: exclusive, = the last raw row the band consumes
       {
         R2LFsStage s0, s1;
-        r2l_fs_fetch_bf<U16>(a, img, r2l_mirror(R2L_NH(qf - 1), a.H), x0, le, re, lane, s0);
-        r2l_fs_fetch_bf<U16>(a, img, r2l_mirror(R2L_NH(qf), a.H), x0, le, re, lane, s1);
+        r2l_fs_fetch_bf<U16>(a, img, r2l_mirror(qf - 1, a.H), x0, le, re, lane, s0);
+        r2l_fs_fetch_bf<U16>(a, img, r2l_mirror(qf, a.H), x0, le, re, lane, s1);
         r2l_fs_convert<U16>(a, F, s0, le, re, st.v[2]);
         r2l_fs_convert<U16>(a, F, s1, le, re, st.v[0]);
       }
@@ -737,7 +647,7 @@ R2L_BLOCKFN void r2l_fwd_stream_block(const R2LFwdStreamArgs& a, int bid, int nb
       R2L_PRAGMA_UNROLL
       for (int i = 0; i < PF; ++i) {
         const int rr = (qf + 1 + i < q1) ? qf + 1 + i : q1;
-        r2l_fs_fetch_bf<U16>(a, img, r2l_mirror(R2L_NH(rr), a.H), x0, le, re, lane, pf[i]);
+        r2l_fs_fetch_bf<U16>(a, img, r2l_mirror(rr, a.H), x0, le, re, lane, pf[i]);
       }
       const int nsteps = q1 - qf;
 #if defined(R2L_EXP_STAMPS) && !defined(R2L_EMUL)
@@ -756,9 +666,9 @@ R2L_BLOCKFN void r2l_fwd_stream_block(const R2LFwdStreamArgs& a, int bid, int nb
     r2l_fs_convert<U16>(a, F, pf[K % PF], le, re, st.v[(K + 1) % 3]);                                           \
     {                                                                                                           \
       const int rr_ = (q + 1 + PF < q1) ? q + 1 + PF : q1;                                                      \
-      r2l_fs_fetch_bf<U16>(a, img, r2l_mirror(R2L_NH(rr_), a.H), x0, le, re, lane, pf[K % PF]);                         \
+      r2l_fs_fetch_bf<U16>(a, img, r2l_mirror(rr_, a.H), x0, le, re, lane, pf[K % PF]);                         \
     }                                                                                                           \
-    r2l_fs_step<NW, U16, K, EPI, (K + 1) & 1, true>(a, st, q, y0, y1, le, re, wave, lane, ex, fifo,             \
+    r2l_fs_step<NW, U16, K, EPI, (K + 1) & 1>(a, st, q, y0, y1, le, re, wave, lane, ex, fifo,             \
                                                    SONLY ? nullptr : ob, ypb, plane, x0, store_ok, mean, istd, smask); \
     R2L_FS_STEP_STAMP(sb + K)                                                                                   \
   }
@@ -771,65 +681,6 @@ R2L_BLOCKFN void r2l_fwd_stream_block(const R2LFwdStreamArgs& a, int bid, int nb
 #undef R2L_FS_STEP
       }
     }
-#else
-    // first luma row computed: qf = y0 - 3 (Y'(y0-2) needs Y(y0-3)).  The loop is unrolled 6-fold with q = qb + K,
-    // qb a multiple of 6, so that every window slot is a compile-time index; the first pass enters it at K0 = qf - q0
-    // (the steps before qf are skipped, not computed), and the warm-up rows go to the slots that position implies.
-    const int qf = y0 - 3;
-    const int q0 = (qf >= 0) ? qf - qf % 6 : -(((-qf) + 5) / 6) * 6;
-    const int k0 = qf - q0;
-    const int q1 = y1 + 4;  // exclusive: output row y1-1 leaves at step q = y1+3
-    {
-      R2LFsStage s0, s1;
-      r2l_fs_fetch<U16>(a, img, r2l_mirror(R2L_NH(qf - 1), a.H), x0, le, re, lane, s0);
-      r2l_fs_fetch<U16>(a, img, r2l_mirror(R2L_NH(qf), a.H), x0, le, re, lane, s1);
-      switch (k0 % 3) {  // rows qf-1, qf -> slots (k0 + 2) % 3, k0 % 3
-        case 0:
-          r2l_fs_convert<U16>(a, F, s0, le, re, st.v[2]);
-          r2l_fs_convert<U16>(a, F, s1, le, re, st.v[0]);
-          break;
-        case 1:
-          r2l_fs_convert<U16>(a, F, s0, le, re, st.v[0]);
-          r2l_fs_convert<U16>(a, F, s1, le, re, st.v[1]);
-          break;
-        default:
-          r2l_fs_convert<U16>(a, F, s0, le, re, st.v[1]);
-          r2l_fs_convert<U16>(a, F, s1, le, re, st.v[2]);
-          break;
-      }
-    }
-    R2LFsStage pf[PF];  // ring: step K consumes pf[K % PF] (raw row q + 1) and refills it with row q + 1 + PF
-    R2L_PRAGMA_UNROLL
-    for (int i = 0; i < PF; ++i) {
-      R2LFsStage t;
-      r2l_fs_fetch<U16>(a, img, r2l_mirror(R2L_NH(qf + 1 + i), a.H), x0, le, re, lane, t);
-      R2L_PRAGMA_UNROLL
-      for (int j = 0; j < PF; ++j)
-        if ((k0 + i) % PF == j) pf[j] = t;
-    }
-    for (int qb = q0; qb < q1; qb += 6) {
-      R2L_PROGRESS_PRIO(qb - q0, q1 - q0);
-#define R2L_FS_STEP(K)                                                                                          \
-  if (qb + K >= qf && qb + K < q1) {                                                                            \
-    const int q = qb + K;                                                                                       \
-    R2L_PROGRESS_PRIO_STEP(q - q0, q1 - q0);                                                                    \
-    r2l_fs_convert<U16>(a, F, pf[K % PF], le, re, st.v[(K + 1) % 3]);                                           \
-    if (R2L_FS_BF_FETCH) {                                                                                      \
-      const int rr_ = (q + 1 + PF < q1) ? q + 1 + PF : q1;                                                      \
-      r2l_fs_fetch_bf<U16>(a, img, r2l_mirror(R2L_NH(rr_), a.H), x0, le, re, lane, pf[K % PF]);                         \
-    } else if (q + 1 + PF <= q1)                                                                                \
-      r2l_fs_fetch<U16>(a, img, r2l_mirror(R2L_NH(q + 1 + PF), a.H), x0, le, re, lane, pf[K % PF]);                     \
-    r2l_fs_step<NW, U16, K, EPI>(a, st, q, y0, y1, le, re, wave, lane, ex, fifo, ob, ypb, plane, x0, store_ok, mean, istd, smask); \
-  }
-      R2L_FS_STEP(0)
-      R2L_FS_STEP(1)
-      R2L_FS_STEP(2)
-      R2L_FS_STEP(3)
-      R2L_FS_STEP(4)
-      R2L_FS_STEP(5)
-#undef R2L_FS_STEP
-    }
-#endif
     if (NW > 1) R2L_LDS_BARRIER();  // exchange buffers free for the next item
     if (SONLY || a.stat_partial) r2l_fs_lane_sums(st.acc, st.piv, store_ok ? 4.0 * (double)(y1 - y0) : 0.0, store_ok, lane, tots);
   }
@@ -890,14 +741,11 @@ R2L_HD void r2l_fa_fetch_raw(const R2LFwdStreamArgs& a, size_t img0, int ym, int
     s.e = r[eo];
   }
 }
-// NT: the caller is the LAST reader of this plane in the step -- the row goes around the caches (the edge pair, which the neighbouring
-// strip's wavefront also loads as part of its row, stays a plain load)
-template <bool NT = false>
 R2L_HD void r2l_fa_fetch(const float* ypimg, int r, int H, int W, int x0, bool le, bool re, int lane, R2LFaStage& s) {
   const int rc = r < 0 ? 0 : (r >= H ? H - 1 : r);  // rows outside the image are zeroed when the row is built
   const float* p = ypimg + (size_t)rc * W + x0;
   const int eo = (lane < 32) ? (le ? 0 : -2) : (re ? 2 : 4);
-  s.c = NT ? r2l_load_f4_nt(p) : r2l_stream_load_f4(p);
+  s.c = r2l_stream_load_f4(p);
   s.e = *(const r2l_f2*)(p + eo);
 }
 // staged row -> 8 values, columns x0-2 .. x0+5 (mirror padding of the blur at the image edges, :165 reflect)
@@ -951,13 +799,8 @@ R2L_HD void r2l_fa_step(const R2LFwdStreamArgs& a, R2LFaState& st, r2l_p2* acc, 
       R2L_PRAGMA_UNROLL
     for (int j = 0; j < 8; ++j) yw[i][j] = st.yp[(K + 4 + i) % 6][j];
     const int set = (y < 2) ? y : (y - (H - 2)) + 2;
-#ifdef R2L_EXP_CONST_WEIGHTS
-    const float* w25 = &Fb.blur[0];  // (timing only: no border sets)
-    (void)set;
-#else
     const R2L_CONSTAS float* w25 =
         (y >= 2 && y < H - 2) ? &Fb.blur[0] : &Fb.blur_edge[0][0] + 25 * set;
-#endif
     r2l_blur_row2w(yw, w25, ypp);
   }
   R2LFoldedRef Fc = R2L_FOLDED_REF(r2l_opaque_after(a.F, ypp[1][1]));
@@ -1009,15 +852,15 @@ R2L_HD void r2l_fa_item(const R2LFwdStreamArgs& a, int item, int lane, const flo
   // step q builds V(q+1) and Y'(q+2); from q = y0 on it also finishes output row q.  Warm-up: q = y0-4 .. y0-1 = K 2 .. 5.
   R2L_PRAGMA_UNROLL
   for (int i = 0; i < PF; ++i) {
-    r2l_fa_fetch_raw<U16>(a, img, r2l_mirror(R2L_NH(y0 - 3 + i), a.H), x0, le, re, lane, pf[(2 + i) % PF]);
-    r2l_fa_fetch(ypimg, R2L_NH(y0 - 2 + i), a.H, a.W, x0, le, re, lane, pfy[(2 + i) % PF]);
+    r2l_fa_fetch_raw<U16>(a, img, r2l_mirror(y0 - 3 + i, a.H), x0, le, re, lane, pf[(2 + i) % PF]);
+    r2l_fa_fetch(ypimg, y0 - 2 + i, a.H, a.W, x0, le, re, lane, pfy[(2 + i) % PF]);
   }
 #define R2L_FA_LOAD_STEP(K, q)                                                                          \
   {                                                                                                     \
     r2l_fs_convert<U16>(a, F, pf[(K) % PF], le, re, st.v[((K) + 1) % 3]);                               \
     r2l_fa_build(pfy[(K) % PF], (unsigned)((q) + 2) < (unsigned)a.H, le, re, st.yp[((K) + 2) % 6]);     \
-    r2l_fa_fetch_raw<U16>(a, img, r2l_mirror(R2L_NH((q) + 1 + PF), a.H), x0, le, re, lane, pf[(K) % PF]);       \
-    r2l_fa_fetch(ypimg, R2L_NH((q) + 2 + PF), a.H, a.W, x0, le, re, lane, pfy[(K) % PF]);                       \
+    r2l_fa_fetch_raw<U16>(a, img, r2l_mirror((q) + 1 + PF, a.H), x0, le, re, lane, pf[(K) % PF]);       \
+    r2l_fa_fetch(ypimg, (q) + 2 + PF, a.H, a.W, x0, le, re, lane, pfy[(K) % PF]);                       \
   }
   R2L_FA_LOAD_STEP(2, y0 - 4)
   R2L_FA_LOAD_STEP(3, y0 - 3)
@@ -1030,7 +873,6 @@ R2L_HD void r2l_fa_item(const R2LFwdStreamArgs& a, int item, int lane, const flo
 #define R2L_FA_STEP(K)                                                                                  \
   {                                                                                                     \
     const int q = qb + K;                                                                               \
-    R2L_PROGRESS_PRIO_STEP(q - y0, y1 - y0);                                                            \
     R2L_FA_LOAD_STEP(K, q)                                                                              \
     if (!STATS || r2l_opaque_true())                                                                    \
       r2l_fa_step<K, EPI, STATS>(a, st, acc, piv, q, y0, in_w && q < y1, ob, plane, x0, mean, istd);    \
@@ -1062,7 +904,7 @@ R2L_BLOCKFN void r2l_fwd_apply_block(const R2LFwdStreamArgs& a, int bid, int nbl
     }
     // one item per wavefront; NWV wavefronts per workgroup only because the dispatcher starts ~250 workgroups per
     // microsecond: 4,096 single-wavefront workgroups take 15 us to launch (tests/timeline_fwd.py)
-    const int item = r2l_xcd_window(bid, nblk, a.xcdm) * NWV + wave;
+    const int item = bid * NWV + wave;
     if (item < a.nitems) r2l_fa_item<U16, EPI, false>(a, item, lane, mean, istd, nullptr);
     R2L_TL_END(a, bid)
   } else {
@@ -1070,7 +912,7 @@ R2L_BLOCKFN void r2l_fwd_apply_block(const R2LFwdStreamArgs& a, int bid, int nbl
     double* tots = (double*)(lds + 16 + R2L_FS_RED_FLOATS(NWV)) + wave * 6;
     if (lane < 6) tots[lane] = 0.0;
     R2L_PRAGMA_NOUNROLL
-    for (int item = r2l_xcd_window(bid, nblk, a.xcdm) * NWV + wave; item < a.nitems; item += nblk * NWV)
+    for (int item = bid * NWV + wave; item < a.nitems; item += nblk * NWV)
       r2l_fa_item<U16, false, true>(a, item, lane, mean, istd, tots);
     R2L_TL_END(a, bid)
     r2l_fs_stats_finish<NWV, NWV * 64>(a, bid, nblk, tid, wave, tots, red);
@@ -1090,7 +932,7 @@ struct R2LFlStage {
   r2l_f2 e;  // columns (x0-2, x0-1) in the first half of the wavefront, (x0+4, x0+5) in the second: (even, odd)
   int ym;
 };
-template <bool U16, bool NT = false>
+template <bool U16>
 R2L_HD void r2l_fl_fetch(const R2LFwdStreamArgs& a, size_t img0, int ym, int x0, bool le, bool re, int lane,
                          R2LFlStage& s) {
   const size_t e = img0 + (size_t)ym * a.W + x0;
@@ -1104,7 +946,7 @@ R2L_HD void r2l_fl_fetch(const R2LFwdStreamArgs& a, size_t img0, int ym, int x0,
     s.e.x = *(const float*)(r + eo);  // two 16-bit values
   } else {
     const float* r = a.raw.f32 + e;
-    s.c = NT ? r2l_load_f4_nt(r) : r2l_stream_load_f4(r);
+    s.c = r2l_stream_load_f4(r);
     s.e = *(const r2l_f2*)(r + eo);
   }
 }
@@ -1202,7 +1044,7 @@ template <bool U16, int NWV>
 R2L_BLOCKFN void r2l_fwd_luma_block(const R2LFwdStreamArgs& a, int bid, int nblk, float* lds) {
   (void)lds;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  const int item = r2l_xcd_window(bid, nblk, a.xcdm) * NWV + wave;  // one item per wavefront (NWV per workgroup: see r2l_fwd_apply_block)
+  const int item = bid * NWV + wave;  // one item per wavefront (NWV per workgroup: see r2l_fwd_apply_block)
   if (item >= a.nitems) return;
   R2LFoldedRef F = R2L_FOLDED_REF(a.F);
   const int nstrip = (a.W + 255) >> 8;
@@ -1224,11 +1066,11 @@ R2L_BLOCKFN void r2l_fwd_luma_block(const R2LFwdStreamArgs& a, int bid, int nblk
   // warm-up: y = y0-4 (V(y0-2)), y0-3 (V(y0-1)), y0-2 (V(y0), Y(y0-1)), y0-1 (V(y0+1), Y(y0)) = K 2 .. 5
   R2L_PRAGMA_UNROLL
   for (int i = 0; i < PF; ++i)
-    r2l_fl_fetch<U16>(a, img, r2l_mirror(R2L_NH(y0 - 2 + i), a.H), x0, le, re, lane, pf[(2 + i) % PF]);
+    r2l_fl_fetch<U16>(a, img, r2l_mirror(y0 - 2 + i, a.H), x0, le, re, lane, pf[(2 + i) % PF]);
 #define R2L_FL_STEP(K, y, LUMA, OUT)                                                                    \
   {                                                                                                     \
     r2l_fl_convert<U16>(a, F, pf[(K) % PF], le, re, st.v[((K) + 2) % 3], st.xp[((K) + 2) % 3]);                      \
-    r2l_fl_fetch<U16>(a, img, r2l_mirror(R2L_NH((y) + 2 + PF), a.H), x0, le, re, lane, pf[(K) % PF]);           \
+    r2l_fl_fetch<U16>(a, img, r2l_mirror((y) + 2 + PF, a.H), x0, le, re, lane, pf[(K) % PF]);           \
     r2l_fl_step<K, LUMA, OUT>(a, st, y, le, re, in_w && (y) < y1, ypb, x0);                             \
   }
   R2L_FL_STEP(2, y0 - 4, false, false)

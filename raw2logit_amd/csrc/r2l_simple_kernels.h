@@ -163,7 +163,6 @@ struct R2LBnReduceArgs {
   double* sums;
   const double* totals;  // optional: totals[6] = pixel count n of the global batch
   float* bn_bwd;         // optional (needs totals): mean_c(g)[3], mean_c(g*xhat)[3] = sums / n as float32
-  int order;             // 0: items in memory order; 1: from the end of the tensors to their start (diagnostic builds)
 };
 struct R2LAcc6 {
   float acc[6];
@@ -182,11 +181,7 @@ R2L_HD void r2l_bn_reduce_item(int tid, const R2LBnReduceArgs& a, int item, int 
     if (e < hw) {
       // nontemporal: 400 MB read once; plain loads also evict the raw frames and dL/dY'' that the two backward
       // kernels are about to re-read (82 -> 65 us here, -8 us in bwd1, -5 us in bwd2)
-#ifdef R2L_BNR_GOUT_PLAIN  // A/B builds: grad_out allocates in the caches on its way through (kernel B1 reads it again right away)
-      const r2l_f4 gv = *(const r2l_f4*)(g + e);
-#else
       const r2l_f4 gv = r2l_load_f4_nt(g + e);
-#endif
       const r2l_f4 ov = r2l_load_f4_nt(o + e);
       sg += (gv.x + gv.y) + (gv.z + gv.w);
       sgx = fmaf(gv.x, ov.x, sgx);
@@ -212,7 +207,7 @@ R2L_BLOCKFN void r2l_bn_reduce_block(const R2LBnReduceArgs& a, int bid, int nblk
   const int nitems = 3 * a.B * nsegpp;
   R2L_PHASE_BEGIN  // one phase: the wavefronts stream independently (a barrier per item would cap the loads in flight)
   for (int item = bid; item < nitems; item += nblk)
-    r2l_bn_reduce_item(tid, a, a.order ? nitems - 1 - item : item, nsegpp, R2L_TREG(regs));
+    r2l_bn_reduce_item(tid, a, item, nsegpp, R2L_TREG(regs));
   R2L_PHASE_END
   R2L_TAILST(10);
   R2L_BLOCK_REDUCE(6, regs, lds, a.partial, bid, nblk)

@@ -28,17 +28,6 @@
 // r2l_static_kernels.h), log2 / exp2 in float32.
 #pragma once
 #include "r2l_static_stream.h"
-#ifndef R2L_CHAIN_BF
-#define R2L_CHAIN_BF 1
-#endif
-#ifndef R2L_CHAIN_PROGRESS_PRIO
-#define R2L_CHAIN_PROGRESS_PRIO 1  // (default chain 963 -> 944 us, profiles/r04_static_chain_ab.txt)
-#endif
-#if R2L_CHAIN_PROGRESS_PRIO
-#define R2L_CHAIN_PRIO(d, t) R2L_PROGRESS_PRIO(d, t)
-#else
-#define R2L_CHAIN_PRIO(d, t)
-#endif
 
 #ifndef R2L_SERIAL
 
@@ -120,11 +109,7 @@ R2L_HD void r2l_chain_step(const R2LStaticArgs& a_, R2LChainState<DEB, SH, DN>& 
   constexpr int PY = K0 & 1;
   constexpr int FR = R2L_CHAIN_FIFO_ROWS(SH);
   const int H = a_.H;
-#ifdef R2L_CHAIN_ARGS_LIVE
-  const R2LStaticArgs& a = a_;
-#else
   const R2L_CONSTAS R2LStaticArgs& a = *r2l_chain_consts();
-#endif
   double yq[4];  // Y(q) (new)
   double yp[4];  // the sharpened row it completes
   {
@@ -436,10 +421,10 @@ R2L_BLOCKFN void r2l_static_chain_block(const R2LStaticChainArgs& ca, int bid, i
   constexpr bool LANES = R2L_HAVE_LANE_SHIFTS;
   constexpr int PF = DEB ? 2 : R2L_CHAIN_PF;
   R2LRowStageT<RAWK> stage;
-  // BRANCH-FREE row loop on float32 / 16-bit frames (R2L_CHAIN_BF; r2l_stream_fetch_row_bf): every fetch unconditional
+  // BRANCH-FREE row loop on float32 / 16-bit frames (r2l_stream_fetch_row_bf): every fetch unconditional
   // (rows past the band's last needed one re-fetch that row), every group of 6 steps in full (a step past q1 only finishes
   // rows >= y1, which are not stored) -- hipcc then counts its vmcnt waits instead of waiting for the row just requested
-  constexpr bool BF = R2L_CHAIN_BF && RAWK != R2L_RAW_F64;
+  constexpr bool BF = RAWK != R2L_RAW_F64;
   constexpr unsigned ESZ = (RAWK == R2L_RAW_U16) ? 2u : 4u;
   const unsigned xo = ESZ * (unsigned)x0, xleft = ESZ * (unsigned)(x0 + (le ? 0 : -2)), xright = ESZ * (unsigned)(x0 + (re ? 2 : 4));
   const unsigned xl = LANES ? (lane < 32 ? xleft : xright) : xleft, xr = xright;
@@ -465,7 +450,7 @@ R2L_BLOCKFN void r2l_static_chain_block(const R2LStaticChainArgs& ca, int bid, i
   R2L_PRAGMA_UNROLL
   for (int i = 0; i < PF; ++i) R2L_CHAIN_FETCH(q0 + LA + i, pf[i])
   for (int qb = q0; qb < q1; qb += 6) {
-    R2L_CHAIN_PRIO(qb - q0, q1 - q0);
+    R2L_PROGRESS_PRIO(qb - q0, q1 - q0);  // (default chain 963 -> 944 us, profiles/r04_static_chain_ab.txt)
 #define R2L_CHAIN_STEP(K)                                                                                         \
   if (BF || qb + K < q1) {                                                                                        \
     const int q = qb + K;                                                                                         \

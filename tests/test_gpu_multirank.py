@@ -44,7 +44,7 @@ def _spawn(world, out_dir, backend, cases=None, timeout=900, extra_env=None, ret
     """retry_crash: how often to start over when a rank DIES (killed by a signal / aborted by the runtime: exit code other than 0
     or 1) instead of failing an assertion.  Used by the RCCL graph-capture tests only: a one-rank RCCL group capturing its
     collectives into a HIP graph is a configuration that exists for these tests.  Round 6: that test failed ONCE in 9 full-suite
-    runs (+ 14 clean partial repeats; tests/experiments/r06_suite_repeat.sh), at the end of an 80-minute GPU session, and the
+    runs (+ 14 clean partial repeats of the suite), at the end of an 80-minute GPU session, and the
     report did not survive (the collecting script kept the log's tail only) -- round 5 had seen aborts of the process group's
     watchdog thread during captures (raw2logit_amd/graphs.py).  An abort of the stack must not cost the suite; a wrong bit or any
     Python exception (exit code 1) still does and is never retried.  Every retry is appended to gpurun_out/multirank_retries.txt
