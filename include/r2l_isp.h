@@ -206,6 +206,22 @@ int r2l_isp_step_bwd(const void *raw, int raw_u16, float denom, const float *add
                      const float *out, float *grad_params, float *grad_additive, int bn_mode, void *workspace,
                      size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
                      const double *gathered_sums, void *stream);
+/* r2l_isp_step_bwd_raw = r2l_isp_step_bwd that also writes d loss / d raw into grad_raw ((B,H,W) float32, device memory,
+ * 16-byte aligned), by one more pass over planes behind the gradient kernels; grad_raw = NULL: exactly r2l_isp_step_bwd.
+ * raw_grad_scratch: caller-owned device memory of r2l_isp_raw_grad_scratch_bytes(B, H, W) bytes (16-byte aligned) for the
+ * two chroma gradient planes between the passes; the workspace and r2l_isp_workspace_bytes are those of r2l_isp_step_bwd.
+ * Supported: float32 frames (raw_u16 = 0) with W % 4 == 0 and W <= 2048, no additive layer, no output epilogue, after a
+ * forward with R2L_STEP_KEEP_LUMA (set it in `phase` of both calls); grad_params must be given (the parameter sums run
+ * with it).  Anything else returns -3 with the reason in r2l_last_error(), as does the serial emulation build.  Several
+ * ranks: as r2l_isp_step_bwd (phase A computes the BatchNorm sums, grad_raw is written in phase B).  Deterministic: no
+ * atomics; the output and grad_params are those of r2l_isp_step_bwd on the same backward route (the plane passes, which
+ * this call takes at every size). */
+size_t r2l_isp_raw_grad_scratch_bytes(int B, int H, int W);
+int r2l_isp_step_bwd_raw(const void *raw, int raw_u16, float denom, const float *additive, const float *grad_out,
+                         const float *out, float *grad_params, float *grad_additive, int bn_mode, void *workspace,
+                         size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                         const double *gathered_sums, void *stream, float *grad_raw, void *raw_grad_scratch,
+                         size_t raw_grad_scratch_bytes);
 
 /* ---- static pipeline, numpy semantics (processing(), processing/pipeline_numpy.py:70-141, batched):
  * remove_blacklv (:152-158) -> demosaicing_CFA_Bayer_{bilinear,Malvar2004} (:92-95) -> wb (:161-162) ->

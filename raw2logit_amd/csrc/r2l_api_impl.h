@@ -281,12 +281,26 @@ R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane, R2LBwd1Args, R2L_BP_NT, R2L_BP_LDS_FLOA
 R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane_u16, R2LBwd1Args, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2, r2l_bwd1_plane_block<true, false>)
 R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane_epi, R2LBwd1Args, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2, r2l_bwd1_plane_block<false, true>)
 R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane_epi_u16, R2LBwd1Args, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2, r2l_bwd1_plane_block<true, true>)
+// ... storing the chroma gradient planes gU, gV as well, for the d/d raw pass (float32 frames, no epilogue)
+struct R2LBwd1GuvArgs {
+  R2LBwd1Args b;
+  float* guv;  // gU (B,H,W), then gV (B,H,W)
+};
+R2L_BLOCKFN void r2l_bwd1_plane_guv_block(const R2LBwd1GuvArgs& a, int bid, int nblk, float* lds) {
+  r2l_bwd1_plane_block<false, false, true>(a.b, bid, nblk, lds, a.guv);
+}
+R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane_guv, R2LBwd1GuvArgs, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2, r2l_bwd1_plane_guv_block)
 R2L_KERNEL_NT_LDS(r2l_launch_bwd1_blur, R2LBwd1Args, R2L_BP_NT, R2L_BP_RED_FLOATS, 3, r2l_bwd1_blur_block)
 R2L_KERNEL_NT_LDS(r2l_launch_bwd1_blur_hp, R2LBwd1Args, R2L_BP_NT, R2L_BP_RED_FLOATS, R2L_HB_OCC, r2l_bwd1_blur_hp_block)
 // kernel B2 likewise: the blur's adjoint into a plane, then the sums + the final reduction and unfold
 R2L_KERNEL_NT_LDS(r2l_launch_bwd2_hp, R2LBwd2Args, R2L_BP_NT, 4, 4, r2l_bwd2_hp_block)
 R2L_KERNEL_NT_LDS(r2l_launch_bwd2_sums, R2LBwd2Args, R2L_B2S_NT, R2L_B2S_LDS_FLOATS, 3, r2l_bwd2_sums_block<false>)
 R2L_KERNEL_NT_LDS(r2l_launch_bwd2_sums_u16, R2LBwd2Args, R2L_B2S_NT, R2L_B2S_LDS_FLOATS, 3, r2l_bwd2_sums_block<true>)
+// d/d raw: HP + gU + gV -> grad_raw (independent wavefronts, no LDS)
+#ifndef R2L_BR_OCC
+#define R2L_BR_OCC 3
+#endif
+R2L_KERNEL_NT_LDS(r2l_launch_bwd_raw_plane, R2LRawGradArgs, 64 * R2L_BR_NWV, 4, R2L_BR_OCC, r2l_bwd_raw_plane_block)
 // BatchNorm's backward sums from the raw frame, Y' and grad_out (xhat recomputed, the output not read back): r2l_bnr_planes_block
 #ifndef R2L_BNR_OCC
 #define R2L_BNR_OCC 3
@@ -863,7 +877,7 @@ int r2l_bn_bwd_reduce(const float* grad_out, const float* out, const double* tot
 static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float* additive,
                             const float* bn_mean_istd, const float* bn_bwd, const float* grad_out,
                             float* grad_params, float* grad_raw, void* workspace, size_t workspace_bytes, int B,
-                            int H, int W, int flags, void* stream, const R2LEpi* ep = nullptr) {
+                            int H, int W, int flags, void* stream, const R2LEpi* ep = nullptr, float* guv = nullptr) {
   if (int e = r2l_check_dims(B, H, W)) return e;
   if (int e = r2l_check_raw(raw, W, "r2l_isp_bwd")) return e;
   if (!params || !grad_out || !grad_params || !workspace)
@@ -871,8 +885,9 @@ static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float*
   if (bn_bwd && !bn_mean_istd) return r2l_fail(-1, "r2l_isp_bwd: bn_bwd given without bn_mean_istd");
   if (additive && (H != 256 || W != 256))
     return r2l_fail(-1, "additive_layer is (1,3,256,256): needs 256x256 frames");
-  if (grad_raw)
-    return r2l_fail(-3, "r2l_isp_bwd: grad_raw is produced by the staged path, not the fused kernels");
+  // grad_raw: only r2l_isp_step_bwd_raw, which hands the chroma gradient planes (guv) and has checked the frames
+  if (grad_raw && !guv)
+    return r2l_fail(-3, "r2l_isp_bwd: grad_raw is produced by the staged path or r2l_isp_step_bwd_raw, not this call");
   const R2LWorkspace ws = r2l_carve(workspace, B, H, W);
   if (workspace_bytes < ws.total) return r2l_fail(-2, "r2l_isp_bwd: workspace too small");
   if (!(flags & R2L_F_FOLDED_VALID)) {
@@ -894,7 +909,8 @@ static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float*
   a1.H = H;
   a1.W = W;
   a1.debug = ws.debug + 8 * R2L_MAX_BLOCKS;
-  const bool saved = (flags & R2L_F_KEEP_LUMA) && r2l_fwd_streams(additive, W) && !r2l_env_int("R2L_BWD1_RECOMPUTE", 0);
+  const bool saved = (flags & R2L_F_KEEP_LUMA) && r2l_fwd_streams(additive, W) &&
+                     (grad_raw || !r2l_env_int("R2L_BWD1_RECOMPUTE", 0));
   a1.yp = saved ? ws.yp : nullptr;
   a1.ep = (ep && ep->on) ? *ep : R2LEpi{0, 0, 0, 0};
   a1.band_h = 0;
@@ -908,8 +924,9 @@ static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float*
   // ... where there is enough work for their launch tails: 128x256x256 (8.4 Mpx) 102 us against the tile kernels' 110+,
   // 64x256x256 (4.2 Mpx) 77.7 against 80.5 since the tails were shortened (profiles/r04_small.txt; round 3: 99 against 85,
   // and the threshold was 6 Mi px)
-  const bool planes = r2l_env_int("R2L_BWD_PLANES", 0) || (size_t)B * H * W >= ((size_t)4 << 20);
-  if (saved && planes && !r2l_env_int("R2L_BWD1_TILED", 0)) {
+  // (d/d raw: the plane passes at every size -- the gather pass reads the planes they leave)
+  const bool planes = grad_raw || r2l_env_int("R2L_BWD_PLANES", 0) || (size_t)B * H * W >= ((size_t)4 << 20);
+  if (saved && planes && (grad_raw || !r2l_env_int("R2L_BWD1_TILED", 0))) {
     // persistent workgroups of 4 independent wavefronts, two per CU (<= 256 VGPRs), not more workgroups than kernel B2
     // runs (its last workgroups reduce both kernels' partials); band height as for the forward's plane passes
     const long nstrip = (W + 255) / 256;
@@ -925,11 +942,14 @@ static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float*
   int e1;
   if (g1p) {
 #ifndef R2L_SERIAL
-    e1 = a1.ep.on ? (raw.u16 ? r2l_launch_bwd1_plane_epi_u16(a1, g1p, stream) : r2l_launch_bwd1_plane_epi(a1, g1p, stream))
-                  : (raw.u16 ? r2l_launch_bwd1_plane_u16(a1, g1p, stream) : r2l_launch_bwd1_plane(a1, g1p, stream));
+    if (grad_raw)  // (float32 frames, no epilogue: r2l_isp_step_bwd_raw checked)
+      e1 = r2l_launch_bwd1_plane_guv(R2LBwd1GuvArgs{a1, guv}, g1p, stream);
+    else
+      e1 = a1.ep.on ? (raw.u16 ? r2l_launch_bwd1_plane_epi_u16(a1, g1p, stream) : r2l_launch_bwd1_plane_epi(a1, g1p, stream))
+                    : (raw.u16 ? r2l_launch_bwd1_plane_u16(a1, g1p, stream) : r2l_launch_bwd1_plane(a1, g1p, stream));
     // its second pass (the blur-weight sums) and kernel B2's first (the blur's adjoint) read the same plane: one pass
     // when B2 runs as plane passes too
-    blur_hp = !r2l_env_int("R2L_BWD2_TILED", 0) && !r2l_env_int("R2L_BWD_SPLIT_BLUR", 0);
+    blur_hp = (grad_raw || !r2l_env_int("R2L_BWD2_TILED", 0)) && !r2l_env_int("R2L_BWD_SPLIT_BLUR", 0);
     a1.hp = ws.hp;
     // (its own band height: R2L_HB_OCC wavefronts per SIMD; not more workgroups than wrote the first pass's partials)
     a1.band_hb = r2l_band_rows(B, H, W, 256L * 4 * R2L_HB_OCC, "R2L_HB_BAND");
@@ -968,7 +988,7 @@ static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float*
   // launches do it
   const int g1w = g1p ? g1p : g1;  // workgroups that wrote B1's partials
 #ifndef R2L_SERIAL
-  if (g1p && !r2l_env_int("R2L_BWD2_TILED", 0)) {
+  if (g1p && (grad_raw || !r2l_env_int("R2L_BWD2_TILED", 0))) {
     // kernel B2 as two passes over planes (r2l_param_plane_bwd.h)
     const long nstrip = (W + 255) / 256;
     auto band_rows = [&](long slots, const char* env) { return r2l_band_rows(B, H, W, slots, env); };
@@ -996,9 +1016,16 @@ static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float*
     a2.params = params;
     a2.grad_params = grad_params;
     const int grid = (int)gs + R2L_B2S_HELPERS;
-    return raw.u16 ? r2l_launch_bwd2_sums_u16(a2, grid, stream) : r2l_launch_bwd2_sums(a2, grid, stream);
+    if (int e = raw.u16 ? r2l_launch_bwd2_sums_u16(a2, grid, stream) : r2l_launch_bwd2_sums(a2, grid, stream)) return e;
+    if (!grad_raw) return 0;
+    // d/d raw from HP and the chroma gradient planes (r2l_bwd_raw_plane_block): one item per wavefront
+    R2LRawGradArgs ar{ws.folded, ws.hp, guv, grad_raw, B, H, W, band_rows(256L * 4 * R2L_BR_OCC, "R2L_BR_BAND")};
+    const long ritems = (long)B * nstrip * ((H + ar.band_h - 1) / ar.band_h);
+    if (ritems > (1L << 30)) return r2l_fail(-1, "r2l_isp_step_bwd_raw: batch too large");
+    return r2l_launch_bwd_raw_plane(ar, (int)((ritems + R2L_BR_NWV - 1) / R2L_BR_NWV), stream);
   }
 #endif
+  if (grad_raw) return r2l_fail(-3, "r2l_isp_step_bwd_raw: internal: the plane passes did not run");
   const bool in_kernel = g1w <= g2;
   a2.tree = R2LTree{ws.part_b1, ws.part_b2, ws.gpartial, in_kernel ? ws.counters : nullptr, R2L_B1_NACC, g1w};
   a2.params = params;
@@ -1177,10 +1204,11 @@ static int r2l_bn_bwd_reduce_planes(const R2LRaw& raw, const float* additive, co
 #endif
 }
 
-int r2l_isp_step_bwd(const void* raw, int raw_u16, float denom, const float* additive, const float* grad_out,
-                     const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
-                     size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
-                     const double* gathered_sums, void* stream) {
+static int r2l_isp_step_bwd_impl(const void* raw, int raw_u16, float denom, const float* additive, const float* grad_out,
+                                 const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
+                                 size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                                 const double* gathered_sums, void* stream, float* grad_raw = nullptr,
+                                 float* guv = nullptr) {
   const int keep = (phase & R2L_STEP_KEEP_LUMA) ? R2L_F_KEEP_LUMA : 0;
   R2LEpi ep;
   if (int e = r2l_check_dims(B, H, W)) return e;
@@ -1216,12 +1244,56 @@ int r2l_isp_step_bwd(const void* raw, int raw_u16, float denom, const float* add
     if (int e = r2l_launch_bn_bwd_means(m, 1, stream)) return e;
   }
   if (grad_params) {
-    if (int e = r2l_isp_bwd_impl(rw, ws.packed, additive, bn, bn_bwd, grad_out, grad_params, nullptr, workspace,
-                                 workspace_bytes, B, H, W, R2L_F_FOLDED_VALID | keep, stream, &ep))
+    if (int e = r2l_isp_bwd_impl(rw, ws.packed, additive, bn, bn_bwd, grad_out, grad_params, grad_raw, workspace,
+                                 workspace_bytes, B, H, W, R2L_F_FOLDED_VALID | keep, stream, &ep, guv))
       return e;
   }
   if (grad_additive) return r2l_additive_bwd(grad_out, out, bn, bn_bwd, grad_additive, B, H, W, stream);
   return 0;
+}
+int r2l_isp_step_bwd(const void* raw, int raw_u16, float denom, const float* additive, const float* grad_out,
+                     const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
+                     size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                     const double* gathered_sums, void* stream) {
+  return r2l_isp_step_bwd_impl(raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode, workspace,
+                               workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream);
+}
+size_t r2l_isp_raw_grad_scratch_bytes(int B, int H, int W) {
+  if (B < 1 || H < 1 || W < 1) return 0;
+  return (size_t)2 * B * H * W * sizeof(float);  // gU, gV
+}
+int r2l_isp_step_bwd_raw(const void* raw, int raw_u16, float denom, const float* additive, const float* grad_out,
+                         const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
+                         size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                         const double* gathered_sums, void* stream, float* grad_raw, void* raw_grad_scratch,
+                         size_t raw_grad_scratch_bytes) {
+  if (!grad_raw)
+    return r2l_isp_step_bwd_impl(raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode,
+                                 workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream);
+#ifdef R2L_SERIAL
+  (void)raw_grad_scratch; (void)raw_grad_scratch_bytes;
+  return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw needs the plane passes, which the serial emulation does not have");
+#else
+  if (int e = r2l_check_dims(B, H, W)) return e;
+  if (raw_u16) return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw needs float32 frames (16-bit containers have no gradient)");
+  if (additive) return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw is not produced with an additive layer");
+  if ((W & 3) || W > 2048) return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw needs W % 4 == 0 and W <= 2048");
+  if (r2l_env_int("R2L_FWD_TILED", 0))
+    return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw needs the row-streaming forward (R2L_FWD_TILED is set)");
+  if (phase & R2L_STEP_EPI_MASK) return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw is not produced with an output epilogue");
+  if (!(phase & R2L_STEP_KEEP_LUMA))
+    return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw needs a forward that kept Y' (R2L_STEP_KEEP_LUMA in both calls)");
+  if (!grad_params) return r2l_fail(-1, "r2l_isp_step_bwd_raw: grad_raw needs grad_params (the parameter sums run with it)");
+  if (!raw_grad_scratch) return r2l_fail(-1, "r2l_isp_step_bwd_raw: null raw_grad_scratch");
+  if (raw_grad_scratch_bytes < r2l_isp_raw_grad_scratch_bytes(B, H, W))
+    return r2l_fail(-2, "r2l_isp_step_bwd_raw: raw_grad_scratch too small (r2l_isp_raw_grad_scratch_bytes)");
+  if ((uintptr_t)raw_grad_scratch % 16 || (uintptr_t)grad_raw % 16)
+    return r2l_fail(-1, "r2l_isp_step_bwd_raw: grad_raw and raw_grad_scratch must be 16-byte aligned");
+  // (phase A computes the BatchNorm sums only: the gradient kernels, and with them d/d raw, run in phase B / ALL)
+  return r2l_isp_step_bwd_impl(raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode, workspace,
+                               workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw,
+                               (float*)raw_grad_scratch);
+#endif
 }
 
 static int r2l_raw2rgb_fwd_impl(const R2LRaw& raw, const float* black_level, float* out, int B, int H, int W,

@@ -254,10 +254,11 @@ R2L_HD void r2l_bp_swap(R2LBpAcc& A, float* bank /* this lane's 40 floats, [chun
 #undef R2L_BP_SW
 }
 
-// one output row y (K = y mod 6, row parity K & 1); the windows hold V(y-1 .. y+1) and Y'(y-2 .. y+2)
-template <int K>
+// one output row y (K = y mod 6, row parity K & 1); the windows hold V(y-1 .. y+1) and Y'(y-2 .. y+2).  GUV: the chroma
+// gradients gU, gV of the row are stored too (planes gub, gvb: the input of r2l_bwd_raw_plane_block, d/d raw)
+template <int K, bool GUV = false>
 R2L_HD void r2l_bp_step(const R2LBwd1Args& a, R2LBpState& st, R2LBpAcc& A, const R2LBpStage& gs, int y, bool store_ok,
-                        float* gyb, int x0, const R2LBnConsts& bc) {
+                        float* gyb, int x0, const R2LBnConsts& bc, float* gub = nullptr, float* gvb = nullptr) {
   constexpr int PY = K & 1;
   const int H = a.H;
   // ---- the blur's window: rows outside the image are zero; the forward takes the weight sets with the mirror padding
@@ -328,6 +329,19 @@ R2L_HD void r2l_bp_step(const R2LBwd1Args& a, R2LBpState& st, R2LBpAcc& A, const
     s4.z = gy2[1][0];
     s4.w = gy2[1][1];
     *(r2l_f4*)(gyb + (unsigned)y * (unsigned)a.W + (unsigned)x0) = s4;
+    if (GUV) {
+      r2l_f4 u4, v4;
+      u4.x = gu[0][0];
+      u4.y = gu[0][1];
+      u4.z = gu[1][0];
+      u4.w = gu[1][1];
+      v4.x = gv[0][0];
+      v4.y = gv[0][1];
+      v4.z = gv[1][0];
+      v4.w = gv[1][1];
+      *(r2l_f4*)(gub + (unsigned)y * (unsigned)a.W + (unsigned)x0) = u4;
+      *(r2l_f4*)(gvb + (unsigned)y * (unsigned)a.W + (unsigned)x0) = v4;
+    }
   }
   // ---- folded chroma stencils of this row's parity ----------------------------------------------------------------------
   const float* rows[3] = {vu, vm, vl};
@@ -409,8 +423,11 @@ R2L_BLOCKFN void r2l_bp_block_reduce(float* lds, int tid, float* partial, int sl
   }
 }
 
-template <bool U16, bool EPI>
-R2L_BLOCKFN void r2l_bwd1_plane_block(const R2LBwd1Args& a, int bid, int nblk, float* lds) {
+// GUV (float32 frames, no epilogue: r2l_bwd1_plane_guv_block): also the chroma gradient planes gU, gV -- guv[0 .. B H W) and
+// guv[B H W .. 2 B H W) -- for the d/d raw pass
+template <bool U16, bool EPI, bool GUV = false>
+R2L_BLOCKFN void r2l_bwd1_plane_block(const R2LBwd1Args& a, int bid, int nblk, float* lds, float* guv = nullptr) {
+  static_assert(!GUV || (!U16 && !EPI), "the chroma gradient planes are for float32 frames without an epilogue");
   constexpr int NWV = R2L_BP_NWV, NT = R2L_BP_NT;
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   R2LFoldedRef F = R2L_FOLDED_REF(a.F);
@@ -458,6 +475,8 @@ R2L_BLOCKFN void r2l_bwd1_plane_block(const R2LBwd1Args& a, int bid, int nblk, f
     const float* ypimg = a.yp + img;
     const float* gimg = a.gout + (size_t)b * 3 * plane;
     float* gyb = a.gypp + img;
+    float* gub = GUV ? guv + img : nullptr;
+    float* gvb = GUV ? guv + (size_t)a.B * plane + img : nullptr;
     R2LBpState st;
     R2LFsStage pf[PF];   // raw row q + 1
     R2LFaStage pfy[PF];  // Y' row q + 2
@@ -489,7 +508,7 @@ R2L_BLOCKFN void r2l_bwd1_plane_block(const R2LBwd1Args& a, int bid, int nblk, f
     const R2LBpStage g_ = pfg[(K) % PFG];                                                               \
     r2l_bp_fetch_g<EPI>(gimg, plane, q + PFG, a.H, a.W, x0, a.ep, pfg[(K) % PFG]);                      \
     if (K) r2l_bp_swap(A, bank); /* the bank of this row's parity into the registers */                 \
-    if (r2l_opaque_true()) r2l_bp_step<K>(a, st, A, g_, q, in_w && q < y1, gyb, x0, bc);                \
+    if (r2l_opaque_true()) r2l_bp_step<K, GUV>(a, st, A, g_, q, in_w && q < y1, gyb, x0, bc, gub, gvb); \
   }
       R2L_BP_STEP(0)
       R2L_BP_STEP(1)
@@ -1323,6 +1342,188 @@ R2L_BLOCKFN void r2l_bwd2_sums_block(const R2LBwd2Args& a, int bid, int nblk_lau
     r2l_unfold_from_lds<NT, true>(sums, tg, pl, a.grad_params);
     R2L_TAILST(27);
   }
+}
+
+// ================================================================================================
+// d/d raw (r2l_isp_step_bwd_raw): one gather pass behind kernel B2, over the planes the backward leaves anyway -- HP (the
+// blur's adjoint, dL/dY') and the chroma gradients gU, gV that the GUV form of kernel B1 stores:
+//   gY(q) = sum_t sharp[t] HP(q - t)                   (the adjoint of the zero-padded sharpen; HP is zero outside)
+//   D(r)  = sum_k sum_t A_k[parity(r - t)][t] g_k(r - t)     k = Y, U, V; A = the folded stencils (R2LFolded::AY2 ..)
+//   grad_raw(q) = sum of D(r) over the positions r of the padded frame that the debayer's reflect padding maps to q:
+//     q itself; for row 1 also row -1, for row H-2 also row H; columns likewise, corners both
+// An output row y has row parity K & 1, so the parity of its source row y - 1 + i and the tap (2 - i, 2 - j) of window
+// column j are known at compile time: the weights are scalar operands of the existing [k][row parity][tap][column parity]
+// block read transposed; the pair (even, odd output column) takes the column parities (0, 1) for the middle column and
+// (1, 0) for its neighbours.  The mirror rows -1 / H are one more window row's products with the other tap row, behind a
+// uniform branch on rows 1 and H-2; the mirror columns -1 / W are one extra pair per lane, (D(y, -1), D(y, W)) from the
+// lane's own first / last column, added to its columns 1 / 2 where the lane sits at the image's left / right edge.
+// A wavefront owns (image, band of rows, 256-column strip) and keeps three-row windows of HP (8 wide), gY, gU and gV
+// (6 wide, zero outside the image) in registers; neighbour columns are DPP lane shifts, the strip's first / last lane
+// load its own.  No LDS, no atomics: deterministic.  Traffic 12 B/px in (HP, gU, gV) + 4 B/px out, plus halo rows.
+struct R2LRawGradArgs {
+  const R2LFolded* F;
+  const float* hp;   // (B,H,W) dL/dY' (kernel B2's plane)
+  const float* guv;  // gU (B,H,W), then gV (B,H,W): r2l_bwd1_plane_guv_block
+  float* grad_raw;   // (B,H,W)
+  int B, H, W;
+  int band_h;        // rows per work item (a multiple of 6)
+};
+// one window row (columns x0-1 .. x0+4) of g_k against tap row tr of the row parity's table w = A_k[row parity]:
+// the lane's two output pairs, and (D(., -1), D(., W)) from the row's columns x0 (even) and x0+3 (odd)
+template <class WT>
+R2L_HD void r2l_br_row(r2l_p2 o[2], r2l_p2& e, const float row[6], WT w /* [9][2] */, int tr) {
+  r2l_p2 x[3][2];
+  r2l_row_pairs(row, x);
+  R2L_PRAGMA_UNROLL
+  for (int j = 0; j < 3; ++j) {
+    const int t = tr * 3 + 2 - j;  // source column x + j - 1 -> tap column 2 - j
+    const r2l_p2 wp = (j == 1) ? r2l_mk2(w[t][0], w[t][1]) : r2l_mk2(w[t][1], w[t][0]);
+    R2L_PRAGMA_UNROLL
+    for (int p = 0; p < 2; ++p) o[p] = r2l_pfma(wp, x[j][p], o[p]);
+  }
+  e = r2l_pfma(r2l_mk2(w[tr * 3][0], w[tr * 3 + 2][1]), r2l_mk2(row[1], row[4]), e);
+}
+struct R2LBrState {
+  float hp[3][8];  // HP rows (slot = row mod 3), columns x0-2 .. x0+5, zero outside the image
+  float g[3][3][6];  // [k][slot] gY, gU, gV rows, columns x0-1 .. x0+4, zero outside the image
+};
+// gY of row r = q + 1 of step K (into slot K + 1) from HP rows r-1, r, r+1 = slots K, K+1, K+2
+template <int K>
+R2L_HD void r2l_br_gy(const R2LRawGradArgs& a, R2LBrState& st, int r, bool le, bool re) {
+  R2LFoldedRef F = R2L_FOLDED_REF(r2l_opaque_after(a.F, st.hp[(K + 2) % 3][3]));
+  r2l_p2 gy[3];
+  gy[0] = gy[1] = gy[2] = r2l_splat2(0.f);
+  R2L_PRAGMA_UNROLL
+  for (int i = 0; i < 3; ++i) {
+    const float* h = st.hp[(K + 2 - i) % 3];  // HP(r - (i - 1))
+    R2L_PRAGMA_UNROLL
+    for (int j = 0; j < 3; ++j) {
+      const r2l_p2 w = r2l_splat2(F.sharp[i * 3 + j]);
+      R2L_PRAGMA_UNROLL
+      for (int P = 0; P < 3; ++P) gy[P] = r2l_pfma(w, r2l_mk2(h[2 * P + 2 - j], h[2 * P + 3 - j]), gy[P]);
+    }
+  }
+  const bool rin = (unsigned)r < (unsigned)a.H;
+  float* o = st.g[0][(K + 1) % 3];
+  o[0] = (rin && !le) ? gy[0][0] : 0.f;
+  o[1] = rin ? gy[0][1] : 0.f;
+  o[2] = rin ? gy[1][0] : 0.f;
+  o[3] = rin ? gy[1][1] : 0.f;
+  o[4] = rin ? gy[2][0] : 0.f;
+  o[5] = (rin && !re) ? gy[2][1] : 0.f;
+}
+// grad_raw of row y (K = y mod 6): g windows y-1, y, y+1 = slots K+2, K, K+1
+template <int K>
+R2L_HD void r2l_br_out(const R2LRawGradArgs& a, const R2LBrState& st, int y, bool le, bool re, bool store_ok, float* ob,
+                       int x0) {
+  constexpr int PY = K & 1;
+  const int H = a.H;
+  r2l_p2 o[2], e;
+  o[0] = o[1] = e = r2l_splat2(0.f);
+  R2LFoldedRef F = R2L_FOLDED_REF(r2l_opaque_after(a.F, st.g[0][(K + 1) % 3][2]));
+  R2L_PRAGMA_UNROLL
+  for (int i = 0; i < 3; ++i) {
+    const int rp = (PY + i + 1) & 1;  // parity of the source row y - 1 + i
+    r2l_br_row(o, e, st.g[0][(K + 2 + i) % 3], F.AY2[rp], 2 - i);
+    r2l_br_row(o, e, st.g[1][(K + 2 + i) % 3], F.AU2[rp], 2 - i);
+    r2l_br_row(o, e, st.g[2][(K + 2 + i) % 3], F.AV2[rp], 2 - i);
+  }
+  if (y == 1 || y == H - 2) {  // uniform: row -1 (mirror image of row 1) sees source row 0, row H sees row H-1
+    R2LFoldedRef Fm = R2L_FOLDED_REF(r2l_opaque_after(a.F, o[1][1]));
+    if (y == 1) {  // window row 0 (source row 0, parity PY ^ 1) through tap row 0
+      r2l_br_row(o, e, st.g[0][(K + 2) % 3], Fm.AY2[PY ^ 1], 0);
+      r2l_br_row(o, e, st.g[1][(K + 2) % 3], Fm.AU2[PY ^ 1], 0);
+      r2l_br_row(o, e, st.g[2][(K + 2) % 3], Fm.AV2[PY ^ 1], 0);
+    }
+    if (y == H - 2) {  // window row 2 (source row H-1, parity PY ^ 1) through tap row 2
+      r2l_br_row(o, e, st.g[0][(K + 1) % 3], Fm.AY2[PY ^ 1], 2);
+      r2l_br_row(o, e, st.g[1][(K + 1) % 3], Fm.AU2[PY ^ 1], 2);
+      r2l_br_row(o, e, st.g[2][(K + 1) % 3], Fm.AV2[PY ^ 1], 2);
+    }
+  }
+  if (store_ok) {
+    r2l_f4 s4;
+    s4.x = o[0][0];
+    s4.y = o[0][1] + (le ? e[0] : 0.f);  // column 1 adds column -1
+    s4.z = o[1][0] + (re ? e[1] : 0.f);  // column W-2 adds column W
+    s4.w = o[1][1];
+    *(r2l_f4*)(ob + (unsigned)y * (unsigned)a.W + (unsigned)x0) = s4;
+  }
+}
+#ifndef R2L_BR_PF
+#define R2L_BR_PF 2
+#endif
+#define R2L_BR_NWV 4
+R2L_BLOCKFN void r2l_bwd_raw_plane_block(const R2LRawGradArgs& a, int bid, int nblk, float* lds) {
+  (void)lds;
+  (void)nblk;
+  constexpr int NWV = R2L_BR_NWV;
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int nstrip = (a.W + 255) >> 8;
+  const unsigned plane = (unsigned)a.H * (unsigned)a.W;
+  const int band_h = a.band_h, nband = (a.H + band_h - 1) / band_h, nitems = a.B * nband * nstrip;
+  const int item = bid * NWV + wave;  // one item per wavefront
+  if (item >= nitems) return;
+  const int strip = item % nstrip, ib = item / nstrip;
+  const int band = ib % nband, b = ib / nband;
+  const int xs = strip * 256 + 4 * lane;
+  const bool in_w = xs < a.W;
+  const int x0 = in_w ? xs : a.W - 4;
+  const bool le = x0 == 0, re = x0 + 4 >= a.W;
+  const int y0 = band * band_h;  // a multiple of 6
+  const int y1 = (y0 + band_h < a.H) ? y0 + band_h : a.H;
+  const size_t img = (size_t)b * plane;
+  const float* hpimg = a.hp + img;
+  const float* guimg = a.guv + img;
+  const float* gvimg = a.guv + (size_t)a.B * plane + img;
+  float* ob = a.grad_raw + img;
+  R2LBrState st;
+  constexpr int PF = R2L_BR_PF;
+  static_assert(6 % PF == 0, "the prefetch ring is indexed by the unroll position");
+  R2LFaStage pfh[PF];   // HP row q + 2
+  R2LSumStage pfu[PF];  // gU row q + 1
+  R2LSumStage pfv[PF];  // gV row q + 1
+  R2L_PRAGMA_UNROLL
+  for (int i = 0; i < PF; ++i) {
+    r2l_fa_fetch(hpimg, y0 - 2 + i, a.H, a.W, x0, le, re, lane, pfh[(2 + i) % PF]);
+    r2l_b2s_fetch_hp(guimg, y0 - 3 + i, a.H, a.W, x0, le, re, lane, pfu[(2 + i) % PF]);
+    r2l_b2s_fetch_hp(gvimg, y0 - 3 + i, a.H, a.W, x0, le, re, lane, pfv[(2 + i) % PF]);
+  }
+  // step q: HP(q + 2), gU(q + 1), gV(q + 1) arrive; gY(q + 1); grad_raw(q).  Warm-up: q = y0-4 .. y0-1 (K = 2 .. 5), the last
+  // two also form gY(y0 - 1), gY(y0)
+#define R2L_BR_LOAD_STEP(K, q)                                                                                \
+  r2l_hp_build(pfh[(K) % PF], (unsigned)((q) + 2) < (unsigned)a.H, le, re, st.hp[((K) + 2) % 3]);             \
+  r2l_b2s_build_hp(pfu[(K) % PF], (unsigned)((q) + 1) < (unsigned)a.H, le, re, st.g[1][((K) + 1) % 3]);       \
+  r2l_b2s_build_hp(pfv[(K) % PF], (unsigned)((q) + 1) < (unsigned)a.H, le, re, st.g[2][((K) + 1) % 3]);       \
+  r2l_fa_fetch(hpimg, (q) + 2 + PF, a.H, a.W, x0, le, re, lane, pfh[(K) % PF]);                               \
+  r2l_b2s_fetch_hp(guimg, (q) + 1 + PF, a.H, a.W, x0, le, re, lane, pfu[(K) % PF]);                           \
+  r2l_b2s_fetch_hp(gvimg, (q) + 1 + PF, a.H, a.W, x0, le, re, lane, pfv[(K) % PF]);
+  R2L_BR_LOAD_STEP(2, y0 - 4)
+  R2L_BR_LOAD_STEP(3, y0 - 3)
+  R2L_BR_LOAD_STEP(4, y0 - 2)
+  if (r2l_opaque_true()) r2l_br_gy<4>(a, st, y0 - 1, le, re);
+  R2L_BR_LOAD_STEP(5, y0 - 1)
+  if (r2l_opaque_true()) r2l_br_gy<5>(a, st, y0, le, re);
+  for (int qb = y0; qb < y1; qb += 6) {
+    R2L_PROGRESS_PRIO(qb - y0, y1 - y0);
+#define R2L_BR_STEP(K)                                                                                        \
+  {                                                                                                           \
+    const int q = qb + K;                                                                                     \
+    R2L_BR_LOAD_STEP(K, q)                                                                                    \
+    if (r2l_opaque_true()) {                                                                                  \
+      r2l_br_gy<K>(a, st, q + 1, le, re);                                                                     \
+      r2l_br_out<K>(a, st, q, le, re, in_w && q < y1, ob, x0);                                                \
+    }                                                                                                         \
+  }
+    R2L_BR_STEP(0)
+    R2L_BR_STEP(1)
+    R2L_BR_STEP(2)
+    R2L_BR_STEP(3)
+    R2L_BR_STEP(4)
+    R2L_BR_STEP(5)
+#undef R2L_BR_STEP
+  }
+#undef R2L_BR_LOAD_STEP
 }
 
 #endif  // !R2L_SERIAL

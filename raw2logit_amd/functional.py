@@ -324,6 +324,24 @@ def epilogue_supported(raw, module):
     """can the fused kernels write this module's output through an epilogue?  (no additive layer: its gradient is
     summed in the ISP's own layout; rotations by 90 degrees need square frames -- checked per draw)"""
     return module.additive_layer is None
+def _raw_grad_why(f32, W, has_additive, epi=False):
+    """why r2l_isp_step_bwd_raw cannot produce d/d raw for such a call, or None if it can"""
+    if epi:
+        return 'the fused ISP kernels do not produce d/d raw with an output epilogue'
+    if not f32:
+        return 'd/d raw on the fused kernels needs float32 frames'
+    if W % 4 or W > 2048:
+        return 'd/d raw on the fused kernels needs W % 4 == 0 and W <= 2048'
+    if has_additive:
+        return 'd/d raw on the fused kernels is not produced with an additive layer'
+    return None
+
+
+def raw_grad_supported(raw, module):
+    """can the fused kernels produce d/d raw for these frames (ParametrizedProcessing.fused_raw_grad)?"""
+    return _raw_grad_why(raw.dtype == torch.float32, raw.shape[-1], module.additive_layer is not None) is None
+
+
 _STEP_STATS, _STEP_MOMENTS, _STEP_BN_SUMS = 0, 1, 2
 _STEP_LAYOUT = {}
 
@@ -393,7 +411,7 @@ class _IspFused(torch.autograd.Function):
         mom = float(momentum) if momentum is not None else -1.0
         # a backward will follow: the forward keeps the sharpened luma plane for its first gradient kernel
         # (needs_input_grad is also set under torch.no_grad(); grad_mode is the caller's torch.is_grad_enabled())
-        keep = _STEP_KEEP_LUMA if (grad_mode and any(ctx.needs_input_grad[1:8])) else 0
+        keep = _STEP_KEEP_LUMA if (grad_mode and any(ctx.needs_input_grad[:8])) else 0
 
         def call(phase, gathered):
             lib.check(lib.r2l_isp_step_fwd(ptr(raw), int(denom is not None), denom or 1.0, table, ptr(additive),
@@ -420,30 +438,43 @@ class _IspFused(torch.autograd.Function):
         ctx.shapes = [tuple(p.shape) for p in params[:7]]
         ctx.save_for_backward(raw, additive, out)
         ctx.ws = ws
+        ctx.raw_why = _raw_grad_why(denom is None, W, additive is not None, bool(epi)) if ctx.needs_input_grad[0] else None
         return out
 
     @staticmethod
     def backward(ctx, gout):
         raw, additive, out = ctx.saved_tensors
-        if ctx.needs_input_grad[0]:
-            raise _lib.R2LError(
-                'the fused ISP kernels do not produce d/d raw; gradients w.r.t. the raw frames are '
-                'only defined on the staged path (track_stages=True)')
+        need_r = ctx.needs_input_grad[0]
+        if need_r and ctx.raw_why is not None:
+            raise _lib.R2LError(ctx.raw_why + '; gradients w.r.t. such raw frames are defined on the staged path '
+                                '(ParametrizedProcessing routes them there)')
         gout = _f32c(gout, 'grad_out')
         B, H, W = raw.shape
         lib, stream = _lib.library_for(raw)
         ws, nws = ctx.ws, ctx.ws.numel()
         need_p = any(ctx.needs_input_grad[1:8])
         need_a = ctx.has_additive and ctx.needs_input_grad[10]
-        gp = torch.empty(_lib.R2L_P_NTRAIN, dtype=torch.float32, device=raw.device) if need_p else None
+        # (d/d raw runs behind the parameter-gradient kernels: they get a buffer even when no parameter needs its gradient)
+        gp = torch.empty(_lib.R2L_P_NTRAIN, dtype=torch.float32, device=raw.device) if (need_p or need_r) else None
         gadd = torch.empty_like(additive) if need_a else None
         denom = ctx.denom
+        graw = scratch = None
+        if need_r:
+            graw = torch.empty((B, H, W), dtype=torch.float32, device=raw.device)
+            nscr = lib.r2l_isp_raw_grad_scratch_bytes(B, H, W)
+            scratch = torch.empty(nscr, dtype=torch.uint8, device=raw.device)
 
         def call(phase, gathered):
+            if need_r:
+                lib.check(lib.r2l_isp_step_bwd_raw(ptr(raw), 0, 1.0, ptr(additive), ptr(gout), ptr(out), ptr(gp),
+                                                   ptr(gadd), ctx.bn_mode, ptr(ws), nws, B, H, W, ctx.nranks,
+                                                   phase | ctx.keep, ptr(gathered), stream, ptr(graw), ptr(scratch),
+                                                   nscr), 'r2l_isp_step_bwd_raw')
+                return
             lib.check(lib.r2l_isp_step_bwd(ptr(raw), int(denom is not None), denom or 1.0, ptr(additive), ptr(gout),
                                            ptr(out), ptr(gp), ptr(gadd), ctx.bn_mode, ptr(ws), nws, B, H, W,
                                            ctx.nranks, phase | ctx.keep, ptr(gathered), stream), 'r2l_isp_step_bwd')
-        if need_p or need_a:
+        if need_p or need_a or need_r:
             if not ctx.split:
                 call(_STEP_ALL, None)
             else:
@@ -456,7 +487,7 @@ class _IspFused(torch.autograd.Function):
             for i, ((_, off, n), shape) in enumerate(zip(PARAM_LAYOUT, ctx.shapes)):
                 if ctx.needs_input_grad[1 + i]:
                     grads[i] = gp[off:off + n].view(shape)
-        return (None, *grads, None, None, gadd, None, None, None, None, None, None, None, None)
+        return (graw, *grads, None, None, gadd, None, None, None, None, None, None, None, None)
 
 
 def isp_fused(raw, module, bn_mode=BN_NONE, group=None, epilogue=None):

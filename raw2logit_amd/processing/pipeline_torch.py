@@ -216,10 +216,14 @@ class ParametrizedProcessing(nn.Module):
     uint16 / int16 tensors (the sensor's 16-bit containers) are divided by 2**raw_bits - 1 inside the kernels,
     bit-identically to the host-side normalisation of the reference's datasets (dataset.py:86-87).
     ``supports_output_epilogue`` -- this class pops the one-shot `_epilogue` an augmentation armed (ComposeState.arm)
-    in its forward; processors without the attribute are never armed."""
+    in its forward; processors without the attribute are never armed.  ``fused_raw_grad`` (opt-in, default False) --
+    frames that require grad take the fused kernels instead of the stage-by-stage ones when ``track_stages`` is False and
+    the kernels can produce d/d raw for them (float32 frames, W % 4 == 0, W <= 2048, no additive layer); an armed output
+    epilogue then runs as the separate permutation kernel behind them."""
 
     raw_bits = 16
     supports_output_epilogue = True
+    fused_raw_grad = False
 
     def __init__(self, camera_parameters=None, track_stages=False, batch_norm_output=True):
         super().__init__()
@@ -278,16 +282,23 @@ class ParametrizedProcessing(nn.Module):
         d['stages'] = {}
         d['buffer'] = {}
 
-        # The fused kernels keep every intermediate in LDS / registers: they neither materialise the stage
-        # tensors nor produce d/d raw.  Whenever a caller can observe either (track_stages=True, or frames
-        # that require grad as in model.py:228), the stage-by-stage kernels run instead and fill
+        # The fused kernels keep every intermediate in LDS / registers: they do not materialise the stage tensors,
+        # and by default they do not produce d/d raw.  Whenever a caller can observe either (track_stages=True, or
+        # frames that require grad as in model.py:228), the stage-by-stage kernels run instead and fill
         # ``self.stages`` exactly like the reference (:183-214).
         # a one-shot output epilogue armed by the augmentation drop-in (ComposeState.arm): the flips / rot90 of
         # utils/augmentation.py:70-74 (applied to this module's output at model.py:79-81) leave the fused kernels as part
         # of their output stores; on the staged path, or where the kernels cannot take it, the moves run as the separate
         # permutation kernel right here -- either way the caller gets the augmented batch
         epilogue = d.pop('_epilogue', None)
-        if self.track_stages or (raw.requires_grad and torch.is_grad_enabled()):
+        # `fused_raw_grad = True` (opt-in): frames that require grad take the fused kernels too where they can produce
+        # d/d raw (float32 frames, W % 4 == 0, W <= 2048, no additive layer); the epilogue then runs after them
+        needs_raw_grad = raw.requires_grad and torch.is_grad_enabled()
+        fused_raw = needs_raw_grad and not self.track_stages and self.fused_raw_grad and F_.raw_grad_supported(raw, self)
+        if fused_raw:
+            rgb = self._fused_forward(raw)
+            d['stages'] = _LazyStages(self, raw)
+        elif self.track_stages or needs_raw_grad:
             from ..staged import staged_forward
             rgb = staged_forward(self, raw)
         else:
