@@ -223,6 +223,39 @@ int r2l_isp_step_bwd_raw(const void *raw, int raw_u16, float denom, const float 
                          const double *gathered_sums, void *stream, float *grad_raw, void *raw_grad_scratch,
                          size_t raw_grad_scratch_bytes);
 
+/* r2l_isp_step_bwd_select = r2l_isp_step_bwd_raw for a SUBSET of the gradients: grad_mask has one R2L_GRAD_* bit per gradient
+ * the caller wants (autograd's needs_input_grad, kept across the C boundary), and masks made of R2L_GRAD_GAMMA, R2L_GRAD_BLUR and
+ * R2L_GRAD_RAW only -- a frozen processor under frames that require grad, adversarial training of one parameter -- run reduced
+ * passes instead of the whole backward:
+ *   RAW            kernel B1 as a pure map (dL/dY'', gU, gV; no sums), the blur's adjoint, the d/d raw pass
+ *   GAMMA          kernel B1's pointwise part with the gamma sum alone: one launch
+ *   BLUR [+ GAMMA] kernel B1 writing dL/dY'' [+ the gamma sum], then the 25 blur-weight sums
+ *   RAW + GAMMA | BLUR   the RAW route with those sums added
+ * On such a route the elements of grad_params that belong to gradients NOT in the mask are written as 0.0f (not computed).
+ * grad_raw must be non-NULL exactly when R2L_GRAD_RAW is set; then the preconditions, error codes and texts of
+ * r2l_isp_step_bwd_raw apply.  Every other mask -- any of BLACK_LEVEL, WHITE_BALANCE, CCM, DEBAYER, SHARPEN (their sums need the
+ * whole chain) -- and every call the reduced passes do not serve (an additive layer, W % 4 != 0 or W > 2048, no
+ * R2L_STEP_KEEP_LUMA, batches the tile kernels take: < 4 Mi px without RAW, the serial emulation) runs exactly the code path of
+ * r2l_isp_step_bwd / r2l_isp_step_bwd_raw and fills all of grad_params.  Phases, several ranks and the BatchNorm backward sums:
+ * as r2l_isp_step_bwd (the sums are needed by every route and are not part of the selection).  Deterministic: no atomics; the
+ * sums go through the same fixed-order reductions as the full backward's.
+ * r2l_isp_step_bwd_select_passes: the passes (R2L_SELECT_* bits) such a call runs behind the BatchNorm sums, R2L_SELECT_FULL = the
+ * whole backward.  `phase` as given to the call (R2L_STEP_KEEP_LUMA, R2L_STEP_EPI_*). */
+enum { R2L_GRAD_BLACK_LEVEL = 1, R2L_GRAD_WHITE_BALANCE = 2, R2L_GRAD_CCM = 4, R2L_GRAD_GAMMA = 8, R2L_GRAD_DEBAYER = 16,
+       R2L_GRAD_SHARPEN = 32, R2L_GRAD_BLUR = 64, R2L_GRAD_RAW = 128, R2L_GRAD_ALL_PARAMS = 127 };
+enum { R2L_SELECT_FULL = 0,
+       R2L_SELECT_B1 = 1,      /* a reduced form of kernel B1's plane pass */
+       R2L_SELECT_BLUR = 2,    /* the blur-weight sums (dL/dY'' + Y') */
+       R2L_SELECT_BLUR_HP = 4, /* the blur-weight sums and the blur's adjoint HP in one pass */
+       R2L_SELECT_HP = 8,      /* the blur's adjoint HP alone */
+       R2L_SELECT_RAW = 16     /* HP + gU + gV -> grad_raw */ };
+int r2l_isp_step_bwd_select_passes(unsigned grad_mask, int raw_u16, int has_additive, int B, int H, int W, int phase);
+int r2l_isp_step_bwd_select(const void *raw, int raw_u16, float denom, const float *additive, const float *grad_out,
+                            const float *out, float *grad_params, float *grad_additive, int bn_mode, void *workspace,
+                            size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                            const double *gathered_sums, void *stream, float *grad_raw, void *raw_grad_scratch,
+                            size_t raw_grad_scratch_bytes, unsigned grad_mask);
+
 /* ---- static pipeline, numpy semantics (processing(), processing/pipeline_numpy.py:70-141, batched):
  * remove_blacklv (:152-158) -> demosaicing_CFA_Bayer_{bilinear,Malvar2004} (:92-95) -> wb (:161-162) ->
  * CCM (:165-167) -> [sharpening_filter (:180-191) | unsharp_masking (:170-177)] -> [gaussian_denoising (:203-209) | median_denoising

@@ -75,6 +75,12 @@ _SIGNATURES = {
                                             ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, _c_float_p, ctypes.c_void_p,
                                             ctypes.c_size_t]),
+    'r2l_isp_step_bwd_select_passes': (ctypes.c_int, [ctypes.c_uint] + [ctypes.c_int] * 6),
+    'r2l_isp_step_bwd_select': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, _c_float_p, _c_float_p,
+                                               _c_float_p, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_void_p,
+                                               ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, _c_float_p, ctypes.c_void_p,
+                                               ctypes.c_size_t, ctypes.c_uint]),
     'r2l_additive_bwd': (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p,
                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     'r2l_isp_fwd_u16': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, _c_float_p, _c_float_p, _c_float_p,

@@ -292,6 +292,44 @@ R2L_BLOCKFN void r2l_bwd1_plane_guv_block(const R2LBwd1GuvArgs& a, int bid, int 
 R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane_guv, R2LBwd1GuvArgs, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2, r2l_bwd1_plane_guv_block)
 R2L_KERNEL_NT_LDS(r2l_launch_bwd1_blur, R2LBwd1Args, R2L_BP_NT, R2L_BP_RED_FLOATS, 3, r2l_bwd1_blur_block)
 R2L_KERNEL_NT_LDS(r2l_launch_bwd1_blur_hp, R2LBwd1Args, R2L_BP_NT, R2L_BP_RED_FLOATS, R2L_HB_OCC, r2l_bwd1_blur_hp_block)
+// the reduced forms r2l_isp_step_bwd_select routes to (R2L_BPS_*: what each keeps).  Without the 38 stencil accumulator pairs
+// and with one row of raw / Y' in flight instead of two the pass fits three wavefronts per SIMD (133 .. 164 VGPRs, no scratch)
+// -- except the pure map with the gU / gV stores: hipcc keeps ~250 folded weights live in scalar registers there and spills
+// them into vector lanes (3 VGPRs over at one row in flight, 17 at two), so that one stays at two wavefronts (184 VGPRs)
+#define R2L_BPS_OCC 3
+#define R2L_BPS_OCC_RAW 2
+struct R2LBwd1SelArgs {
+  R2LBwd1Args b;
+  float* guv;  // gU, gV planes (the GUV forms), else null
+  R2LBpSelect s;
+};
+template <bool U16, bool EPI, bool GUV, int SEL, int PF = R2L_BPS_PF>
+R2L_BLOCKFN void r2l_bwd1_sel_block(const R2LBwd1SelArgs& a, int bid, int nblk, float* lds) {
+  r2l_bwd1_plane_block<U16, EPI, GUV, SEL, PF>(a.b, bid, nblk, lds, a.guv, &a.s);
+}
+R2L_BLOCKFN void r2l_bwd1_blur_fin_block(const R2LBwd1SelArgs& a, int bid, int nblk, float* lds) {
+  r2l_bwd1_blur_block<true>(a.b, bid, nblk, lds, &a.s);
+}
+R2L_BLOCKFN void r2l_bwd1_blur_hp_fin_block(const R2LBwd1SelArgs& a, int bid, int nblk, float* lds) {
+  r2l_bwd1_blur_hp_block<true>(a.b, bid, nblk, lds, &a.s);
+}
+// d/d raw alone: a pure map raw + Y' + grad_out -> dL/dY'', gU, gV (no accumulator, no LDS, no tail); ... with the gamma sum
+R2L_KERNEL_NT_LDS(r2l_launch_bwd1_sel_raw, R2LBwd1SelArgs, R2L_BP_NT, 4, R2L_BPS_OCC_RAW,
+                  r2l_bwd1_sel_block<false, false, true, R2L_BPS_GYPP, R2L_BP_PF>)
+R2L_KERNEL_NT_LDS(r2l_launch_bwd1_sel_raw_gamma, R2LBwd1SelArgs, R2L_BP_NT, R2L_BPS_LDS_FLOATS, R2L_BPS_OCC,
+                  r2l_bwd1_sel_block<false, false, true, R2L_BPS_GYPP | R2L_BPS_GAMMA>)
+// gamma alone (no plane written); dL/dY'' for the blur pass; both -- float32 / 16-bit frames, with / without the output epilogue
+#define R2L_BPS_KERNELS(name, LDSF, SEL)                                                                                       \
+  R2L_KERNEL_NT_LDS(name, R2LBwd1SelArgs, R2L_BP_NT, LDSF, R2L_BPS_OCC, r2l_bwd1_sel_block<false, false, false, SEL>)         \
+  R2L_KERNEL_NT_LDS(name##_u16, R2LBwd1SelArgs, R2L_BP_NT, LDSF, R2L_BPS_OCC, r2l_bwd1_sel_block<true, false, false, SEL>)    \
+  R2L_KERNEL_NT_LDS(name##_epi, R2LBwd1SelArgs, R2L_BP_NT, LDSF, R2L_BPS_OCC, r2l_bwd1_sel_block<false, true, false, SEL>)    \
+  R2L_KERNEL_NT_LDS(name##_epi_u16, R2LBwd1SelArgs, R2L_BP_NT, LDSF, R2L_BPS_OCC, r2l_bwd1_sel_block<true, true, false, SEL>)
+R2L_BPS_KERNELS(r2l_launch_bwd1_sel_gamma, R2L_BPS_LDS_FLOATS, R2L_BPS_GAMMA)
+R2L_BPS_KERNELS(r2l_launch_bwd1_sel_gypp, 4, R2L_BPS_GYPP)
+R2L_BPS_KERNELS(r2l_launch_bwd1_sel_gypp_gamma, R2L_BPS_LDS_FLOATS, R2L_BPS_GYPP | R2L_BPS_GAMMA)
+// the blur passes whose last workgroup finishes the 25 sums into the blur gradient
+R2L_KERNEL_NT_LDS(r2l_launch_bwd1_blur_fin, R2LBwd1SelArgs, R2L_BP_NT, R2L_BP_RED_FLOATS, 3, r2l_bwd1_blur_fin_block)
+R2L_KERNEL_NT_LDS(r2l_launch_bwd1_blur_hp_fin, R2LBwd1SelArgs, R2L_BP_NT, R2L_BP_RED_FLOATS, R2L_HB_OCC, r2l_bwd1_blur_hp_fin_block)
 // kernel B2 likewise: the blur's adjoint into a plane, then the sums + the final reduction and unfold
 R2L_KERNEL_NT_LDS(r2l_launch_bwd2_hp, R2LBwd2Args, R2L_BP_NT, 4, 4, r2l_bwd2_hp_block)
 R2L_KERNEL_NT_LDS(r2l_launch_bwd2_sums, R2LBwd2Args, R2L_B2S_NT, R2L_B2S_LDS_FLOATS, 3, r2l_bwd2_sums_block<false>)
@@ -1041,6 +1079,135 @@ static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float*
   return r2l_launch_unfold(ua, 1, stream);
 }
 
+// ---- the backward of a subset of the gradients (r2l_isp_step_bwd_select) ------------------------------------------------
+#define R2L_STEP_EPI_MASK (R2L_STEP_EPI_HFLIP | R2L_STEP_EPI_VFLIP | (3 << R2L_STEP_EPI_ROT_SHIFT))
+// the passes a mask takes (R2L_SELECT_*), R2L_SELECT_FULL = today's route: the sums of the black level, white balance, colour
+// matrix, debayer and sharpen gradients need the whole chain; the reduced passes exist as plane passes only
+static int r2l_select_route(unsigned mask, int raw_u16, bool has_additive, int B, int H, int W, int phase) {
+#ifdef R2L_SERIAL
+  (void)mask; (void)raw_u16; (void)has_additive; (void)B; (void)H; (void)W; (void)phase;
+  return R2L_SELECT_FULL;
+#else
+  const unsigned cheap = R2L_GRAD_GAMMA | R2L_GRAD_BLUR | R2L_GRAD_RAW;
+  if (!mask || (mask & ~cheap)) return R2L_SELECT_FULL;
+  static const float some_layer = 0.f;
+  if (!(phase & R2L_STEP_KEEP_LUMA) || !r2l_fwd_streams(has_additive ? &some_layer : nullptr, W)) return R2L_SELECT_FULL;
+  const size_t px = (size_t)B * H * W;
+  const bool raw = (mask & R2L_GRAD_RAW) != 0;
+  // (d/d raw: the plane passes at every size, as r2l_isp_step_bwd_raw; 16-bit frames and an output epilogue have no d/d raw --
+  // r2l_raw_grad_preconditions refuses them before a call gets here, the query reports the full route for them)
+  if (raw) {
+    if (raw_u16 || (phase & R2L_STEP_EPI_MASK)) return R2L_SELECT_FULL;
+  } else {  // (where r2l_isp_bwd_impl takes the plane passes)
+    if (!(r2l_env_int("R2L_BWD_PLANES", 0) || px >= ((size_t)4 << 20))) return R2L_SELECT_FULL;
+    if (r2l_env_int("R2L_BWD1_RECOMPUTE", 0) || r2l_env_int("R2L_BWD1_TILED", 0) || r2l_env_int("R2L_BWD2_TILED", 0))
+      return R2L_SELECT_FULL;
+  }
+  int passes = R2L_SELECT_B1;
+  if (mask & R2L_GRAD_BLUR) passes |= raw ? R2L_SELECT_BLUR_HP : R2L_SELECT_BLUR;
+  else if (raw) passes |= R2L_SELECT_HP;
+  if (raw) passes |= R2L_SELECT_RAW;
+  return passes;
+#endif
+}
+int r2l_isp_step_bwd_select_passes(unsigned grad_mask, int raw_u16, int has_additive, int B, int H, int W, int phase) {
+  if (B < 1 || H < 1 || W < 1) return R2L_SELECT_FULL;
+  return r2l_select_route(grad_mask, raw_u16, has_additive != 0, B, H, W, phase);
+}
+// the reduced passes of `passes` (!= R2L_SELECT_FULL: r2l_select_route has checked the frames); the workspace went through this
+// step's forward (folded weights, packed parameters, Y')
+static int r2l_isp_bwd_select(const R2LRaw& raw, const float* bn_mean_istd, const float* bn_bwd, const float* grad_out,
+                              float* grad_params, float* grad_raw, float* guv, const R2LWorkspace& ws, int B, int H, int W,
+                              const R2LEpi& ep, unsigned mask, int passes, void* stream) {
+#ifdef R2L_SERIAL
+  (void)raw; (void)bn_mean_istd; (void)bn_bwd; (void)grad_out; (void)grad_params; (void)grad_raw; (void)guv; (void)ws;
+  (void)B; (void)H; (void)W; (void)ep; (void)mask; (void)passes; (void)stream;
+  return r2l_fail(-3, "r2l_isp_step_bwd_select: internal: the serial emulation has no plane passes");
+#else
+  const bool gam = (mask & R2L_GRAD_GAMMA) != 0, blur = (mask & R2L_GRAD_BLUR) != 0;
+  const long nstrip = (W + 255) / 256;
+  auto band_rows = [&](long slots, const char* env) { return r2l_band_rows(B, H, W, slots, env); };
+  R2LBwd1SelArgs sa;
+  R2LBwd1Args& a1 = sa.b;
+  a1.raw = raw;
+  a1.additive = nullptr;
+  a1.F = ws.folded;
+  a1.bn = bn_mean_istd;
+  a1.bn_bwd = bn_bwd;
+  a1.gout = grad_out;
+  a1.gypp = ws.gypp;
+  a1.partial = ws.part_b1;
+  a1.B = B;
+  a1.H = H;
+  a1.W = W;
+  a1.debug = ws.debug + 8 * R2L_MAX_BLOCKS;
+  a1.yp = ws.yp;
+  a1.ep = ep.on ? ep : R2LEpi{0, 0, 0, 0};
+  a1.hp = ws.hp;
+  // persistent workgroups of 4 independent wavefronts, `occ` per CU
+  const int occ = (grad_raw && !gam) ? R2L_BPS_OCC_RAW : R2L_BPS_OCC;
+  a1.band_h = band_rows(256L * 4 * occ, "R2L_BP_BAND");
+  a1.band_hb = band_rows(256L * 4 * R2L_HB_OCC, "R2L_HB_BAND");
+  const long items = (long)B * nstrip * ((H + a1.band_h - 1) / a1.band_h);
+  long g = (items + R2L_BP_NWV - 1) / R2L_BP_NWV;
+  const long cap = r2l_env_int("R2L_GRID_BWD1", 256 * occ);
+  if (g > cap) g = cap;
+  if (g > R2L_MAX_BLOCKS) g = R2L_MAX_BLOCKS;
+  const int g1 = (int)g;
+  sa.guv = guv;
+  sa.s.params = ws.packed;
+  sa.s.grad_params = grad_params;
+  sa.s.blur_follows = blur;
+  // the gamma sum: slot R2L_B1_GGAM of kernel B1's partials, one slot through the shared tree
+  sa.s.tree = R2LTree{ws.part_b1 + (size_t)R2L_B1_GGAM * g1, nullptr, ws.gpartial, ws.counters, 1, 0};
+  int e;
+  if (grad_raw)
+    e = gam ? r2l_launch_bwd1_sel_raw_gamma(sa, g1, stream) : r2l_launch_bwd1_sel_raw(sa, g1, stream);
+  else {
+#define R2L_BPS_PICK(name)                                                                       \
+  (a1.ep.on ? (raw.u16 ? name##_epi_u16(sa, g1, stream) : name##_epi(sa, g1, stream))            \
+            : (raw.u16 ? name##_u16(sa, g1, stream) : name(sa, g1, stream)))
+    e = !blur ? R2L_BPS_PICK(r2l_launch_bwd1_sel_gamma)
+              : (gam ? R2L_BPS_PICK(r2l_launch_bwd1_sel_gypp_gamma) : R2L_BPS_PICK(r2l_launch_bwd1_sel_gypp));
+#undef R2L_BPS_PICK
+  }
+  if (e) return e;
+  if (blur) {  // the 25 sums (and HP, for d/d raw) on kernel B1's grid; its last workgroup writes the blur gradient
+    sa.s.tree = R2LTree{ws.part_b1, nullptr, ws.gpartial, ws.counters, R2L_B1_GAU, 0};
+    if (int eb = (passes & R2L_SELECT_BLUR_HP) ? r2l_launch_bwd1_blur_hp_fin(sa, g1, stream)
+                                               : r2l_launch_bwd1_blur_fin(sa, g1, stream))
+      return eb;
+  }
+  if (!grad_raw) return 0;
+  if (passes & R2L_SELECT_HP) {
+    R2LBwd2Args a2;
+    a2.nmain = 0;
+    a2.b1_partial = nullptr;
+    a2.b1_n = 0;
+    a2.b1_tot = nullptr;
+    a2.raw = raw;
+    a2.F = ws.folded;
+    a2.gypp = ws.gypp;
+    a2.partial = ws.part_b2;
+    a2.B = B;
+    a2.H = H;
+    a2.W = W;
+    a2.debug = ws.debug + 16 * R2L_MAX_BLOCKS;
+    a2.hp = ws.hp;
+    a2.band_h = band_rows(256L * 4 * 4, "R2L_HP_BAND");
+    a2.tree = R2LTree{nullptr, nullptr, nullptr, nullptr, 0, 0};
+    a2.params = nullptr;
+    a2.grad_params = nullptr;
+    const long hitems = (long)B * nstrip * ((H + a2.band_h - 1) / a2.band_h);
+    if (int eh = r2l_launch_bwd2_hp(a2, (int)((hitems + R2L_BP_NWV - 1) / R2L_BP_NWV), stream)) return eh;
+  }
+  R2LRawGradArgs ar{ws.folded, ws.hp, guv, grad_raw, B, H, W, band_rows(256L * 4 * R2L_BR_OCC, "R2L_BR_BAND")};
+  const long ritems = (long)B * nstrip * ((H + ar.band_h - 1) / ar.band_h);
+  if (ritems > (1L << 30)) return r2l_fail(-1, "r2l_isp_step_bwd_raw: batch too large");
+  return r2l_launch_bwd_raw_plane(ar, (int)((ritems + R2L_BR_NWV - 1) / R2L_BR_NWV), stream);
+#endif
+}
+
 int r2l_additive_bwd(const float* grad_out, const float* out, const float* bn_mean_istd,
                      const float* bn_bwd, float* grad_additive, int B, int H, int W, void* stream) {
   if (int e = r2l_check_dims(B, H, W)) return e;
@@ -1073,7 +1240,6 @@ static int r2l_epi_from_phase(int phase, int H, int W, R2LEpi& ep) {
   ep.sc = (r2 * Wo + c2) - ep.s0;
   return 0;
 }
-#define R2L_STEP_EPI_MASK (R2L_STEP_EPI_HFLIP | R2L_STEP_EPI_VFLIP | (3 << R2L_STEP_EPI_ROT_SHIFT))
 static R2LRaw r2l_raw_any(const void* raw, int raw_u16, float denom) {
   return raw_u16 ? r2l_raw_u16((const unsigned short*)raw, denom) : r2l_raw_f32((const float*)raw);
 }
@@ -1208,7 +1374,7 @@ static int r2l_isp_step_bwd_impl(const void* raw, int raw_u16, float denom, cons
                                  const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
                                  size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
                                  const double* gathered_sums, void* stream, float* grad_raw = nullptr,
-                                 float* guv = nullptr) {
+                                 float* guv = nullptr, unsigned select_mask = 0, int select_passes = R2L_SELECT_FULL) {
   const int keep = (phase & R2L_STEP_KEEP_LUMA) ? R2L_F_KEEP_LUMA : 0;
   R2LEpi ep;
   if (int e = r2l_check_dims(B, H, W)) return e;
@@ -1243,7 +1409,11 @@ static int r2l_isp_step_bwd_impl(const void* raw, int raw_u16, float denom, cons
     R2LBnBwdMeansArgs m{gathered_sums, nranks, ws.moments + 6, ws.bn_bwd};
     if (int e = r2l_launch_bn_bwd_means(m, 1, stream)) return e;
   }
-  if (grad_params) {
+  if (grad_params && select_passes != R2L_SELECT_FULL) {  // (r2l_isp_step_bwd_select: the passes of the asked gradients only)
+    if (int e = r2l_isp_bwd_select(rw, bn, bn_bwd, grad_out, grad_params, grad_raw, guv, ws, B, H, W, ep, select_mask,
+                                   select_passes, stream))
+      return e;
+  } else if (grad_params) {
     if (int e = r2l_isp_bwd_impl(rw, ws.packed, additive, bn, bn_bwd, grad_out, grad_params, grad_raw, workspace,
                                  workspace_bytes, B, H, W, R2L_F_FOLDED_VALID | keep, stream, &ep, guv))
       return e;
@@ -1262,16 +1432,13 @@ size_t r2l_isp_raw_grad_scratch_bytes(int B, int H, int W) {
   if (B < 1 || H < 1 || W < 1) return 0;
   return (size_t)2 * B * H * W * sizeof(float);  // gU, gV
 }
-int r2l_isp_step_bwd_raw(const void* raw, int raw_u16, float denom, const float* additive, const float* grad_out,
-                         const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
-                         size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
-                         const double* gathered_sums, void* stream, float* grad_raw, void* raw_grad_scratch,
-                         size_t raw_grad_scratch_bytes) {
-  if (!grad_raw)
-    return r2l_isp_step_bwd_impl(raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode,
-                                 workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream);
+// what d/d raw needs of a call (r2l_isp_step_bwd_raw, r2l_isp_step_bwd_select): 0, or the error
+static int r2l_raw_grad_preconditions(int raw_u16, const float* additive, const float* grad_params, const float* grad_raw,
+                                      const void* raw_grad_scratch, size_t raw_grad_scratch_bytes, int B, int H, int W,
+                                      int phase) {
 #ifdef R2L_SERIAL
-  (void)raw_grad_scratch; (void)raw_grad_scratch_bytes;
+  (void)raw_u16; (void)additive; (void)grad_params; (void)grad_raw; (void)raw_grad_scratch; (void)raw_grad_scratch_bytes;
+  (void)B; (void)H; (void)W; (void)phase;
   return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw needs the plane passes, which the serial emulation does not have");
 #else
   if (int e = r2l_check_dims(B, H, W)) return e;
@@ -1289,11 +1456,45 @@ int r2l_isp_step_bwd_raw(const void* raw, int raw_u16, float denom, const float*
     return r2l_fail(-2, "r2l_isp_step_bwd_raw: raw_grad_scratch too small (r2l_isp_raw_grad_scratch_bytes)");
   if ((uintptr_t)raw_grad_scratch % 16 || (uintptr_t)grad_raw % 16)
     return r2l_fail(-1, "r2l_isp_step_bwd_raw: grad_raw and raw_grad_scratch must be 16-byte aligned");
+  return 0;
+#endif
+}
+int r2l_isp_step_bwd_raw(const void* raw, int raw_u16, float denom, const float* additive, const float* grad_out,
+                         const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
+                         size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                         const double* gathered_sums, void* stream, float* grad_raw, void* raw_grad_scratch,
+                         size_t raw_grad_scratch_bytes) {
+  if (!grad_raw)
+    return r2l_isp_step_bwd_impl(raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode,
+                                 workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream);
+  if (int e = r2l_raw_grad_preconditions(raw_u16, additive, grad_params, grad_raw, raw_grad_scratch, raw_grad_scratch_bytes,
+                                         B, H, W, phase))
+    return e;
   // (phase A computes the BatchNorm sums only: the gradient kernels, and with them d/d raw, run in phase B / ALL)
   return r2l_isp_step_bwd_impl(raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode, workspace,
                                workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw,
                                (float*)raw_grad_scratch);
-#endif
+}
+int r2l_isp_step_bwd_select(const void* raw, int raw_u16, float denom, const float* additive, const float* grad_out,
+                            const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
+                            size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                            const double* gathered_sums, void* stream, float* grad_raw, void* raw_grad_scratch,
+                            size_t raw_grad_scratch_bytes, unsigned grad_mask) {
+  if (grad_mask & ~(unsigned)(R2L_GRAD_ALL_PARAMS | R2L_GRAD_RAW))
+    return r2l_fail(-1, "r2l_isp_step_bwd_select: unknown bits in grad_mask");
+  if ((grad_raw != nullptr) != ((grad_mask & R2L_GRAD_RAW) != 0))
+    return r2l_fail(-1, "r2l_isp_step_bwd_select: grad_raw goes with R2L_GRAD_RAW in grad_mask");
+  if (grad_mask && !grad_params) return r2l_fail(-1, "r2l_isp_step_bwd_select: a gradient is asked for but grad_params is null");
+  if (grad_raw)
+    if (int e = r2l_raw_grad_preconditions(raw_u16, additive, grad_params, grad_raw, raw_grad_scratch,
+                                           raw_grad_scratch_bytes, B, H, W, phase))
+      return e;
+  // a mask without a reduced route: exactly r2l_isp_step_bwd / r2l_isp_step_bwd_raw
+  const int passes = (B < 1 || H < 1 || W < 1) ? R2L_SELECT_FULL
+                                               : r2l_select_route(grad_mask, raw_u16, additive != nullptr, B, H, W, phase);
+  return r2l_isp_step_bwd_impl(raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode, workspace,
+                               workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw,
+                               (float*)raw_grad_scratch, grad_mask, passes);
 }
 
 static int r2l_raw2rgb_fwd_impl(const R2LRaw& raw, const float* black_level, float* out, int B, int H, int W,

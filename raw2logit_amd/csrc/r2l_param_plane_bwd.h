@@ -254,9 +254,15 @@ R2L_HD void r2l_bp_swap(R2LBpAcc& A, float* bank /* this lane's 40 floats, [chun
 #undef R2L_BP_SW
 }
 
+// What an instantiation of the pass keeps (compile-time; r2l_isp_step_bwd_select runs the reduced ones when only some gradients
+// are asked for).  Each kept part is the full kernel's per-lane arithmetic in the same order; a dropped part leaves no code.
+#define R2L_BPS_STENCIL 1  // the folded chroma-stencil / black-level sums: both parity banks, the LDS swap, their partials
+#define R2L_BPS_GAMMA 2    // the gamma sum
+#define R2L_BPS_GYPP 4     // the dL/dY'' store
+#define R2L_BPS_FULL (R2L_BPS_STENCIL | R2L_BPS_GAMMA | R2L_BPS_GYPP)
 // one output row y (K = y mod 6, row parity K & 1); the windows hold V(y-1 .. y+1) and Y'(y-2 .. y+2).  GUV: the chroma
 // gradients gU, gV of the row are stored too (planes gub, gvb: the input of r2l_bwd_raw_plane_block, d/d raw)
-template <int K, bool GUV = false>
+template <int K, bool GUV = false, int SEL = R2L_BPS_FULL>
 R2L_HD void r2l_bp_step(const R2LBwd1Args& a, R2LBpState& st, R2LBpAcc& A, const R2LBpStage& gs, int y, bool store_ok,
                         float* gyb, int x0, const R2LBnConsts& bc, float* gub = nullptr, float* gvb = nullptr) {
   constexpr int PY = K & 1;
@@ -311,7 +317,7 @@ R2L_HD void r2l_bp_step(const R2LBwd1Args& a, R2LBpState& st, R2LBpAcc& A, const
         grgb[k][p] = r2l_mk2((rgb[0] == xc[0]) ? gc[0] : 0.f, (rgb[1] == xc[1]) ? gc[1] : 0.f);  // clip backward
       }
     }
-    A.ggam = r2l_padd(A.ggam, ggam);
+    if (SEL & R2L_BPS_GAMMA) A.ggam = r2l_padd(A.ggam, ggam);
     R2L_PRAGMA_UNROLL
     for (int p = 0; p < 2; ++p) {
       gy2[p] = r2l_pfma(r2l_splat2(F.M2[6]), grgb[2][p],
@@ -323,12 +329,14 @@ R2L_HD void r2l_bp_step(const R2LBwd1Args& a, R2LBpState& st, R2LBpAcc& A, const
     }
   }
   if (store_ok) {
-    r2l_f4 s4;
-    s4.x = gy2[0][0];
-    s4.y = gy2[0][1];
-    s4.z = gy2[1][0];
-    s4.w = gy2[1][1];
-    *(r2l_f4*)(gyb + (unsigned)y * (unsigned)a.W + (unsigned)x0) = s4;
+    if (SEL & R2L_BPS_GYPP) {
+      r2l_f4 s4;
+      s4.x = gy2[0][0];
+      s4.y = gy2[0][1];
+      s4.z = gy2[1][0];
+      s4.w = gy2[1][1];
+      *(r2l_f4*)(gyb + (unsigned)y * (unsigned)a.W + (unsigned)x0) = s4;
+    }
     if (GUV) {
       r2l_f4 u4, v4;
       u4.x = gu[0][0];
@@ -343,6 +351,7 @@ R2L_HD void r2l_bp_step(const R2LBwd1Args& a, R2LBpState& st, R2LBpAcc& A, const
       *(r2l_f4*)(gvb + (unsigned)y * (unsigned)a.W + (unsigned)x0) = v4;
     }
   }
+  if (!(SEL & R2L_BPS_STENCIL)) return;
   // ---- folded chroma stencils of this row's parity ----------------------------------------------------------------------
   const float* rows[3] = {vu, vm, vl};
   R2L_PRAGMA_UNROLL
@@ -423,20 +432,36 @@ R2L_BLOCKFN void r2l_bp_block_reduce(float* lds, int tid, float* partial, int sl
   }
 }
 
+// The reduced routes' own tails (r2l_isp_step_bwd_select): no unfold, the kept sum IS the gradient up to the factor
+// r2l_unfold_one applies.  grad_params entries of gradients that were not asked for are written as 0; the blur-weight entries
+// belong to the blur pass behind kernel B1 when it runs (blur_follows).
+struct R2LBpSelect {
+  R2LTree tree;          // the kept slots' partials, the shared group partials and arrival counters (r2l_tree_finish)
+  const float* params;   // the packed parameters the forward saw
+  float* grad_params;    // [R2L_P_NTRAIN]
+  int blur_follows;
+};
+#define R2L_BPS_LDS_FLOATS 512  // reduction scratch of a reduced B1 with the gamma sum: one slot, then the tree's
 // GUV (float32 frames, no epilogue: r2l_bwd1_plane_guv_block): also the chroma gradient planes gU, gV -- guv[0 .. B H W) and
-// guv[B H W .. 2 B H W) -- for the d/d raw pass
-template <bool U16, bool EPI, bool GUV = false>
-R2L_BLOCKFN void r2l_bwd1_plane_block(const R2LBwd1Args& a, int bid, int nblk, float* lds, float* guv = nullptr) {
+// guv[B H W .. 2 B H W) -- for the d/d raw pass.  SEL: what the instantiation keeps (R2L_BPS_*); without R2L_BPS_STENCIL the
+// pass has no parity banks, no LDS swap, and -- without R2L_BPS_GAMMA either -- no reduction at all: a pure map.  PF_: rows of
+// raw / Y' in flight (the reduced forms that run three wavefronts per SIMD keep one: 10 registers less, R2L_BPS_PF)
+#define R2L_BPS_PF 1
+template <bool U16, bool EPI, bool GUV = false, int SEL = R2L_BPS_FULL, int PF_ = R2L_BP_PF>
+R2L_BLOCKFN void r2l_bwd1_plane_block(const R2LBwd1Args& a, int bid, int nblk, float* lds, float* guv = nullptr,
+                                      const R2LBpSelect* sel = nullptr) {
   static_assert(!GUV || (!U16 && !EPI), "the chroma gradient planes are for float32 frames without an epilogue");
   constexpr int NWV = R2L_BP_NWV, NT = R2L_BP_NT;
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   R2LFoldedRef F = R2L_FOLDED_REF(a.F);
-  float* bank = lds + (size_t)wave * 64 * R2L_BP_BANK + lane * 4;  // [chunk][lane][4]
-  R2L_PRAGMA_UNROLL
-  for (int c = 0; c < 10; ++c) {
-    r2l_f4 z;
-    z.x = z.y = z.z = z.w = 0.f;
-    *(r2l_f4*)(bank + c * 64 * 4) = z;
+  float* bank = (SEL & R2L_BPS_STENCIL) ? lds + (size_t)wave * 64 * R2L_BP_BANK + lane * 4 : lds;  // [chunk][lane][4]
+  if (SEL & R2L_BPS_STENCIL) {
+    R2L_PRAGMA_UNROLL
+    for (int c = 0; c < 10; ++c) {
+      r2l_f4 z;
+      z.x = z.y = z.z = z.w = 0.f;
+      *(r2l_f4*)(bank + c * 64 * 4) = z;
+    }
   }
   R2LBpAcc A;
   R2L_PRAGMA_UNROLL
@@ -458,7 +483,7 @@ R2L_BLOCKFN void r2l_bwd1_plane_block(const R2LBwd1Args& a, int bid, int nblk, f
   const int nstrip = (a.W + 255) >> 8;
   const unsigned plane = (unsigned)a.H * (unsigned)a.W;
   const int band_h = a.band_h, nband = (a.H + band_h - 1) / band_h, nitems = a.B * nband * nstrip;
-  constexpr int PF = R2L_BP_PF, PFG = R2L_BP_PFG;
+  constexpr int PF = PF_, PFG = R2L_BP_PFG;
   static_assert(6 % PF == 0 && 6 % PFG == 0, "the prefetch rings are indexed by the unroll position");
   // the registers hold the bank of EVEN rows between items (every band starts on an even row, at K = 0)
   R2L_PRAGMA_NOUNROLL
@@ -507,8 +532,8 @@ R2L_BLOCKFN void r2l_bwd1_plane_block(const R2LBwd1Args& a, int bid, int nblk, f
     R2L_BP_LOAD_STEP(K, q)                                                                              \
     const R2LBpStage g_ = pfg[(K) % PFG];                                                               \
     r2l_bp_fetch_g<EPI>(gimg, plane, q + PFG, a.H, a.W, x0, a.ep, pfg[(K) % PFG]);                      \
-    if (K) r2l_bp_swap(A, bank); /* the bank of this row's parity into the registers */                 \
-    if (r2l_opaque_true()) r2l_bp_step<K, GUV>(a, st, A, g_, q, in_w && q < y1, gyb, x0, bc, gub, gvb); \
+    if (K && (SEL & R2L_BPS_STENCIL)) r2l_bp_swap(A, bank); /* the bank of this row's parity into the registers */ \
+    if (r2l_opaque_true()) r2l_bp_step<K, GUV, SEL>(a, st, A, g_, q, in_w && q < y1, gyb, x0, bc, gub, gvb); \
   }
       R2L_BP_STEP(0)
       R2L_BP_STEP(1)
@@ -516,10 +541,32 @@ R2L_BLOCKFN void r2l_bwd1_plane_block(const R2LBwd1Args& a, int bid, int nblk, f
       R2L_BP_STEP(3)
       R2L_BP_STEP(4)
       R2L_BP_STEP(5)
-      r2l_bp_swap(A, bank);  // (K = 5 was an odd row)
+      if (SEL & R2L_BPS_STENCIL) r2l_bp_swap(A, bank);  // (K = 5 was an odd row)
 #undef R2L_BP_STEP
     }
 #undef R2L_BP_LOAD_STEP
+  }
+  if constexpr (!(SEL & R2L_BPS_STENCIL)) {
+    // ---- a reduced route: at most the gamma sum, through the same fixed-order LDS reduction, per-workgroup partial slot and
+    // arrival-counter tree as the full kernel's; the launch's last workgroup writes grad_params ----------------------------
+    const bool mine = tid < R2L_P_NTRAIN && !(sel->blur_follows && tid >= R2L_P_BLUR);
+    if constexpr ((SEL & R2L_BPS_GAMMA) != 0) {
+      r2l_bp_block_reduce<1, R2L_BP_NT, 1>(lds, tid, a.partial, R2L_B1_GGAM, bid, nblk,
+                                           [&](int) { return A.ggam[0] + A.ggam[1]; });
+      double* tot = (double*)(lds + 4);
+      if (!r2l_tree_finish<1, NT>(sel->tree, bid, nblk, lds, tot, (double*)(lds + 16), 16)) return;
+      if (mine) {
+        float g = 0.f;
+        if (tid == R2L_P_GAMMA) {  // (as r2l_unfold_one)
+          const double gamma = sel->params[R2L_P_GAMMA];
+          g = (float)(-tot[0] * R2L_LN2 / (gamma * gamma));
+        }
+        sel->grad_params[tid] = g;
+      }
+    } else {
+      if (bid == 0 && mine) sel->grad_params[tid] = 0.f;
+    }
+    return;
   }
   // ---- lanes -> one partial per slot and workgroup, fixed order (R2L_BLOCK_REDUCE_F for NT threads) ----------------------
   float E[R2L_BP_BANK], O[R2L_BP_BANK];
@@ -546,6 +593,13 @@ R2L_BLOCKFN void r2l_bwd1_plane_block(const R2LBwd1Args& a, int bid, int nblk, f
   // (not the blur-weight sums, slots < R2L_B1_GAU: the blur pass that runs behind this launch on the same grid writes them)
   r2l_bp_block_reduce<R2L_B1_NACC - R2L_B1_GAU, R2L_BP_NT, R2L_BP_ROWS>(
       lds, tid, a.partial, R2L_B1_GAU, bid, nblk, [&](int i) { return r2l_bp_slot(A, E, O, R2L_B1_GAU + i); });
+}
+// the blur-weight sums of a reduced route (r2l_isp_step_bwd_select): the 25 totals are the gradient (r2l_unfold_one casts them)
+template <int NT>
+R2L_BLOCKFN void r2l_bp_blur_finish(const R2LBpSelect& sel, int bid, int nblk, float* lds, int tid) {
+  double* tot = (double*)(lds + 4);
+  if (!r2l_tree_finish<R2L_B1_GAU, NT>(sel.tree, bid, nblk, lds, tot, (double*)(lds + 64), 16 * R2L_B1_GAU)) return;
+  if (tid < R2L_B1_GAU) sel.grad_params[R2L_P_BLUR + tid] = (float)tot[tid];
 }
 
 // ---- second pass: the 25 blur-weight sums  d/d gaussian_blur.weight[i][j] = sum_p gY''(p) * Y'_ext(p + (i-2, j-2)) from
@@ -602,7 +656,8 @@ R2L_HD void r2l_bb_step(const R2LBwd1Args& a, const float yp[6][8], r2l_p2 blur[
 #ifndef R2L_BB_PF
 #define R2L_BB_PF 2
 #endif
-R2L_BLOCKFN void r2l_bwd1_blur_block(const R2LBwd1Args& a, int bid, int nblk, float* lds) {
+template <bool FINISH = false>  // FINISH: the launch's last workgroup turns the 25 sums into the blur gradient (reduced routes)
+R2L_BLOCKFN void r2l_bwd1_blur_block(const R2LBwd1Args& a, int bid, int nblk, float* lds, const R2LBpSelect* sel = nullptr) {
   constexpr int NWV = R2L_BP_NWV;
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   r2l_p2 blur[25];
@@ -666,6 +721,7 @@ R2L_BLOCKFN void r2l_bwd1_blur_block(const R2LBwd1Args& a, int bid, int nblk, fl
 #undef R2L_BB_LOAD_STEP
   }
   r2l_bp_block_reduce<R2L_B1_GAU, R2L_BP_NT>(lds, tid, a.partial, 0, bid, nblk, [&](int i) { return blur[i][0] + blur[i][1]; });
+  if constexpr (FINISH) r2l_bp_blur_finish<R2L_BP_NT>(*sel, bid, nblk, lds, tid);
 }
 
 // ================================================================================================
@@ -920,7 +976,8 @@ R2L_HD void r2l_hb_step(const R2LBwd1Args& a, const float gw[6][8], r2l_p2 blur[
 #ifndef R2L_HB_OCC
 #define R2L_HB_OCC 2
 #endif
-R2L_BLOCKFN void r2l_bwd1_blur_hp_block(const R2LBwd1Args& a, int bid, int nblk, float* lds) {
+template <bool FINISH = false>
+R2L_BLOCKFN void r2l_bwd1_blur_hp_block(const R2LBwd1Args& a, int bid, int nblk, float* lds, const R2LBpSelect* sel = nullptr) {
   constexpr int NWV = R2L_BP_NWV;
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   r2l_p2 blur[25];
@@ -985,6 +1042,7 @@ R2L_BLOCKFN void r2l_bwd1_blur_hp_block(const R2LBwd1Args& a, int bid, int nblk,
 #undef R2L_BH_LOAD_STEP
   }
   r2l_bp_block_reduce<R2L_B1_GAU, R2L_BP_NT>(lds, tid, a.partial, 0, bid, nblk, [&](int i) { return blur[i][0] + blur[i][1]; });
+  if constexpr (FINISH) r2l_bp_blur_finish<R2L_BP_NT>(*sel, bid, nblk, lds, tid);
 }
 
 // ---- second pass of B2: HP + raw -> gY = sharpen^T(HP) (zero padding), the sums  d/d sharpening_filter.weight[t] =

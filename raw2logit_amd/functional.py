@@ -342,6 +342,17 @@ def raw_grad_supported(raw, module):
     return _raw_grad_why(raw.dtype == torch.float32, raw.shape[-1], module.additive_layer is not None) is None
 
 
+# one bit per gradient of r2l_isp_step_bwd_select (include/r2l_isp.h: R2L_GRAD_*), in the order of _IspFused.forward's inputs:
+# raw, black_level, white_balance, colour_correction, gamma_correct, debayer.weight, sharpening_filter.weight, gaussian_blur.weight
+GRAD_RAW = 128
+_GRAD_BITS = (GRAD_RAW, 1, 2, 4, 8, 16, 32, 64)
+
+
+def grad_mask(needs_input_grad):
+    """autograd's needs_input_grad[0:8] of _IspFused -> the grad_mask of r2l_isp_step_bwd_select"""
+    return sum(bit for bit, need in zip(_GRAD_BITS, needs_input_grad[:8]) if need)
+
+
 _STEP_STATS, _STEP_MOMENTS, _STEP_BN_SUMS = 0, 1, 2
 _STEP_LAYOUT = {}
 
@@ -364,11 +375,13 @@ class _IspFused(torch.autograd.Function):
     The workspace tensor carries the step's state (packed parameters as the forward saw them, folded weights,
     BatchNorm constants) from one to the other; backward hands each parameter a view of the single 132-float
     gradient the kernels produce.  With several ranks and train-mode BatchNorm each call splits in two around an
-    all-gather of 7 resp. 6 doubles (RCCL)."""
+    all-gather of 7 resp. 6 doubles (RCCL).  selective (ParametrizedProcessing.selective_backward): the backward hands
+    needs_input_grad to the library (r2l_isp_step_bwd_select), which runs reduced passes where only the gamma, blur or raw
+    gradients are asked for; parameters that did not ask get None either way."""
 
     @staticmethod
     def forward(ctx, raw, bl, wb, ccm, gamma, deb, sharp, blur, m1, m2, additive, bn_mode, bn_module, eps,
-                momentum, group, bits=16, grad_mode=True, epilogue=None):
+                momentum, group, bits=16, grad_mode=True, epilogue=None, selective=False):
         raw, denom = _raw_arg(raw, bits)
         params = (bl, wb, ccm, gamma, deb, sharp, blur, m1, m2)
         sizes = (4, 3, 9, 1, 81, 9, 25, 9, 9)
@@ -438,6 +451,7 @@ class _IspFused(torch.autograd.Function):
         ctx.shapes = [tuple(p.shape) for p in params[:7]]
         ctx.save_for_backward(raw, additive, out)
         ctx.ws = ws
+        ctx.selective = bool(selective)
         ctx.raw_why = _raw_grad_why(denom is None, W, additive is not None, bool(epi)) if ctx.needs_input_grad[0] else None
         return out
 
@@ -459,12 +473,21 @@ class _IspFused(torch.autograd.Function):
         gadd = torch.empty_like(additive) if need_a else None
         denom = ctx.denom
         graw = scratch = None
+        nscr = 0
         if need_r:
             graw = torch.empty((B, H, W), dtype=torch.float32, device=raw.device)
             nscr = lib.r2l_isp_raw_grad_scratch_bytes(B, H, W)
             scratch = torch.empty(nscr, dtype=torch.uint8, device=raw.device)
 
+        mask = grad_mask(ctx.needs_input_grad) if ctx.selective else 0
+
         def call(phase, gathered):
+            if mask:
+                lib.check(lib.r2l_isp_step_bwd_select(ptr(raw), int(denom is not None), denom or 1.0, ptr(additive), ptr(gout),
+                                                      ptr(out), ptr(gp), ptr(gadd), ctx.bn_mode, ptr(ws), nws, B, H, W,
+                                                      ctx.nranks, phase | ctx.keep, ptr(gathered), stream, ptr(graw),
+                                                      ptr(scratch), nscr, mask), 'r2l_isp_step_bwd_select')
+                return
             if need_r:
                 lib.check(lib.r2l_isp_step_bwd_raw(ptr(raw), 0, 1.0, ptr(additive), ptr(gout), ptr(out), ptr(gp),
                                                    ptr(gadd), ctx.bn_mode, ptr(ws), nws, B, H, W, ctx.nranks,
@@ -487,7 +510,7 @@ class _IspFused(torch.autograd.Function):
             for i, ((_, off, n), shape) in enumerate(zip(PARAM_LAYOUT, ctx.shapes)):
                 if ctx.needs_input_grad[1 + i]:
                     grads[i] = gp[off:off + n].view(shape)
-        return (graw, *grads, None, None, gadd, None, None, None, None, None, None, None, None)
+        return (graw, *grads, None, None, gadd, None, None, None, None, None, None, None, None, None)
 
 
 def isp_fused(raw, module, bn_mode=BN_NONE, group=None, epilogue=None):
@@ -499,7 +522,7 @@ def isp_fused(raw, module, bn_mode=BN_NONE, group=None, epilogue=None):
                            module.gaussian_blur.weight, module.M_RGB_2_YUV, module.M_YUV_2_RGB,
                            module.additive_layer, bn_mode, bn, bn.eps if bn is not None else 1e-5,
                            bn.momentum if bn is not None else None, group, getattr(module, 'raw_bits', 16),
-                           torch.is_grad_enabled(), epilogue)
+                           torch.is_grad_enabled(), epilogue, bool(getattr(module, 'selective_backward', False)))
 
 
 # --------------------------------------------------------------------------------------------------

@@ -219,11 +219,16 @@ class ParametrizedProcessing(nn.Module):
     in its forward; processors without the attribute are never armed.  ``fused_raw_grad`` (opt-in, default False) --
     frames that require grad take the fused kernels instead of the stage-by-stage ones when ``track_stages`` is False and
     the kernels can produce d/d raw for them (float32 frames, W % 4 == 0, W <= 2048, no additive layer); an armed output
-    epilogue then runs as the separate permutation kernel behind them."""
+    epilogue then runs as the separate permutation kernel behind them.  ``selective_backward`` (opt-in, default False) -- the
+    fused backward computes only the gradients autograd asks for (r2l_isp_step_bwd_select): with nothing but ``gamma_correct``
+    and / or ``gaussian_blur.weight`` trainable (train.py's --adv_parameters with one name), or a frozen processor under frames
+    that require grad (with ``fused_raw_grad``), reduced passes run instead of all 155 sums; any other set of trainable
+    parameters takes the full backward unchanged.  Parameters that do not require grad get no gradient either way."""
 
     raw_bits = 16
     supports_output_epilogue = True
     fused_raw_grad = False
+    selective_backward = False
 
     def __init__(self, camera_parameters=None, track_stages=False, batch_norm_output=True):
         super().__init__()
