@@ -63,16 +63,9 @@ static void r2l_ls_note(const char* name) {
     for (int b = 0; b < grid; ++b) __VA_ARGS__(a, b, grid, lds);             \
     return 0;                                                                \
   }
+#define R2L_KERNEL(name, ArgsT, blockfn, LDS_FLOATS) R2L_KERNEL_V(name, ArgsT, LDS_FLOATS, 1, blockfn)
 #define R2L_KERNEL_OCC(name, ArgsT, blockfn, LDS_FLOATS, W) R2L_KERNEL(name, ArgsT, blockfn, LDS_FLOATS)
 #define R2L_KERNEL_NT(name, ArgsT, blockfn, NT, W) R2L_KERNEL(name, ArgsT, blockfn, 4)
-#define R2L_KERNEL(name, ArgsT, blockfn, LDS_FLOATS)                         \
-  static int name(const ArgsT& a, int grid, void* stream) {                  \
-    (void)stream;                                                            \
-    std::vector<float> buf((size_t)(LDS_FLOATS) + 8);                        \
-    float* lds = (float*)(((uintptr_t)buf.data() + 15) & ~(uintptr_t)15);    \
-    for (int b = 0; b < grid; ++b) blockfn(a, b, grid, lds);                 \
-    return 0;                                                                \
-  }
 #else
 // Optional per-kernel timing (bench.py's roofline leg): when enabled, every launch is bracketed by
 // hipEvents recorded on the stream the kernel is launched on; r2l_timing_report() synchronises the
@@ -97,68 +90,45 @@ static void r2l_time_end(hipStream_t s, R2LTimedLaunch& t) {
   std::lock_guard<std::mutex> g(r2l_timing_mutex);
   r2l_timed.push_back(t);
 }
-#define R2L_KERNEL(name, ArgsT, blockfn, LDS_FLOATS) R2L_KERNEL_OCC(name, ArgsT, blockfn, LDS_FLOATS, 1)
+// the host side of every launch wrapper `static int name(const ArgsT& a, int grid, void* stream)`: NT threads per workgroup,
+// LDS_BYTES of dynamic LDS
+#define R2L_LAUNCH(name, NT, LDS_BYTES)                                                                     \
+  {                                                                                                         \
+    R2LTimedLaunch t_;                                                                                      \
+    const bool timed_ = r2l_timing_on;                                                                      \
+    if (timed_) r2l_time_begin(#name "_kernel", (hipStream_t)stream, t_);                                   \
+    hipLaunchKernelGGL(name##_kernel, dim3(grid), dim3(NT), LDS_BYTES, (hipStream_t)stream, a);             \
+    if (timed_) r2l_time_end((hipStream_t)stream, t_);                                                      \
+    const hipError_t e = hipGetLastError();                                                                 \
+    if (e != hipSuccess) return r2l_fail(-10, std::string(#name ": ") + hipGetErrorString(e));              \
+    return 0;                                                                                               \
+  }
 // LDS-free kernels with their own workgroup size (independent wavefronts)
 #define R2L_KERNEL_NT(name, ArgsT, blockfn, NT, WAVES_PER_SIMD)                                 \
   __global__ __launch_bounds__(NT, WAVES_PER_SIMD) void name##_kernel(const ArgsT a) {         \
     blockfn(a, (int)blockIdx.x, (int)gridDim.x, nullptr);                                      \
   }                                                                                            \
-  static int name(const ArgsT& a, int grid, void* stream) {                                    \
-    R2LTimedLaunch t_;                                                                         \
-    const bool timed_ = r2l_timing_on;                                                         \
-    if (timed_) r2l_time_begin(#name "_kernel", (hipStream_t)stream, t_);                      \
-    hipLaunchKernelGGL(name##_kernel, dim3(grid), dim3(NT), 0, (hipStream_t)stream, a);       \
-    if (timed_) r2l_time_end((hipStream_t)stream, t_);                                         \
-    const hipError_t e = hipGetLastError();                                                    \
-    if (e != hipSuccess) return r2l_fail(-10, std::string(#name ": ") + hipGetErrorString(e)); \
-    return 0;                                                                                  \
-  }
+  static int name(const ArgsT& a, int grid, void* stream) R2L_LAUNCH(name, NT, 0)
 // kernels with their own workgroup size AND static LDS
 #define R2L_KERNEL_NT_LDS(name, ArgsT, NT, LDS_FLOATS, WAVES_PER_SIMD, ...)                    \
   __global__ __launch_bounds__(NT, WAVES_PER_SIMD) void name##_kernel(const ArgsT a) {         \
     __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];                             \
     __VA_ARGS__(a, (int)blockIdx.x, (int)gridDim.x, lds);                                      \
   }                                                                                            \
-  static int name(const ArgsT& a, int grid, void* stream) {                                    \
-    R2LTimedLaunch t_;                                                                         \
-    const bool timed_ = r2l_timing_on;                                                         \
-    if (timed_) r2l_time_begin(#name "_kernel", (hipStream_t)stream, t_);                      \
-    hipLaunchKernelGGL(name##_kernel, dim3(grid), dim3(NT), 0, (hipStream_t)stream, a);       \
-    if (timed_) r2l_time_end((hipStream_t)stream, t_);                                         \
-    const hipError_t e = hipGetLastError();                                                    \
-    if (e != hipSuccess) return r2l_fail(-10, std::string(#name ": ") + hipGetErrorString(e)); \
-    return 0;                                                                                  \
-  }
-#define R2L_KERNEL_V(name, ArgsT, LDS_FLOATS, WAVES_PER_SIMD, ...)                             \
-  __global__ __launch_bounds__(R2L_NT, WAVES_PER_SIMD) void name##_kernel(const ArgsT a) {     \
-    __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];                             \
-    __VA_ARGS__(a, (int)blockIdx.x, (int)gridDim.x, lds);                                      \
-  }                                                                                            \
-  static int name(const ArgsT& a, int grid, void* stream) {                                    \
-    R2LTimedLaunch t_;                                                                         \
-    const bool timed_ = r2l_timing_on;                                                         \
-    if (timed_) r2l_time_begin(#name "_kernel", (hipStream_t)stream, t_);                      \
-    hipLaunchKernelGGL(name##_kernel, dim3(grid), dim3(R2L_NT), 0, (hipStream_t)stream, a);   \
-    if (timed_) r2l_time_end((hipStream_t)stream, t_);                                         \
-    const hipError_t e = hipGetLastError();                                                    \
-    if (e != hipSuccess) return r2l_fail(-10, std::string(#name ": ") + hipGetErrorString(e)); \
-    return 0;                                                                                  \
-  }
-#define R2L_KERNEL_OCC(name, ArgsT, blockfn, LDS_FLOATS, WAVES_PER_SIMD)                       \
-  __global__ __launch_bounds__(R2L_NT, WAVES_PER_SIMD) void name##_kernel(const ArgsT a) {                     \
-    __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];                             \
-    blockfn(a, (int)blockIdx.x, (int)gridDim.x, lds);                                          \
-  }                                                                                            \
-  static int name(const ArgsT& a, int grid, void* stream) {                                    \
-    R2LTimedLaunch t_;                                                                         \
-    const bool timed_ = r2l_timing_on;                                                         \
-    if (timed_) r2l_time_begin(#name "_kernel", (hipStream_t)stream, t_);                      \
-    hipLaunchKernelGGL(name##_kernel, dim3(grid), dim3(R2L_NT), 0, (hipStream_t)stream, a);   \
-    if (timed_) r2l_time_end((hipStream_t)stream, t_);                                         \
-    const hipError_t e = hipGetLastError();                                                    \
-    if (e != hipSuccess) return r2l_fail(-10, std::string(#name ": ") + hipGetErrorString(e)); \
-    return 0;                                                                                  \
-  }
+  static int name(const ArgsT& a, int grid, void* stream) R2L_LAUNCH(name, NT, 0)
+// ... of R2L_NT threads
+#define R2L_KERNEL_V(name, ArgsT, LDS_FLOATS, WAVES_PER_SIMD, ...) \
+  R2L_KERNEL_NT_LDS(name, ArgsT, R2L_NT, LDS_FLOATS, WAVES_PER_SIMD, __VA_ARGS__)
+#define R2L_KERNEL_OCC(name, ArgsT, blockfn, LDS_FLOATS, WAVES_PER_SIMD) \
+  R2L_KERNEL_NT_LDS(name, ArgsT, R2L_NT, LDS_FLOATS, WAVES_PER_SIMD, blockfn)
+#define R2L_KERNEL(name, ArgsT, blockfn, LDS_FLOATS) R2L_KERNEL_OCC(name, ArgsT, blockfn, LDS_FLOATS, 1)
+#endif
+
+// the serial emulation compiles the tile forms of the kernels only (r2l_common.h): no row-streaming forward, no plane passes
+#ifdef R2L_SERIAL
+#define R2L_PLANE_PASSES 0
+#else
+#define R2L_PLANE_PASSES 1
 #endif
 
 typedef R2LGeom<64, 64> GFwd;
@@ -439,14 +409,7 @@ R2L_KERNEL(r2l_launch_static_menon, R2LMenonArgs, r2l_static_menon_block, 4)
         ok_ = lds_bytes;                                                                                      \
       }                                                                                                       \
     }                                                                                                         \
-    R2LTimedLaunch t_;                                                                                        \
-    const bool timed_ = r2l_timing_on;                                                                        \
-    if (timed_) r2l_time_begin(#name "_kernel", (hipStream_t)stream, t_);                                     \
-    hipLaunchKernelGGL(name##_kernel, dim3(grid), dim3(a.nw * 64), lds_bytes, (hipStream_t)stream, a);        \
-    if (timed_) r2l_time_end((hipStream_t)stream, t_);                                                        \
-    const hipError_t e = hipGetLastError();                                                                   \
-    if (e != hipSuccess) return r2l_fail(-10, std::string(#name ": ") + hipGetErrorString(e));                \
-    return 0;                                                                                                 \
+    R2L_LAUNCH(name, a.nw * 64, lds_bytes)                                                                    \
   }
 #endif
 // [16-bit / float64 frames] x [Malvar2004] x [unsharp_masking] x [median_denoising]
@@ -530,6 +493,18 @@ static int r2l_band_rows(int B, int H, int W, long slots, const char* env) {
     }
   }
   return (r2l_env_int(env, bh) + 5) / 6 * 6;
+}
+// Work items of a plane pass -- one per (image, 256-column strip, band of band_h rows) -- and its workgroups: nwv items in
+// flight per workgroup, at most `cap` workgroups and R2L_MAX_BLOCKS (the partials of the reduction trees); cap = 0: a pass
+// without partials, one workgroup per nwv items
+static long r2l_plane_items(int B, int H, int W, int band_h) {
+  return (long)B * ((W + 255) / 256) * ((H + band_h - 1) / band_h);
+}
+static int r2l_plane_grid(int B, int H, int W, int band_h, int nwv, long cap) {
+  long g = (r2l_plane_items(B, H, W, band_h) + nwv - 1) / nwv;
+  if (cap && g > cap) g = cap;
+  if (cap && g > R2L_MAX_BLOCKS) g = R2L_MAX_BLOCKS;
+  return (int)g;
 }
 
 // ---- workspace ----------------------------------------------------------------------------------
@@ -689,13 +664,8 @@ static int r2l_check_raw(const R2LRaw& raw, int W, const char* who) {
 #define R2L_F_SPLIT_STATS 2048
 #define R2L_F_INTERNAL (R2L_F_LUMA_VALID | R2L_F_SPLIT_STATS)
 // where the row-streaming forward (r2l_param_stream.h) runs -- and with R2L_F_KEEP_LUMA leaves Y' for kernel B1
-static bool r2l_fwd_streams(const float* additive, int W) {
-#ifdef R2L_SERIAL
-  (void)additive; (void)W;
-  return false;
-#else
-  return !additive && (W & 3) == 0 && W <= 2048 && !r2l_env_int("R2L_FWD_TILED", 0);
-#endif
+static bool r2l_fwd_streams(bool additive, int W) {
+  return R2L_PLANE_PASSES && !additive && (W & 3) == 0 && W <= 2048 && !r2l_env_int("R2L_FWD_TILED", 0);
 }
 static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float* additive,
                             const float* bn_mean_istd, float* out, double* stats, void* workspace,
@@ -801,11 +771,8 @@ static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float*
       const long items = (long)B * fa.nband * nstrip;
       if (items > (1L << 30)) return r2l_fail(-1, "r2l_isp_fwd: batch too large");
       fa.nitems = (int)items;
-      long g = (items + R2L_FA_STATS_NWV - 1) / R2L_FA_STATS_NWV;
-      const long gcap = r2l_env_int("R2L_GRID_FWD", R2L_MAX_BLOCKS);
-      if (g > gcap) g = gcap;
-      if (g > R2L_MAX_BLOCKS) g = R2L_MAX_BLOCKS;
-      return raw.u16 ? r2l_launch_fwd_stats_u16(fa, (int)g, stream) : r2l_launch_fwd_stats(fa, (int)g, stream);
+      const int g = r2l_plane_grid(B, H, W, fa.band_h, R2L_FA_STATS_NWV, r2l_env_int("R2L_GRID_FWD", R2L_MAX_BLOCKS));
+      return raw.u16 ? r2l_launch_fwd_stats_u16(fa, g, stream) : r2l_launch_fwd_stats(fa, g, stream);
     }
     if (out && !stats && (flags & R2L_F_LUMA_VALID) && kept_ok) {
       // apply pass on the kept Y'
@@ -912,10 +879,255 @@ int r2l_bn_bwd_reduce(const float* grad_out, const float* out, const double* tot
   return r2l_launch_reduce_rows(r, 6, stream);
 }
 
-static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float* additive,
-                            const float* bn_mean_istd, const float* bn_bwd, const float* grad_out,
-                            float* grad_params, float* grad_raw, void* workspace, size_t workspace_bytes, int B,
-                            int H, int W, int flags, void* stream, const R2LEpi* ep = nullptr, float* guv = nullptr) {
+// ---- the backward: one plan, one launcher ---------------------------------------------------------------------------------
+#define R2L_STEP_EPI_MASK (R2L_STEP_EPI_HFLIP | R2L_STEP_EPI_VFLIP | (3 << R2L_STEP_EPI_ROT_SHIFT))
+// R2L_BWD_PLANES of diagnostic builds: the plane passes (and the recomputing BatchNorm sums) below their pixel thresholds too
+static bool r2l_bwd_planes_forced() { return r2l_env_int("R2L_BWD_PLANES", 0) != 0; }
+// kernel B1 as a tile kernel (which instantiation), as the plane passes, or as a reduced plane pass (R2LBwdPlan::select)
+enum { R2L_B1_TILE_SAVED, R2L_B1_TILE_ADD, R2L_B1_TILE_EXACT, R2L_B1_TILE_RAGGED, R2L_B1_PLANES };
+// What a backward launches, decided from the shape of the call alone (r2l_bwd_plan): r2l_bwd_launch walks it, and
+// r2l_isp_step_bwd_select_passes reports its `select`
+struct R2LBwdPlan {
+  int select;           // R2L_SELECT_FULL: every sum; else the R2L_SELECT_* bits of the reduced passes that run
+  int b1;               // R2L_B1_*
+  bool saved;           // kernel B1 reads the Y' the forward kept
+  bool b2_planes;       // kernel B2 as plane passes (the blur's adjoint HP, then the sums) instead of the tile kernel
+  bool blur_hp;         // the blur-weight sums and HP in one pass (r2l_bwd1_blur_hp_block)
+  bool in_kernel;       // the last workgroups of kernel B2 reduce and unfold; else three tiny launches do
+  int b1_grid, b1_band;  // kernel B1 (band heights: 0 for a tile kernel); b1_grid workgroups write its partials
+  int hb_band;           // the blur / blur + HP pass, on kernel B1's grid
+  int hp_grid, hp_band;  // the HP pass alone
+  int b2_grid, b2_band, b2_nmain;  // kernel B2: the tile kernel, or the sums pass (b2_nmain workgroups + R2L_B2S_HELPERS)
+  int raw_grid, raw_band;          // the d/d raw gather pass
+};
+// grad_mask: the R2L_GRAD_* bits a caller of r2l_isp_step_bwd_select asks for, 0 = every parameter gradient; want_raw: d/d raw too.
+// The only reader of the backward's overrides of diagnostic builds (R2L_BWD_*, R2L_GRID_BWD*, the band heights).
+static R2LBwdPlan r2l_bwd_plan(unsigned grad_mask, bool want_raw, int raw_u16, bool has_additive, bool epi_on,
+                               bool keep_luma, int B, int H, int W) {
+  R2LBwdPlan p = {};
+  // (the serial emulation has no row-streaming forward, so nothing is ever saved there and every plan is tile kernels)
+  p.saved = keep_luma && r2l_fwd_streams(has_additive, W) && (want_raw || !r2l_env_int("R2L_BWD1_RECOMPUTE", 0));
+  // frames that do not tile by 64: Y' recomputed in LDS, kept or not; an additive layer means 256 x 256 frames, which tile exactly
+  const bool exact = (H % GBwd1::TH == 0) && (W % GBwd1::TW == 0);
+  p.b1 = (p.saved && exact) ? R2L_B1_TILE_SAVED
+                            : (has_additive ? R2L_B1_TILE_ADD : (exact ? R2L_B1_TILE_EXACT : R2L_B1_TILE_RAGGED));
+#ifndef R2L_SERIAL
+  // The plane passes where there is enough work for their launch tails: 128x256x256 (8.4 Mpx) 102 us against the tile kernels'
+  // 110+, 64x256x256 (4.2 Mpx) 77.7 against 80.5 since the tails were shortened (profiles/r04_small.txt; round 3: 99 against 85,
+  // and the threshold was 6 Mi px)
+  // (d/d raw: the plane passes at every size -- the gather pass reads the planes they leave)
+  const bool planes = want_raw || r2l_bwd_planes_forced() || (size_t)B * H * W >= ((size_t)4 << 20);
+  const bool b1_planes = p.saved && planes && (want_raw || !r2l_env_int("R2L_BWD1_TILED", 0));
+  p.b2_planes = b1_planes && (want_raw || !r2l_env_int("R2L_BWD2_TILED", 0));
+  // The reduced passes: the sums of the black level, white balance, colour matrix, debayer and sharpen gradients need the whole
+  // chain; the reduced forms exist as plane passes only
+  // (16-bit frames and an output epilogue have no d/d raw -- r2l_raw_grad_preconditions refuses them before a call gets here, the
+  // query reports the full route for them)
+  const unsigned cheap = R2L_GRAD_GAMMA | R2L_GRAD_BLUR | R2L_GRAD_RAW;
+  const bool gam = (grad_mask & R2L_GRAD_GAMMA) != 0, blur = (grad_mask & R2L_GRAD_BLUR) != 0;
+  if (grad_mask && !(grad_mask & ~cheap) && p.b2_planes && !(want_raw && (raw_u16 || epi_on))) {
+    p.select = R2L_SELECT_B1 | (want_raw ? R2L_SELECT_RAW : 0);
+    if (blur) p.select |= want_raw ? R2L_SELECT_BLUR_HP : R2L_SELECT_BLUR;
+    else if (want_raw) p.select |= R2L_SELECT_HP;
+  }
+  auto band_rows = [&](long slots, const char* env) { return r2l_band_rows(B, H, W, slots, env); };
+  if (b1_planes) {
+    // persistent workgroups of 4 independent wavefronts, `occ` per CU (the full pass: two, <= 256 VGPRs), not more workgroups
+    // than kernel B2 runs (its last workgroups reduce both kernels' partials); band height as for the forward's plane passes
+    const int occ = !p.select ? 2 : ((want_raw && !gam) ? R2L_BPS_OCC_RAW : R2L_BPS_OCC);
+    p.b1 = R2L_B1_PLANES;
+    p.b1_band = band_rows(256L * 4 * occ, "R2L_BP_BAND");
+    p.b1_grid = r2l_plane_grid(B, H, W, p.b1_band, R2L_BP_NWV, r2l_env_int("R2L_GRID_BWD1", 256 * occ));
+    // its second pass (the blur-weight sums) and kernel B2's first (the blur's adjoint) read the same plane: one pass when B2
+    // runs as plane passes too.  Its own band height: R2L_HB_OCC wavefronts per SIMD; not more workgroups than wrote the first
+    // pass's partials
+    p.blur_hp = p.select ? (p.select & R2L_SELECT_BLUR_HP) != 0 : (p.b2_planes && !r2l_env_int("R2L_BWD_SPLIT_BLUR", 0));
+    p.hb_band = band_rows(256L * 4 * R2L_HB_OCC, "R2L_HB_BAND");
+  }
+  if (p.select ? (p.select & R2L_SELECT_HP) != 0 : (p.b2_planes && !p.blur_hp)) {
+    p.hp_band = band_rows(256L * 4 * 4, "R2L_HP_BAND");
+    p.hp_grid = r2l_plane_grid(B, H, W, p.hp_band, R2L_BP_NWV, 0);
+  }
+  if (p.b2_planes && !p.select) {
+    // the sums pass: its last workgroups reduce B2's partials; R2L_B2S_HELPERS more workgroups (the grid leaves room for them
+    // beside one round of the others) add B1's meanwhile; the last arrival of all unfolds the 155 totals into the 132 gradients
+    p.b2_band = band_rows(256L * 4 * 3, "R2L_B2S_BAND");
+    p.b2_nmain = r2l_plane_grid(B, H, W, p.b2_band, R2L_B2S_NWV, r2l_env_int("R2L_GRID_BWD2", 768));  // 3 workgroups per CU
+    p.b2_grid = p.b2_nmain + R2L_B2S_HELPERS;
+    p.in_kernel = true;
+  }
+  if (want_raw && p.b2_planes) {  // d/d raw from HP and the chroma gradient planes: one item per wavefront
+    p.raw_band = band_rows(256L * 4 * R2L_BR_OCC, "R2L_BR_BAND");
+    p.raw_grid = r2l_plane_grid(B, H, W, p.raw_band, R2L_BR_NWV, 0);
+  }
+#endif
+  if (p.b1 != R2L_B1_PLANES) {
+    const int ntiles = B * ((H + GBwd1::TH - 1) / GBwd1::TH) * ((W + GBwd1::TW - 1) / GBwd1::TW);
+    p.b1_grid = r2l_tile_grid(ntiles, r2l_env_int("R2L_GRID_BWD1", 256));
+  }
+  if (!p.b2_planes) {
+    // bwd2 fits two workgroups per CU (<= 128 VGPRs, 68 KB of LDS): 512 workgroups.  Its last workgroups reduce both kernels'
+    // partials (B1's were written by b1_grid workgroups: every level-1 group of B2's grid adds the B1 partials of its own 16
+    // workgroup ids, as far as they exist) and unfold them into the 132 gradients; if B1 ran MORE workgroups than B2 (R2L_GRID_*
+    // overrides of diagnostic builds) three tiny launches do it
+    const int ntiles = B * ((H + GBwd2::TH - 1) / GBwd2::TH) * ((W + GBwd2::TW - 1) / GBwd2::TW);
+    p.b2_grid = r2l_tile_grid(ntiles, r2l_env_int("R2L_GRID_BWD2", R2L_OCC_BWD2 >= 4 ? 512 : 256));
+    p.in_kernel = p.b1_grid <= p.b2_grid;
+  }
+  return p;
+}
+int r2l_isp_step_bwd_select_passes(unsigned grad_mask, int raw_u16, int has_additive, int B, int H, int W, int phase) {
+  if (B < 1 || H < 1 || W < 1) return R2L_SELECT_FULL;
+  return r2l_bwd_plan(grad_mask, (grad_mask & R2L_GRAD_RAW) != 0, raw_u16, has_additive != 0, (phase & R2L_STEP_EPI_MASK) != 0,
+                      (phase & R2L_STEP_KEEP_LUMA) != 0, B, H, W)
+      .select;
+}
+// what a backward works on; the workspace holds the folded weights of `params` (and, behind a step's forward, Y')
+struct R2LBwdCall {
+  R2LRaw raw;
+  const float *params, *additive, *bn, *bn_bwd, *gout;
+  float *grad_params, *grad_raw, *guv;  // guv: the chroma gradient planes, with grad_raw
+  R2LEpi ep;
+  unsigned grad_mask;  // r2l_bwd_plan's
+  int B, H, W;
+  void* stream;
+};
+static R2LBwd1Args r2l_bwd1_args(const R2LBwdCall& c, const R2LWorkspace& ws, const R2LBwdPlan& p) {
+  R2LBwd1Args a;
+  a.raw = c.raw;
+  a.additive = c.additive;
+  a.F = ws.folded;
+  a.bn = c.bn;
+  a.bn_bwd = c.bn_bwd;
+  a.gout = c.gout;
+  a.gypp = ws.gypp;
+  a.partial = ws.part_b1;
+  a.B = c.B;
+  a.H = c.H;
+  a.W = c.W;
+  a.debug = ws.debug + 8 * R2L_MAX_BLOCKS;
+  a.yp = p.saved ? ws.yp : nullptr;
+  a.ep = c.ep;
+  a.band_h = p.b1_band;
+  a.hp = p.b1 == R2L_B1_PLANES ? ws.hp : nullptr;
+  a.band_hb = p.hb_band;
+  return a;
+}
+// (as the HP pass takes them: no sums, no reduction)
+static R2LBwd2Args r2l_bwd2_args(const R2LBwdCall& c, const R2LWorkspace& ws, const R2LBwdPlan& p) {
+  R2LBwd2Args a;
+  a.raw = c.raw;
+  a.F = ws.folded;
+  a.gypp = ws.gypp;
+  a.partial = ws.part_b2;
+  a.B = c.B;
+  a.H = c.H;
+  a.W = c.W;
+  a.debug = ws.debug + 16 * R2L_MAX_BLOCKS;
+  a.tree = R2LTree{nullptr, nullptr, nullptr, nullptr, 0, 0};
+  a.params = nullptr;
+  a.grad_params = nullptr;
+  a.hp = p.b2_planes ? ws.hp : nullptr;
+  a.band_h = p.hp_band;
+  a.nmain = 0;
+  a.b1_partial = nullptr;
+  a.b1_n = 0;
+  a.b1_tot = nullptr;
+  return a;
+}
+#ifndef R2L_SERIAL
+static int r2l_bwd_hp_pass(const R2LBwdCall& c, const R2LWorkspace& ws, const R2LBwdPlan& p) {
+  return r2l_launch_bwd2_hp(r2l_bwd2_args(c, ws, p), p.hp_grid, c.stream);
+}
+static int r2l_bwd_raw_pass(const R2LBwdCall& c, const R2LWorkspace& ws, const R2LBwdPlan& p) {
+  if (r2l_plane_items(c.B, c.H, c.W, p.raw_band) > (1L << 30)) return r2l_fail(-1, "r2l_isp_step_bwd_raw: batch too large");
+  const R2LRawGradArgs a{ws.folded, ws.hp, c.guv, c.grad_raw, c.B, c.H, c.W, p.raw_band};
+  return r2l_launch_bwd_raw_plane(a, p.raw_grid, c.stream);
+}
+#endif
+// The launches of plan `p` = r2l_bwd_plan(this call), in order.  The workspace's folded weights and arrival counters are valid
+// (this call's fold kernel, or the step's forward)
+static int r2l_bwd_launch(const R2LBwdCall& c, const R2LWorkspace& ws, const R2LBwdPlan& p) {
+  if (c.ep.on && c.additive) return r2l_fail(-3, "r2l_isp_bwd: no output epilogue with an additive layer");
+  const int u16 = c.raw.u16 ? 1 : 0, g1 = p.b1_grid;
+  void* const stream = c.stream;
+  const R2LBwd1Args a1 = r2l_bwd1_args(c, ws, p);
+  if (p.b1 != R2L_B1_PLANES) {
+    typedef int (*launch_t)(const R2LBwd1Args&, int, void*);
+    static const launch_t tile[4][2] = {{r2l_launch_bwd1_saved, r2l_launch_bwd1_saved_u16},
+                                        {r2l_launch_bwd1_add_exact, r2l_launch_bwd1_add_exact_u16},
+                                        {r2l_launch_bwd1, r2l_launch_bwd1_u16},
+                                        {r2l_launch_bwd1_ragged, r2l_launch_bwd1_ragged_u16}};
+    if (int e = tile[p.b1][u16](a1, g1, stream)) return e;
+  }
+#ifndef R2L_SERIAL
+  else if (p.select) {  // the reduced passes: behind a step's forward only (packed parameters, Y')
+    const bool gam = (c.grad_mask & R2L_GRAD_GAMMA) != 0, blur = (c.grad_mask & R2L_GRAD_BLUR) != 0;
+    // the gamma sum: slot R2L_B1_GGAM of kernel B1's partials, one slot through the shared tree
+    R2LBwd1SelArgs sa{a1, c.guv,
+                      R2LBpSelect{R2LTree{ws.part_b1 + (size_t)R2L_B1_GGAM * g1, nullptr, ws.gpartial, ws.counters, 1, 0},
+                                  c.params, c.grad_params, blur}};
+    typedef int (*launch_t)(const R2LBwd1SelArgs&, int, void*);
+#define R2L_BPS_ROW(name) {{name, name##_u16}, {name##_epi, name##_epi_u16}}
+    static const launch_t sel[3][2][2] = {R2L_BPS_ROW(r2l_launch_bwd1_sel_gamma), R2L_BPS_ROW(r2l_launch_bwd1_sel_gypp),
+                                          R2L_BPS_ROW(r2l_launch_bwd1_sel_gypp_gamma)};
+#undef R2L_BPS_ROW
+    if (int e = c.grad_raw ? (gam ? r2l_launch_bwd1_sel_raw_gamma(sa, g1, stream) : r2l_launch_bwd1_sel_raw(sa, g1, stream))
+                           : sel[!blur ? 0 : (gam ? 2 : 1)][c.ep.on ? 1 : 0][u16](sa, g1, stream))
+      return e;
+    if (blur) {  // the 25 sums (and HP, for d/d raw) on kernel B1's grid; its last workgroup writes the blur gradient
+      sa.s.tree = R2LTree{ws.part_b1, nullptr, ws.gpartial, ws.counters, R2L_B1_GAU, 0};
+      if (int e = p.blur_hp ? r2l_launch_bwd1_blur_hp_fin(sa, g1, stream) : r2l_launch_bwd1_blur_fin(sa, g1, stream)) return e;
+    }
+    if (!c.grad_raw) return 0;
+    if (p.select & R2L_SELECT_HP)
+      if (int e = r2l_bwd_hp_pass(c, ws, p)) return e;
+    return r2l_bwd_raw_pass(c, ws, p);
+  } else {  // kernel B1 as two passes over planes
+    typedef int (*launch_t)(const R2LBwd1Args&, int, void*);
+    static const launch_t plane[2][2] = {{r2l_launch_bwd1_plane, r2l_launch_bwd1_plane_u16},
+                                         {r2l_launch_bwd1_plane_epi, r2l_launch_bwd1_plane_epi_u16}};
+    // (d/d raw: float32 frames, no epilogue -- r2l_raw_grad_preconditions)
+    if (int e = c.grad_raw ? r2l_launch_bwd1_plane_guv(R2LBwd1GuvArgs{a1, c.guv}, g1, stream)
+                           : plane[c.ep.on ? 1 : 0][u16](a1, g1, stream))
+      return e;
+    if (int e = p.blur_hp ? r2l_launch_bwd1_blur_hp(a1, g1, stream) : r2l_launch_bwd1_blur(a1, g1, stream)) return e;
+  }
+#endif
+  R2LBwd2Args a2 = r2l_bwd2_args(c, ws, p);
+  a2.params = c.params;
+  a2.grad_params = c.grad_params;
+#ifndef R2L_SERIAL
+  if (p.b2_planes) {  // kernel B2 as two passes over planes (r2l_param_plane_bwd.h)
+    if (!p.blur_hp)
+      if (int e = r2l_bwd_hp_pass(c, ws, p)) return e;
+    a2.band_h = p.b2_band;
+    a2.tree = R2LTree{nullptr, ws.part_b2, ws.gpartial, ws.counters, 0, 0};
+    a2.nmain = p.b2_nmain;
+    a2.b1_partial = ws.part_b1;
+    a2.b1_n = g1;
+    a2.b1_tot = ws.sums;
+    if (int e = u16 ? r2l_launch_bwd2_sums_u16(a2, p.b2_grid, stream) : r2l_launch_bwd2_sums(a2, p.b2_grid, stream)) return e;
+    return c.grad_raw ? r2l_bwd_raw_pass(c, ws, p) : 0;
+  }
+#endif
+  if (c.grad_raw) return r2l_fail(-3, "r2l_isp_step_bwd_raw: internal: the plane passes did not run");
+  const int g2 = p.b2_grid;
+  a2.tree = R2LTree{ws.part_b1, ws.part_b2, ws.gpartial, p.in_kernel ? ws.counters : nullptr, R2L_B1_NACC, g1};
+  // (even tile shares: uneven ones for the two workgroups of a CU measured no gain, profiles/r03_bwd2_tile_shares.txt)
+  if (int e = u16 ? r2l_launch_bwd2_u16(a2, g2, stream) : r2l_launch_bwd2(a2, g2, stream)) return e;
+  if (p.in_kernel) return 0;
+  R2LReduceRowsArgs r1{ws.part_b1, ws.sums, g1, 1.0, nullptr};
+  if (int e = r2l_launch_reduce_rows(r1, R2L_B1_NACC, stream)) return e;
+  R2LReduceRowsArgs r2{ws.part_b2, ws.sums + R2L_B1_NACC, g2, 1.0, nullptr};
+  if (int e = r2l_launch_reduce_rows(r2, R2L_B2_NACC, stream)) return e;
+  R2LUnfoldArgs ua{c.params, ws.sums, c.grad_params, 1.0f};
+  return r2l_launch_unfold(ua, 1, stream);
+}
+// r2l_isp_bwd / r2l_isp_bwd_u16: no step behind them -- the call folds the parameters itself -- and no d/d raw
+static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float* additive, const float* bn_mean_istd,
+                            const float* bn_bwd, const float* grad_out, float* grad_params, float* grad_raw, void* workspace,
+                            size_t workspace_bytes, int B, int H, int W, int flags, void* stream) {
   if (int e = r2l_check_dims(B, H, W)) return e;
   if (int e = r2l_check_raw(raw, W, "r2l_isp_bwd")) return e;
   if (!params || !grad_out || !grad_params || !workspace)
@@ -923,8 +1135,7 @@ static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float*
   if (bn_bwd && !bn_mean_istd) return r2l_fail(-1, "r2l_isp_bwd: bn_bwd given without bn_mean_istd");
   if (additive && (H != 256 || W != 256))
     return r2l_fail(-1, "additive_layer is (1,3,256,256): needs 256x256 frames");
-  // grad_raw: only r2l_isp_step_bwd_raw, which hands the chroma gradient planes (guv) and has checked the frames
-  if (grad_raw && !guv)
+  if (grad_raw)
     return r2l_fail(-3, "r2l_isp_bwd: grad_raw is produced by the staged path or r2l_isp_step_bwd_raw, not this call");
   const R2LWorkspace ws = r2l_carve(workspace, B, H, W);
   if (workspace_bytes < ws.total) return r2l_fail(-2, "r2l_isp_bwd: workspace too small");
@@ -932,280 +1143,10 @@ static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float*
     R2LFoldArgs fa{params, ws.folded, ws.counters};
     if (int e = r2l_launch_fold(fa, 1, stream)) return e;
   }
-  const int ntiles = B * ((H + GBwd1::TH - 1) / GBwd1::TH) * ((W + GBwd1::TW - 1) / GBwd1::TW);
-  const int g1 = r2l_tile_grid(ntiles, r2l_env_int("R2L_GRID_BWD1", 256));
-  R2LBwd1Args a1;
-  a1.raw = raw;
-  a1.additive = additive;
-  a1.F = ws.folded;
-  a1.bn = bn_mean_istd;
-  a1.bn_bwd = bn_bwd;
-  a1.gout = grad_out;
-  a1.gypp = ws.gypp;
-  a1.partial = ws.part_b1;
-  a1.B = B;
-  a1.H = H;
-  a1.W = W;
-  a1.debug = ws.debug + 8 * R2L_MAX_BLOCKS;
-  const bool saved = (flags & R2L_F_KEEP_LUMA) && r2l_fwd_streams(additive, W) &&
-                     (grad_raw || !r2l_env_int("R2L_BWD1_RECOMPUTE", 0));
-  a1.yp = saved ? ws.yp : nullptr;
-  a1.ep = (ep && ep->on) ? *ep : R2LEpi{0, 0, 0, 0};
-  a1.band_h = 0;
-  a1.hp = nullptr;
-  a1.band_hb = 0;
-  if (a1.ep.on && additive) return r2l_fail(-3, "r2l_isp_bwd: no output epilogue with an additive layer");
-  const bool exact = (H % GBwd1::TH == 0) && (W % GBwd1::TW == 0);
-  int g1p = 0;  // workgroups of the plane passes, when they run
-  bool blur_hp = false;  // ... with r2l_bwd1_blur_hp_block doing kernel B2's first pass
-#ifndef R2L_SERIAL
-  // ... where there is enough work for their launch tails: 128x256x256 (8.4 Mpx) 102 us against the tile kernels' 110+,
-  // 64x256x256 (4.2 Mpx) 77.7 against 80.5 since the tails were shortened (profiles/r04_small.txt; round 3: 99 against 85,
-  // and the threshold was 6 Mi px)
-  // (d/d raw: the plane passes at every size -- the gather pass reads the planes they leave)
-  const bool planes = grad_raw || r2l_env_int("R2L_BWD_PLANES", 0) || (size_t)B * H * W >= ((size_t)4 << 20);
-  if (saved && planes && (grad_raw || !r2l_env_int("R2L_BWD1_TILED", 0))) {
-    // persistent workgroups of 4 independent wavefronts, two per CU (<= 256 VGPRs), not more workgroups than kernel B2
-    // runs (its last workgroups reduce both kernels' partials); band height as for the forward's plane passes
-    const long nstrip = (W + 255) / 256;
-    a1.band_h = r2l_band_rows(B, H, W, 256L * 4 * 2, "R2L_BP_BAND");
-    const long items = (long)B * nstrip * ((H + a1.band_h - 1) / a1.band_h);
-    long g = (items + R2L_BP_NWV - 1) / R2L_BP_NWV;
-    const long cap = r2l_env_int("R2L_GRID_BWD1", 512);
-    if (g > cap) g = cap;
-    if (g > R2L_MAX_BLOCKS) g = R2L_MAX_BLOCKS;
-    g1p = (int)g;
-  }
-#endif
-  int e1;
-  if (g1p) {
-#ifndef R2L_SERIAL
-    if (grad_raw)  // (float32 frames, no epilogue: r2l_isp_step_bwd_raw checked)
-      e1 = r2l_launch_bwd1_plane_guv(R2LBwd1GuvArgs{a1, guv}, g1p, stream);
-    else
-      e1 = a1.ep.on ? (raw.u16 ? r2l_launch_bwd1_plane_epi_u16(a1, g1p, stream) : r2l_launch_bwd1_plane_epi(a1, g1p, stream))
-                    : (raw.u16 ? r2l_launch_bwd1_plane_u16(a1, g1p, stream) : r2l_launch_bwd1_plane(a1, g1p, stream));
-    // its second pass (the blur-weight sums) and kernel B2's first (the blur's adjoint) read the same plane: one pass
-    // when B2 runs as plane passes too
-    blur_hp = (grad_raw || !r2l_env_int("R2L_BWD2_TILED", 0)) && !r2l_env_int("R2L_BWD_SPLIT_BLUR", 0);
-    a1.hp = ws.hp;
-    // (its own band height: R2L_HB_OCC wavefronts per SIMD; not more workgroups than wrote the first pass's partials)
-    a1.band_hb = r2l_band_rows(B, H, W, 256L * 4 * R2L_HB_OCC, "R2L_HB_BAND");
-    if (!e1) e1 = blur_hp ? r2l_launch_bwd1_blur_hp(a1, g1p, stream) : r2l_launch_bwd1_blur(a1, g1p, stream);
-#else
-    e1 = 0;
-#endif
-  } else if (saved && exact)
-    e1 = raw.u16 ? r2l_launch_bwd1_saved_u16(a1, g1, stream) : r2l_launch_bwd1_saved(a1, g1, stream);
-  else if (raw.u16)   // (frames that do not tile by 64: Y' recomputed in LDS, kept or not -- a1.yp is not read)
-    e1 = additive ? r2l_launch_bwd1_add_exact_u16(a1, g1, stream)   // (additive: 256 x 256 frames, which tile exactly)
-                  : (exact ? r2l_launch_bwd1_u16(a1, g1, stream) : r2l_launch_bwd1_ragged_u16(a1, g1, stream));
-  else
-    e1 = additive ? r2l_launch_bwd1_add_exact(a1, g1, stream)
-                  : (exact ? r2l_launch_bwd1(a1, g1, stream) : r2l_launch_bwd1_ragged(a1, g1, stream));
-  if (e1) return e1;
-  const int ntiles2 = B * ((H + GBwd2::TH - 1) / GBwd2::TH) * ((W + GBwd2::TW - 1) / GBwd2::TW);
-  // bwd2 fits two workgroups per CU (<= 128 VGPRs, 68 KB of LDS): 512 workgroups
-  const int g2 = r2l_tile_grid(ntiles2, r2l_env_int("R2L_GRID_BWD2", R2L_OCC_BWD2 >= 4 ? 512 : 256));
-  R2LBwd2Args a2;
-  a2.nmain = 0;
-  a2.b1_partial = nullptr;
-  a2.b1_n = 0;
-  a2.b1_tot = nullptr;
-  a2.raw = raw;
-  a2.F = ws.folded;
-  a2.gypp = ws.gypp;
-  a2.partial = ws.part_b2;
-  a2.B = B;
-  a2.H = H;
-  a2.W = W;
-  a2.debug = ws.debug + 16 * R2L_MAX_BLOCKS;
-  // B2's last workgroups reduce both kernels' partials (B1's were written by g1 workgroups: every level-1 group
-  // of B2's grid adds the B1 partials of its own 16 workgroup ids, as far as they exist) and unfold them into the
-  // 132 gradients; if B1 ran MORE workgroups than B2 (R2L_GRID_* overrides of diagnostic builds) three tiny
-  // launches do it
-  const int g1w = g1p ? g1p : g1;  // workgroups that wrote B1's partials
-#ifndef R2L_SERIAL
-  if (g1p && (grad_raw || !r2l_env_int("R2L_BWD2_TILED", 0))) {
-    // kernel B2 as two passes over planes (r2l_param_plane_bwd.h)
-    const long nstrip = (W + 255) / 256;
-    auto band_rows = [&](long slots, const char* env) { return r2l_band_rows(B, H, W, slots, env); };
-    a2.hp = ws.hp;
-    a2.band_h = band_rows(256L * 4 * 4, "R2L_HP_BAND");
-    const long hitems = (long)B * nstrip * ((H + a2.band_h - 1) / a2.band_h);
-    a2.tree = R2LTree{nullptr, nullptr, nullptr, nullptr, 0, 0};
-    a2.params = nullptr;
-    a2.grad_params = nullptr;
-    if (!blur_hp)
-      if (int e = r2l_launch_bwd2_hp(a2, (int)((hitems + R2L_BP_NWV - 1) / R2L_BP_NWV), stream)) return e;
-    a2.band_h = band_rows(256L * 4 * 3, "R2L_B2S_BAND");
-    const long sitems = (long)B * nstrip * ((H + a2.band_h - 1) / a2.band_h);
-    long gs = (sitems + R2L_B2S_NWV - 1) / R2L_B2S_NWV;
-    const long cap = r2l_env_int("R2L_GRID_BWD2", 768);  // 3 workgroups of 4 wavefronts per CU
-    if (gs > cap) gs = cap;
-    if (gs > R2L_MAX_BLOCKS) gs = R2L_MAX_BLOCKS;
-    // its last workgroups reduce B2's partials; R2L_B2S_HELPERS more workgroups (the grid leaves room for them beside one
-    // round of the others) add B1's meanwhile; the last arrival of all unfolds the 155 totals into the 132 gradients
-    a2.tree = R2LTree{nullptr, ws.part_b2, ws.gpartial, ws.counters, 0, 0};
-    a2.nmain = (int)gs;
-    a2.b1_partial = ws.part_b1;
-    a2.b1_n = g1w;
-    a2.b1_tot = ws.sums;
-    a2.params = params;
-    a2.grad_params = grad_params;
-    const int grid = (int)gs + R2L_B2S_HELPERS;
-    if (int e = raw.u16 ? r2l_launch_bwd2_sums_u16(a2, grid, stream) : r2l_launch_bwd2_sums(a2, grid, stream)) return e;
-    if (!grad_raw) return 0;
-    // d/d raw from HP and the chroma gradient planes (r2l_bwd_raw_plane_block): one item per wavefront
-    R2LRawGradArgs ar{ws.folded, ws.hp, guv, grad_raw, B, H, W, band_rows(256L * 4 * R2L_BR_OCC, "R2L_BR_BAND")};
-    const long ritems = (long)B * nstrip * ((H + ar.band_h - 1) / ar.band_h);
-    if (ritems > (1L << 30)) return r2l_fail(-1, "r2l_isp_step_bwd_raw: batch too large");
-    return r2l_launch_bwd_raw_plane(ar, (int)((ritems + R2L_BR_NWV - 1) / R2L_BR_NWV), stream);
-  }
-#endif
-  if (grad_raw) return r2l_fail(-3, "r2l_isp_step_bwd_raw: internal: the plane passes did not run");
-  const bool in_kernel = g1w <= g2;
-  a2.tree = R2LTree{ws.part_b1, ws.part_b2, ws.gpartial, in_kernel ? ws.counters : nullptr, R2L_B1_NACC, g1w};
-  a2.params = params;
-  a2.grad_params = grad_params;
-  // (even tile shares: uneven ones for the two workgroups of a CU measured no gain, profiles/r03_bwd2_tile_shares.txt)
-  if (int e = raw.u16 ? r2l_launch_bwd2_u16(a2, g2, stream) : r2l_launch_bwd2(a2, g2, stream)) return e;
-  if (in_kernel) return 0;
-  R2LReduceRowsArgs r1{ws.part_b1, ws.sums, g1w, 1.0, nullptr};
-  if (int e = r2l_launch_reduce_rows(r1, R2L_B1_NACC, stream)) return e;
-  R2LReduceRowsArgs r2{ws.part_b2, ws.sums + R2L_B1_NACC, g2, 1.0, nullptr};
-  if (int e = r2l_launch_reduce_rows(r2, R2L_B2_NACC, stream)) return e;
-  R2LUnfoldArgs ua{params, ws.sums, grad_params, 1.0f};
-  return r2l_launch_unfold(ua, 1, stream);
-}
-
-// ---- the backward of a subset of the gradients (r2l_isp_step_bwd_select) ------------------------------------------------
-#define R2L_STEP_EPI_MASK (R2L_STEP_EPI_HFLIP | R2L_STEP_EPI_VFLIP | (3 << R2L_STEP_EPI_ROT_SHIFT))
-// the passes a mask takes (R2L_SELECT_*), R2L_SELECT_FULL = today's route: the sums of the black level, white balance, colour
-// matrix, debayer and sharpen gradients need the whole chain; the reduced passes exist as plane passes only
-static int r2l_select_route(unsigned mask, int raw_u16, bool has_additive, int B, int H, int W, int phase) {
-#ifdef R2L_SERIAL
-  (void)mask; (void)raw_u16; (void)has_additive; (void)B; (void)H; (void)W; (void)phase;
-  return R2L_SELECT_FULL;
-#else
-  const unsigned cheap = R2L_GRAD_GAMMA | R2L_GRAD_BLUR | R2L_GRAD_RAW;
-  if (!mask || (mask & ~cheap)) return R2L_SELECT_FULL;
-  static const float some_layer = 0.f;
-  if (!(phase & R2L_STEP_KEEP_LUMA) || !r2l_fwd_streams(has_additive ? &some_layer : nullptr, W)) return R2L_SELECT_FULL;
-  const size_t px = (size_t)B * H * W;
-  const bool raw = (mask & R2L_GRAD_RAW) != 0;
-  // (d/d raw: the plane passes at every size, as r2l_isp_step_bwd_raw; 16-bit frames and an output epilogue have no d/d raw --
-  // r2l_raw_grad_preconditions refuses them before a call gets here, the query reports the full route for them)
-  if (raw) {
-    if (raw_u16 || (phase & R2L_STEP_EPI_MASK)) return R2L_SELECT_FULL;
-  } else {  // (where r2l_isp_bwd_impl takes the plane passes)
-    if (!(r2l_env_int("R2L_BWD_PLANES", 0) || px >= ((size_t)4 << 20))) return R2L_SELECT_FULL;
-    if (r2l_env_int("R2L_BWD1_RECOMPUTE", 0) || r2l_env_int("R2L_BWD1_TILED", 0) || r2l_env_int("R2L_BWD2_TILED", 0))
-      return R2L_SELECT_FULL;
-  }
-  int passes = R2L_SELECT_B1;
-  if (mask & R2L_GRAD_BLUR) passes |= raw ? R2L_SELECT_BLUR_HP : R2L_SELECT_BLUR;
-  else if (raw) passes |= R2L_SELECT_HP;
-  if (raw) passes |= R2L_SELECT_RAW;
-  return passes;
-#endif
-}
-int r2l_isp_step_bwd_select_passes(unsigned grad_mask, int raw_u16, int has_additive, int B, int H, int W, int phase) {
-  if (B < 1 || H < 1 || W < 1) return R2L_SELECT_FULL;
-  return r2l_select_route(grad_mask, raw_u16, has_additive != 0, B, H, W, phase);
-}
-// the reduced passes of `passes` (!= R2L_SELECT_FULL: r2l_select_route has checked the frames); the workspace went through this
-// step's forward (folded weights, packed parameters, Y')
-static int r2l_isp_bwd_select(const R2LRaw& raw, const float* bn_mean_istd, const float* bn_bwd, const float* grad_out,
-                              float* grad_params, float* grad_raw, float* guv, const R2LWorkspace& ws, int B, int H, int W,
-                              const R2LEpi& ep, unsigned mask, int passes, void* stream) {
-#ifdef R2L_SERIAL
-  (void)raw; (void)bn_mean_istd; (void)bn_bwd; (void)grad_out; (void)grad_params; (void)grad_raw; (void)guv; (void)ws;
-  (void)B; (void)H; (void)W; (void)ep; (void)mask; (void)passes; (void)stream;
-  return r2l_fail(-3, "r2l_isp_step_bwd_select: internal: the serial emulation has no plane passes");
-#else
-  const bool gam = (mask & R2L_GRAD_GAMMA) != 0, blur = (mask & R2L_GRAD_BLUR) != 0;
-  const long nstrip = (W + 255) / 256;
-  auto band_rows = [&](long slots, const char* env) { return r2l_band_rows(B, H, W, slots, env); };
-  R2LBwd1SelArgs sa;
-  R2LBwd1Args& a1 = sa.b;
-  a1.raw = raw;
-  a1.additive = nullptr;
-  a1.F = ws.folded;
-  a1.bn = bn_mean_istd;
-  a1.bn_bwd = bn_bwd;
-  a1.gout = grad_out;
-  a1.gypp = ws.gypp;
-  a1.partial = ws.part_b1;
-  a1.B = B;
-  a1.H = H;
-  a1.W = W;
-  a1.debug = ws.debug + 8 * R2L_MAX_BLOCKS;
-  a1.yp = ws.yp;
-  a1.ep = ep.on ? ep : R2LEpi{0, 0, 0, 0};
-  a1.hp = ws.hp;
-  // persistent workgroups of 4 independent wavefronts, `occ` per CU
-  const int occ = (grad_raw && !gam) ? R2L_BPS_OCC_RAW : R2L_BPS_OCC;
-  a1.band_h = band_rows(256L * 4 * occ, "R2L_BP_BAND");
-  a1.band_hb = band_rows(256L * 4 * R2L_HB_OCC, "R2L_HB_BAND");
-  const long items = (long)B * nstrip * ((H + a1.band_h - 1) / a1.band_h);
-  long g = (items + R2L_BP_NWV - 1) / R2L_BP_NWV;
-  const long cap = r2l_env_int("R2L_GRID_BWD1", 256 * occ);
-  if (g > cap) g = cap;
-  if (g > R2L_MAX_BLOCKS) g = R2L_MAX_BLOCKS;
-  const int g1 = (int)g;
-  sa.guv = guv;
-  sa.s.params = ws.packed;
-  sa.s.grad_params = grad_params;
-  sa.s.blur_follows = blur;
-  // the gamma sum: slot R2L_B1_GGAM of kernel B1's partials, one slot through the shared tree
-  sa.s.tree = R2LTree{ws.part_b1 + (size_t)R2L_B1_GGAM * g1, nullptr, ws.gpartial, ws.counters, 1, 0};
-  int e;
-  if (grad_raw)
-    e = gam ? r2l_launch_bwd1_sel_raw_gamma(sa, g1, stream) : r2l_launch_bwd1_sel_raw(sa, g1, stream);
-  else {
-#define R2L_BPS_PICK(name)                                                                       \
-  (a1.ep.on ? (raw.u16 ? name##_epi_u16(sa, g1, stream) : name##_epi(sa, g1, stream))            \
-            : (raw.u16 ? name##_u16(sa, g1, stream) : name(sa, g1, stream)))
-    e = !blur ? R2L_BPS_PICK(r2l_launch_bwd1_sel_gamma)
-              : (gam ? R2L_BPS_PICK(r2l_launch_bwd1_sel_gypp_gamma) : R2L_BPS_PICK(r2l_launch_bwd1_sel_gypp));
-#undef R2L_BPS_PICK
-  }
-  if (e) return e;
-  if (blur) {  // the 25 sums (and HP, for d/d raw) on kernel B1's grid; its last workgroup writes the blur gradient
-    sa.s.tree = R2LTree{ws.part_b1, nullptr, ws.gpartial, ws.counters, R2L_B1_GAU, 0};
-    if (int eb = (passes & R2L_SELECT_BLUR_HP) ? r2l_launch_bwd1_blur_hp_fin(sa, g1, stream)
-                                               : r2l_launch_bwd1_blur_fin(sa, g1, stream))
-      return eb;
-  }
-  if (!grad_raw) return 0;
-  if (passes & R2L_SELECT_HP) {
-    R2LBwd2Args a2;
-    a2.nmain = 0;
-    a2.b1_partial = nullptr;
-    a2.b1_n = 0;
-    a2.b1_tot = nullptr;
-    a2.raw = raw;
-    a2.F = ws.folded;
-    a2.gypp = ws.gypp;
-    a2.partial = ws.part_b2;
-    a2.B = B;
-    a2.H = H;
-    a2.W = W;
-    a2.debug = ws.debug + 16 * R2L_MAX_BLOCKS;
-    a2.hp = ws.hp;
-    a2.band_h = band_rows(256L * 4 * 4, "R2L_HP_BAND");
-    a2.tree = R2LTree{nullptr, nullptr, nullptr, nullptr, 0, 0};
-    a2.params = nullptr;
-    a2.grad_params = nullptr;
-    const long hitems = (long)B * nstrip * ((H + a2.band_h - 1) / a2.band_h);
-    if (int eh = r2l_launch_bwd2_hp(a2, (int)((hitems + R2L_BP_NWV - 1) / R2L_BP_NWV), stream)) return eh;
-  }
-  R2LRawGradArgs ar{ws.folded, ws.hp, guv, grad_raw, B, H, W, band_rows(256L * 4 * R2L_BR_OCC, "R2L_BR_BAND")};
-  const long ritems = (long)B * nstrip * ((H + ar.band_h - 1) / ar.band_h);
-  if (ritems > (1L << 30)) return r2l_fail(-1, "r2l_isp_step_bwd_raw: batch too large");
-  return r2l_launch_bwd_raw_plane(ar, (int)((ritems + R2L_BR_NWV - 1) / R2L_BR_NWV), stream);
-#endif
+  const R2LBwdCall c{raw, params, additive, bn_mean_istd, bn_bwd, grad_out, grad_params, nullptr, nullptr,
+                     R2LEpi{0, 0, 0, 0}, 0, B, H, W, stream};
+  return r2l_bwd_launch(c, ws, r2l_bwd_plan(0, false, raw.u16 != nullptr, additive != nullptr, false,
+                                            (flags & R2L_F_KEEP_LUMA) != 0, B, H, W));
 }
 
 int r2l_additive_bwd(const float* grad_out, const float* out, const float* bn_mean_istd,
@@ -1330,7 +1271,7 @@ static int r2l_bn_bwd_reduce_planes(const R2LRaw& raw, const float* additive, co
 #else
   // (from 6 Mi px: at 64x256x256 = 4 Mi px the whole step, output included, lives in the memory-side cache and reading the output back
   //  is cheaper than recomputing it -- bn_reduce 22.4-23.8 us against 27.1; at 128x256x256 37.2 against 37.5, the step 2 % faster)
-  const bool planes = r2l_env_int("R2L_BWD_PLANES", 0) || (size_t)B * H * W >= ((size_t)6 << 20);
+  const bool planes = r2l_bwd_planes_forced() || (size_t)B * H * W >= ((size_t)6 << 20);
   if (!keep || !r2l_fwd_streams(additive, W) || !planes) return 1;
   R2LBnrArgs a;
   a.s.raw = raw;
@@ -1349,8 +1290,7 @@ static int r2l_bn_bwd_reduce_planes(const R2LRaw& raw, const float* additive, co
   // (band height as kernel B1's: 36 rows at 64x512x512 -- 61.4 us against 63.2 at 24 rows, 71-73 at 12 / 18 / 30, 68.4 at 48)
   a.s.band_h = r2l_band_rows(B, H, W, 256L * 4 * 2, "R2L_BNR_BAND");
   a.s.nband = (H + a.s.band_h - 1) / a.s.band_h;
-  const long nstrip = (W + 255) / 256;
-  const long items = (long)B * a.s.nband * nstrip;
+  const long items = r2l_plane_items(B, H, W, a.s.band_h);
   if (items > (1L << 30)) return r2l_fail(-1, "r2l_isp_step_bwd: batch too large");
   a.s.nitems = (int)items;
   a.s.tree = R2LTree{ws.part_small, nullptr, ws.gpartial, ws.counters, 12, 0};
@@ -1361,119 +1301,122 @@ static int r2l_bn_bwd_reduce_planes(const R2LRaw& raw, const float* additive, co
   a.sums = ws.bsums;
   a.totals = ws.moments;
   a.bn_bwd = bn_bwd;
-  long g = (items + R2L_BNR_NWV - 1) / R2L_BNR_NWV;
-  const long gcap = r2l_env_int("R2L_GRID_BNR", R2L_MAX_BLOCKS);
-  if (g > gcap) g = gcap;
-  if (g > R2L_MAX_BLOCKS) g = R2L_MAX_BLOCKS;
-  return ep.on ? (raw.u16 ? r2l_launch_bnr_planes_epi_u16(a, (int)g, stream) : r2l_launch_bnr_planes_epi(a, (int)g, stream))
-               : (raw.u16 ? r2l_launch_bnr_planes_u16(a, (int)g, stream) : r2l_launch_bnr_planes(a, (int)g, stream));
+  const int g = r2l_plane_grid(B, H, W, a.s.band_h, R2L_BNR_NWV, r2l_env_int("R2L_GRID_BNR", R2L_MAX_BLOCKS));
+  return ep.on ? (raw.u16 ? r2l_launch_bnr_planes_epi_u16(a, g, stream) : r2l_launch_bnr_planes_epi(a, g, stream))
+               : (raw.u16 ? r2l_launch_bnr_planes_u16(a, g, stream) : r2l_launch_bnr_planes(a, g, stream));
 #endif
 }
 
-static int r2l_isp_step_bwd_impl(const void* raw, int raw_u16, float denom, const float* additive, const float* grad_out,
-                                 const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
-                                 size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
-                                 const double* gathered_sums, void* stream, float* grad_raw = nullptr,
-                                 float* guv = nullptr, unsigned select_mask = 0, int select_passes = R2L_SELECT_FULL) {
-  const int keep = (phase & R2L_STEP_KEEP_LUMA) ? R2L_F_KEEP_LUMA : 0;
+// r2l_isp_step_bwd, r2l_isp_step_bwd_raw and r2l_isp_step_bwd_select: one implementation, what they ask of it
+struct R2LStepBwd {
+  const void* raw;
+  int raw_u16;
+  float denom;
+  const float *additive, *grad_out, *out;
+  float *grad_params, *grad_additive;
+  int bn_mode;
+  void* workspace;
+  size_t workspace_bytes;
+  int B, H, W, nranks, phase;
+  const double* gathered_sums;
+  void* stream;
+  float *grad_raw, *guv;  // d/d raw and its scratch (the chroma gradient planes), or null
+  unsigned grad_mask;     // R2L_GRAD_* bits (r2l_isp_step_bwd_select), 0 = every parameter gradient
+};
+static int r2l_isp_step_bwd_impl(const R2LStepBwd& q) {
+  const int B = q.B, H = q.H, W = q.W;
+  const int keep = (q.phase & R2L_STEP_KEEP_LUMA) ? R2L_F_KEEP_LUMA : 0;
   R2LEpi ep;
   if (int e = r2l_check_dims(B, H, W)) return e;
-  if (int e = r2l_epi_from_phase(phase, H, W, ep)) return e;
-  phase &= ~(R2L_STEP_KEEP_LUMA | R2L_STEP_EPI_MASK);
-  if (ep.on && grad_additive) return r2l_fail(-3, "r2l_isp_step_bwd: no output epilogue with an additive layer");
-  if (!raw || !grad_out || !workspace) return r2l_fail(-1, "r2l_isp_step_bwd: null pointer");
+  if (int e = r2l_epi_from_phase(q.phase, H, W, ep)) return e;
+  const int phase = q.phase & ~(R2L_STEP_KEEP_LUMA | R2L_STEP_EPI_MASK);
+  if (ep.on && q.grad_additive) return r2l_fail(-3, "r2l_isp_step_bwd: no output epilogue with an additive layer");
+  if (!q.raw || !q.grad_out || !q.workspace) return r2l_fail(-1, "r2l_isp_step_bwd: null pointer");
   if (phase != R2L_STEP_ALL && phase != R2L_STEP_A && phase != R2L_STEP_B)
     return r2l_fail(-1, "r2l_isp_step_bwd: unknown phase");
-  if (nranks < 1 || (nranks > 1 && phase == R2L_STEP_ALL && bn_mode == R2L_BN_TRAIN))
+  if (q.nranks < 1 || (q.nranks > 1 && phase == R2L_STEP_ALL && q.bn_mode == R2L_BN_TRAIN))
     return r2l_fail(-1, "r2l_isp_step_bwd: several ranks exchange the BatchNorm sums between phase A and phase B");
-  if (phase != R2L_STEP_ALL && bn_mode != R2L_BN_TRAIN)
+  if (phase != R2L_STEP_ALL && q.bn_mode != R2L_BN_TRAIN)
     return r2l_fail(-1, "r2l_isp_step_bwd: only train-mode BatchNorm has two phases");
-  if (phase == R2L_STEP_B && !gathered_sums) return r2l_fail(-1, "r2l_isp_step_bwd: phase B needs the gathered sums");
-  if (bn_mode == R2L_BN_TRAIN && !out) return r2l_fail(-1, "r2l_isp_step_bwd: train-mode BatchNorm needs the saved output");
-  const R2LRaw rw = r2l_raw_any(raw, raw_u16, denom);
-  // (before ANY launch: the recomputing BatchNorm sums below read the raw frames, r2l_isp_bwd_impl's own check comes later)
+  if (phase == R2L_STEP_B && !q.gathered_sums) return r2l_fail(-1, "r2l_isp_step_bwd: phase B needs the gathered sums");
+  if (q.bn_mode == R2L_BN_TRAIN && !q.out) return r2l_fail(-1, "r2l_isp_step_bwd: train-mode BatchNorm needs the saved output");
+  const R2LRaw rw = r2l_raw_any(q.raw, q.raw_u16, q.denom);
+  // (before ANY launch: the recomputing BatchNorm sums below read the raw frames)
   if (int e = r2l_check_raw(rw, W, "r2l_isp_step_bwd")) return e;
-  const R2LWorkspace ws = r2l_carve(workspace, B, H, W);
-  if (workspace_bytes < ws.total) return r2l_fail(-2, "r2l_isp_step_bwd: workspace too small (r2l_isp_workspace_bytes)");
-  const float* bn = bn_mode == R2L_BN_NONE ? nullptr : ws.bn;
-  const float* bn_bwd = bn_mode == R2L_BN_TRAIN ? ws.bn_bwd : nullptr;
-  if (bn_mode == R2L_BN_TRAIN && phase != R2L_STEP_B) {
+  const R2LWorkspace ws = r2l_carve(q.workspace, B, H, W);
+  if (q.workspace_bytes < ws.total) return r2l_fail(-2, "r2l_isp_step_bwd: workspace too small (r2l_isp_workspace_bytes)");
+  const float* bn = q.bn_mode == R2L_BN_NONE ? nullptr : ws.bn;
+  const float* bn_bwd = q.bn_mode == R2L_BN_TRAIN ? ws.bn_bwd : nullptr;
+  if (q.bn_mode == R2L_BN_TRAIN && phase != R2L_STEP_B) {
     float* means = phase == R2L_STEP_ALL ? ws.bn_bwd : nullptr;
-    int e = r2l_bn_bwd_reduce_planes(rw, additive, grad_out, ws, ep, means, B, H, W, keep, stream);
-    if (e == 1) e = r2l_bn_bwd_reduce(grad_out, out, ws.moments, ws.bsums, means, workspace, workspace_bytes, B, H, W,
-                                      R2L_F_FOLDED_VALID, stream);
+    int e = r2l_bn_bwd_reduce_planes(rw, q.additive, q.grad_out, ws, ep, means, B, H, W, keep, q.stream);
+    if (e == 1) e = r2l_bn_bwd_reduce(q.grad_out, q.out, ws.moments, ws.bsums, means, q.workspace, q.workspace_bytes, B, H, W,
+                                      R2L_F_FOLDED_VALID, q.stream);
     if (e) return e;
     if (phase == R2L_STEP_A) return 0;
   }
   if (phase == R2L_STEP_B) {
-    R2LBnBwdMeansArgs m{gathered_sums, nranks, ws.moments + 6, ws.bn_bwd};
-    if (int e = r2l_launch_bn_bwd_means(m, 1, stream)) return e;
+    R2LBnBwdMeansArgs m{q.gathered_sums, q.nranks, ws.moments + 6, ws.bn_bwd};
+    if (int e = r2l_launch_bn_bwd_means(m, 1, q.stream)) return e;
   }
-  if (grad_params && select_passes != R2L_SELECT_FULL) {  // (r2l_isp_step_bwd_select: the passes of the asked gradients only)
-    if (int e = r2l_isp_bwd_select(rw, bn, bn_bwd, grad_out, grad_params, grad_raw, guv, ws, B, H, W, ep, select_mask,
-                                   select_passes, stream))
-      return e;
-  } else if (grad_params) {
-    if (int e = r2l_isp_bwd_impl(rw, ws.packed, additive, bn, bn_bwd, grad_out, grad_params, grad_raw, workspace,
-                                 workspace_bytes, B, H, W, R2L_F_FOLDED_VALID | keep, stream, &ep, guv))
-      return e;
+  if (q.grad_params) {  // the step's forward has folded the parameters (and kept Y', with R2L_STEP_KEEP_LUMA)
+    if (q.additive && (H != 256 || W != 256))
+      return r2l_fail(-1, "additive_layer is (1,3,256,256): needs 256x256 frames");
+    const R2LBwdCall c{rw, ws.packed, q.additive, bn, bn_bwd, q.grad_out, q.grad_params, q.grad_raw, q.guv, ep, q.grad_mask,
+                       B, H, W, q.stream};
+    const R2LBwdPlan p = r2l_bwd_plan(q.grad_mask, q.grad_raw != nullptr, q.raw_u16, q.additive != nullptr, ep.on != 0,
+                                      keep != 0, B, H, W);
+    if (int e = r2l_bwd_launch(c, ws, p)) return e;
   }
-  if (grad_additive) return r2l_additive_bwd(grad_out, out, bn, bn_bwd, grad_additive, B, H, W, stream);
+  if (q.grad_additive) return r2l_additive_bwd(q.grad_out, q.out, bn, bn_bwd, q.grad_additive, B, H, W, q.stream);
   return 0;
-}
-int r2l_isp_step_bwd(const void* raw, int raw_u16, float denom, const float* additive, const float* grad_out,
-                     const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
-                     size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
-                     const double* gathered_sums, void* stream) {
-  return r2l_isp_step_bwd_impl(raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode, workspace,
-                               workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream);
 }
 size_t r2l_isp_raw_grad_scratch_bytes(int B, int H, int W) {
   if (B < 1 || H < 1 || W < 1) return 0;
   return (size_t)2 * B * H * W * sizeof(float);  // gU, gV
 }
 // what d/d raw needs of a call (r2l_isp_step_bwd_raw, r2l_isp_step_bwd_select): 0, or the error
-static int r2l_raw_grad_preconditions(int raw_u16, const float* additive, const float* grad_params, const float* grad_raw,
-                                      const void* raw_grad_scratch, size_t raw_grad_scratch_bytes, int B, int H, int W,
-                                      int phase) {
-#ifdef R2L_SERIAL
-  (void)raw_u16; (void)additive; (void)grad_params; (void)grad_raw; (void)raw_grad_scratch; (void)raw_grad_scratch_bytes;
-  (void)B; (void)H; (void)W; (void)phase;
-  return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw needs the plane passes, which the serial emulation does not have");
-#else
-  if (int e = r2l_check_dims(B, H, W)) return e;
-  if (raw_u16) return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw needs float32 frames (16-bit containers have no gradient)");
-  if (additive) return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw is not produced with an additive layer");
-  if ((W & 3) || W > 2048) return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw needs W % 4 == 0 and W <= 2048");
+static int r2l_raw_grad_preconditions(const R2LStepBwd& q, size_t raw_grad_scratch_bytes) {
+  if (!R2L_PLANE_PASSES)
+    return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw needs the plane passes, which the serial emulation does not have");
+  if (int e = r2l_check_dims(q.B, q.H, q.W)) return e;
+  if (q.raw_u16) return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw needs float32 frames (16-bit containers have no gradient)");
+  if (q.additive) return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw is not produced with an additive layer");
+  if ((q.W & 3) || q.W > 2048) return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw needs W % 4 == 0 and W <= 2048");
   if (r2l_env_int("R2L_FWD_TILED", 0))
     return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw needs the row-streaming forward (R2L_FWD_TILED is set)");
-  if (phase & R2L_STEP_EPI_MASK) return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw is not produced with an output epilogue");
-  if (!(phase & R2L_STEP_KEEP_LUMA))
+  if (q.phase & R2L_STEP_EPI_MASK) return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw is not produced with an output epilogue");
+  if (!(q.phase & R2L_STEP_KEEP_LUMA))
     return r2l_fail(-3, "r2l_isp_step_bwd_raw: grad_raw needs a forward that kept Y' (R2L_STEP_KEEP_LUMA in both calls)");
-  if (!grad_params) return r2l_fail(-1, "r2l_isp_step_bwd_raw: grad_raw needs grad_params (the parameter sums run with it)");
-  if (!raw_grad_scratch) return r2l_fail(-1, "r2l_isp_step_bwd_raw: null raw_grad_scratch");
-  if (raw_grad_scratch_bytes < r2l_isp_raw_grad_scratch_bytes(B, H, W))
+  if (!q.grad_params) return r2l_fail(-1, "r2l_isp_step_bwd_raw: grad_raw needs grad_params (the parameter sums run with it)");
+  if (!q.guv) return r2l_fail(-1, "r2l_isp_step_bwd_raw: null raw_grad_scratch");
+  if (raw_grad_scratch_bytes < r2l_isp_raw_grad_scratch_bytes(q.B, q.H, q.W))
     return r2l_fail(-2, "r2l_isp_step_bwd_raw: raw_grad_scratch too small (r2l_isp_raw_grad_scratch_bytes)");
-  if ((uintptr_t)raw_grad_scratch % 16 || (uintptr_t)grad_raw % 16)
+  if ((uintptr_t)q.guv % 16 || (uintptr_t)q.grad_raw % 16)
     return r2l_fail(-1, "r2l_isp_step_bwd_raw: grad_raw and raw_grad_scratch must be 16-byte aligned");
   return 0;
-#endif
+}
+int r2l_isp_step_bwd(const void* raw, int raw_u16, float denom, const float* additive, const float* grad_out,
+                     const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
+                     size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                     const double* gathered_sums, void* stream) {
+  return r2l_isp_step_bwd_impl(R2LStepBwd{raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode,
+                                          workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, nullptr,
+                                          nullptr, 0});
 }
 int r2l_isp_step_bwd_raw(const void* raw, int raw_u16, float denom, const float* additive, const float* grad_out,
                          const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
                          size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
                          const double* gathered_sums, void* stream, float* grad_raw, void* raw_grad_scratch,
                          size_t raw_grad_scratch_bytes) {
-  if (!grad_raw)
-    return r2l_isp_step_bwd_impl(raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode,
-                                 workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream);
-  if (int e = r2l_raw_grad_preconditions(raw_u16, additive, grad_params, grad_raw, raw_grad_scratch, raw_grad_scratch_bytes,
-                                         B, H, W, phase))
-    return e;
+  // (without grad_raw: r2l_isp_step_bwd, the scratch is not looked at)
+  const R2LStepBwd q{raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode, workspace,
+                     workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw,
+                     grad_raw ? (float*)raw_grad_scratch : nullptr, 0};
+  if (grad_raw)
+    if (int e = r2l_raw_grad_preconditions(q, raw_grad_scratch_bytes)) return e;
   // (phase A computes the BatchNorm sums only: the gradient kernels, and with them d/d raw, run in phase B / ALL)
-  return r2l_isp_step_bwd_impl(raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode, workspace,
-                               workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw,
-                               (float*)raw_grad_scratch);
+  return r2l_isp_step_bwd_impl(q);
 }
 int r2l_isp_step_bwd_select(const void* raw, int raw_u16, float denom, const float* additive, const float* grad_out,
                             const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
@@ -1485,16 +1428,13 @@ int r2l_isp_step_bwd_select(const void* raw, int raw_u16, float denom, const flo
   if ((grad_raw != nullptr) != ((grad_mask & R2L_GRAD_RAW) != 0))
     return r2l_fail(-1, "r2l_isp_step_bwd_select: grad_raw goes with R2L_GRAD_RAW in grad_mask");
   if (grad_mask && !grad_params) return r2l_fail(-1, "r2l_isp_step_bwd_select: a gradient is asked for but grad_params is null");
+  const R2LStepBwd q{raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode, workspace,
+                     workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw, (float*)raw_grad_scratch,
+                     grad_mask};
   if (grad_raw)
-    if (int e = r2l_raw_grad_preconditions(raw_u16, additive, grad_params, grad_raw, raw_grad_scratch,
-                                           raw_grad_scratch_bytes, B, H, W, phase))
-      return e;
-  // a mask without a reduced route: exactly r2l_isp_step_bwd / r2l_isp_step_bwd_raw
-  const int passes = (B < 1 || H < 1 || W < 1) ? R2L_SELECT_FULL
-                                               : r2l_select_route(grad_mask, raw_u16, additive != nullptr, B, H, W, phase);
-  return r2l_isp_step_bwd_impl(raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode, workspace,
-                               workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw,
-                               (float*)raw_grad_scratch, grad_mask, passes);
+    if (int e = r2l_raw_grad_preconditions(q, raw_grad_scratch_bytes)) return e;
+  // (a mask without a reduced route runs exactly r2l_isp_step_bwd / r2l_isp_step_bwd_raw: r2l_bwd_plan)
+  return r2l_isp_step_bwd_impl(q);
 }
 
 static int r2l_raw2rgb_fwd_impl(const R2LRaw& raw, const float* black_level, float* out, int B, int H, int W,
