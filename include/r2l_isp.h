@@ -397,6 +397,44 @@ int r2l_augment_strong_bwd(const float *grad_y, float *grad_x, const unsigned ch
                            int H, int W, int hflip, int vflip, int rotate, float txx, float txy, float tyx, float tyy,
                            double sharpness, void *stream);
 
+/* ---- common corruptions of the ISP output (utils/hendrycks_robustness.py: Distortions, the C-testing sweep of
+ * figures/ABtesting.py; evaluation only, no backward).  x, y: (N,3,H,W) float32 on the device, y != x.  `kind` picks the
+ * transform; its numbers are launch arguments, params_host = double[nparams] in host memory:
+ *   IDENTITY        -                       y = x (useful with mean / std only)
+ *   GAUSSIAN_NOISE  [c]                     clip(x + c n), n = r2l_add_noise_philox's deviate of (noise_key, noise_offset, i)
+ *   SPECKLE_NOISE   [c]                     clip(x + x (c n)), the same n
+ *   IMPULSE_NOISE   [c]                     scikit-image 0.18 random_noise('s&p', amount=c): every element flips with
+ *                                           probability c to 1 or 0 (1/2 each; two different Philox outputs), else clip(x)
+ *   SHOT_NOISE      [c]                     clip(Poisson(max(x, 0) c) / c): exact samplers (inversion below lambda = 10,
+ *                                           PTRS above), every element on a Philox sub-sequence of its own
+ *   GAUSSIAN_BLUR   [w0, w1, .. wr]         scipy.ndimage.gaussian_filter over H and W, mode='nearest': the radius r <= 4 and
+ *                                           the taps w|t| (centre first) as scipy computes them in float64; clip
+ *   ZOOM_BLUR       nf x [ch, top, out_size, trim_top, scale]   per zoom factor: the centred crop of ch pixels from `top`,
+ *                                           scipy.ndimage.zoom(order=1) to out_size (scale = (ch - 1) / (out_size - 1)), trimmed
+ *                                           from trim_top; clip((x + sum) / (nf + 1)); nf <= 32; H == W (the reference indexes
+ *                                           both axes with the height)
+ *   CONTRAST        [c]                     clip((x - m) c + m), m = the mean of the pixel's own plane (a fixed-order float64
+ *                                           reduction into the workspace; no atomics)
+ *   BRIGHTNESS      [c]                     scikit-image 0.18 rgb2hsv, V <- clip(V + c), hsv2rgb, clip
+ *   SATURATE        [c0, c1]                ... S <- clip(S c0 + c1) ...
+ * (clip = to [0, 1].)  mean3 / std3: float[3] in host memory or both NULL; given, the stores write (y - mean[c]) / std[c],
+ * the T.Normalize that follows Distortions in the reference's Compose.  The random kinds are pure functions of (noise_key,
+ * noise_offset, flat element index over the batch): same distribution as the reference's numpy draws, not the same stream.
+ * No result depends on the launch shape.  Errors: R2L_CORRUPT_E_* with the reason in r2l_last_error().                    */
+enum { R2L_CORRUPT_IDENTITY = 0, R2L_CORRUPT_GAUSSIAN_NOISE = 1, R2L_CORRUPT_SHOT_NOISE = 2, R2L_CORRUPT_IMPULSE_NOISE = 3,
+       R2L_CORRUPT_SPECKLE_NOISE = 4, R2L_CORRUPT_GAUSSIAN_BLUR = 5, R2L_CORRUPT_ZOOM_BLUR = 6, R2L_CORRUPT_CONTRAST = 7,
+       R2L_CORRUPT_BRIGHTNESS = 8, R2L_CORRUPT_SATURATE = 9, R2L_CORRUPT_KINDS = 10 };
+enum { R2L_CORRUPT_E_ARGS = -1,       /* null pointer, y == x, bad dimensions */
+       R2L_CORRUPT_E_WORKSPACE = -2,  /* workspace null or smaller than r2l_corrupt_workspace_bytes() */
+       R2L_CORRUPT_E_PARAMS = -4,     /* wrong count or value of the kind's numbers */
+       R2L_CORRUPT_E_KIND = -5,       /* kind outside the enum */
+       R2L_CORRUPT_E_CHANNELS = -6,   /* C != 3 */
+       R2L_CORRUPT_E_NOT_SQUARE = -7  /* ZOOM_BLUR with H != W */ };
+size_t r2l_corrupt_workspace_bytes(int kind, int N, int C, int H, int W);
+int r2l_corrupt(const float *x, float *y, int N, int C, int H, int W, int kind, const double *params_host, int nparams,
+                unsigned long long noise_key, unsigned long long noise_offset, const float *mean3, const float *std3,
+                void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- adversarial auxiliary losses between the outputs of two processors (SURVEY.md section 8f rank 2;
  * AuxLoss, utils/base.py:346-358: img1 = the default processor's output, img2 = the adversarial processor's).
  *   r2l_ssim_fwd   mean of the SSIM map, window_size 11, sigma 1.5, zero padding, per channel

@@ -105,6 +105,11 @@ _SIGNATURES = {
                                                        ctypes.c_void_p]),
     'r2l_augment_strong_bwd': (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_void_p, _c_float_p] + [ctypes.c_int] * 7 +
                                [ctypes.c_float] * 4 + [ctypes.c_double, ctypes.c_void_p]),
+    'r2l_corrupt_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 5),
+    'r2l_corrupt': (ctypes.c_int, [_c_float_p, _c_float_p] + [ctypes.c_int] * 5 +
+                    [ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
+                     ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_size_t,
+                     ctypes.c_void_p]),
     'r2l_aux_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4),
     'r2l_ssim_fwd': (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t] +
                      [ctypes.c_int] * 5 + [ctypes.c_void_p]),

@@ -24,6 +24,7 @@
 #include "r2l_staged_kernels.h"
 #include "r2l_aux_kernels.h"
 #include "r2l_augment_strong.h"
+#include "r2l_corruptions.h"
 
 static thread_local std::string r2l_err;
 static int r2l_fail(int code, const std::string& msg) {
@@ -444,6 +445,17 @@ R2L_KERNEL(r2l_launch_strong_fwd_flat, R2LStrongArgs, r2l_strong_fwd_flat_block,
 R2L_KERNEL(r2l_launch_strong_fwd_sharp, R2LStrongArgs, r2l_strong_fwd_sharp_block, R2L_AUGS_LDS_FLOATS)
 R2L_KERNEL(r2l_launch_strong_bwd_sharp, R2LStrongBwdArgs, r2l_strong_bwd_sharp_block, 4)
 R2L_KERNEL(r2l_launch_strong_bwd_rot, R2LStrongBwdArgs, r2l_strong_bwd_rot_block, 4)
+R2L_KERNEL(r2l_launch_corrupt_identity, R2LCorruptArgs, r2l_corrupt_point_block<R2L_CORRUPT_IDENTITY>, 4)
+R2L_KERNEL(r2l_launch_corrupt_gaussian_noise, R2LCorruptArgs, r2l_corrupt_point_block<R2L_CORRUPT_GAUSSIAN_NOISE>, 4)
+R2L_KERNEL(r2l_launch_corrupt_shot_noise, R2LCorruptArgs, r2l_corrupt_point_block<R2L_CORRUPT_SHOT_NOISE>, 4)
+R2L_KERNEL(r2l_launch_corrupt_impulse_noise, R2LCorruptArgs, r2l_corrupt_point_block<R2L_CORRUPT_IMPULSE_NOISE>, 4)
+R2L_KERNEL(r2l_launch_corrupt_speckle_noise, R2LCorruptArgs, r2l_corrupt_point_block<R2L_CORRUPT_SPECKLE_NOISE>, 4)
+R2L_KERNEL(r2l_launch_corrupt_contrast, R2LCorruptArgs, r2l_corrupt_point_block<R2L_CORRUPT_CONTRAST>, 4)
+R2L_KERNEL(r2l_launch_corrupt_brightness, R2LCorruptArgs, r2l_corrupt_point_block<R2L_CORRUPT_BRIGHTNESS>, 4)
+R2L_KERNEL(r2l_launch_corrupt_saturate, R2LCorruptArgs, r2l_corrupt_point_block<R2L_CORRUPT_SATURATE>, 4)
+R2L_KERNEL(r2l_launch_corrupt_mean, R2LCorruptArgs, r2l_corrupt_mean_block, R2L_CMEAN_LDS_FLOATS)
+R2L_KERNEL(r2l_launch_corrupt_blur, R2LCorruptArgs, r2l_corrupt_blur_block, R2L_CBLUR_LDS_FLOATS)
+R2L_KERNEL(r2l_launch_corrupt_zoom, R2LCorruptZoomArgs, r2l_corrupt_zoom_block, 4)
 R2L_KERNEL(r2l_launch_ssim, R2LSsimArgs, r2l_ssim_block, R2L_SSIM_LDS_FLOATS)
 R2L_KERNEL(r2l_launch_ssim_bwd, R2LSsimBwdArgs, r2l_ssim_bwd_block, R2L_SSIM_BWD_LDS_FLOATS)
 R2L_KERNEL(r2l_launch_l2, R2LL2Args, r2l_l2_block, R2L_RED_FLOATS_N(1))
@@ -2260,6 +2272,128 @@ int r2l_augment_strong_bwd(const float* grad_y, float* grad_x, const unsigned ch
   return r2l_launch_strong_bwd_rot(a, grid, stream);
 }
 
+// ---- common corruptions (utils/hendrycks_robustness.py: Distortions; r2l_corruptions.h) ----------------------------
+static_assert(R2L_NT == (R2L_CBLUR_TW / 4) * R2L_CBLUR_TH, "one lane per 4 output pixels of the blur tile");
+static const char* const r2l_corrupt_names[R2L_CORRUPT_KINDS] = {"identity",      "gaussian_noise", "shot_noise", "impulse_noise",
+                                                                "speckle_noise", "gaussian_blur",  "zoom_blur",  "contrast",
+                                                                "brightness",    "saturate"};
+size_t r2l_corrupt_workspace_bytes(int kind, int N, int C, int H, int W) {
+  if (kind != R2L_CORRUPT_CONTRAST || N < 1 || C != 3 || H < 1 || W < 1) return 0;
+  return r2l_align_up(sizeof(float) * 3 * (size_t)N);
+}
+// workgroups of a pass over `items` work items of one lane each (diagnostic builds: R2L_GRID_CORRUPT)
+static int r2l_corrupt_grid(size_t items, size_t per_block, size_t cap) {
+  size_t n = (items + per_block - 1) / per_block;
+  if (n > cap) n = cap;
+  return r2l_env_int("R2L_GRID_CORRUPT", (int)(n < 1 ? 1 : n));
+}
+int r2l_corrupt(const float* x, float* y, int N, int C, int H, int W, int kind, const double* params_host, int nparams,
+                unsigned long long noise_key, unsigned long long noise_offset, const float* mean3, const float* std3,
+                void* workspace, size_t workspace_bytes, void* stream) {
+  const std::string who = "r2l_corrupt";
+  if (kind < 0 || kind >= R2L_CORRUPT_KINDS)
+    return r2l_fail(R2L_CORRUPT_E_KIND, who + ": unknown kind " + std::to_string(kind));
+  const std::string what = who + "(" + r2l_corrupt_names[kind] + ")";
+  if (!x || !y || x == y) return r2l_fail(R2L_CORRUPT_E_ARGS, what + ": null pointer, or y aliases x");
+  if (C != 3) return r2l_fail(R2L_CORRUPT_E_CHANNELS, what + ": needs 3 channels (RGB), got C = " + std::to_string(C));
+  if (N < 1 || H < 1 || W < 1 || (size_t)H * W > ((size_t)1 << 29) || (size_t)N * 3 * H * W >= ((size_t)1 << 40))
+    return r2l_fail(R2L_CORRUPT_E_ARGS, what + ": bad dimensions");
+  if ((mean3 == nullptr) != (std3 == nullptr)) return r2l_fail(R2L_CORRUPT_E_ARGS, what + ": mean3 and std3 go together");
+  if (nparams < 0 || (nparams > 0 && !params_host)) return r2l_fail(R2L_CORRUPT_E_PARAMS, what + ": params_host is null");
+  for (int k = 0; k < nparams; ++k)
+    if (!isfinite(params_host[k])) return r2l_fail(R2L_CORRUPT_E_PARAMS, what + ": non-finite parameter");
+  R2LCorruptIO io;
+  io.x = x;
+  io.y = y;
+  io.N = N;
+  io.H = H;
+  io.W = W;
+  io.norm = mean3 != nullptr;
+  for (int c = 0; c < 3; ++c) {
+    io.mean[c] = mean3 ? mean3[c] : 0.0f;
+    io.std[c] = std3 ? std3[c] : 1.0f;
+  }
+  const size_t chunks = (size_t)N * H * ((W + 3) / 4);  // 4 pixels of a row, three channels
+  if (kind == R2L_CORRUPT_ZOOM_BLUR) {
+    if (H != W)
+      return r2l_fail(R2L_CORRUPT_E_NOT_SQUARE, what + ": needs square frames (the reference crops both axes by the height), got " +
+                                                    std::to_string(H) + " x " + std::to_string(W));
+    if (nparams < 5 || nparams % 5 || nparams / 5 > R2L_CZOOM_MAXF)
+      return r2l_fail(R2L_CORRUPT_E_PARAMS, what + ": 5 numbers per zoom factor, 1 to " + std::to_string(R2L_CZOOM_MAXF) + " factors");
+    R2LCorruptZoomArgs z;
+    z.io = io;
+    z.nf = nparams / 5;
+    z.denom = (float)(z.nf + 1);
+    for (int f = 0; f < R2L_CZOOM_MAXF; ++f) {
+      if (f >= z.nf) {
+        z.ch[f] = 1;
+        z.top[f] = z.trim[f] = 0;
+        z.scale[f] = 0.0;
+        continue;
+      }
+      const double* p = params_host + 5 * f;
+      const long ch = (long)p[0], top = (long)p[1], out = (long)p[2], trim = (long)p[3];
+      const double sc = p[4];
+      // the crop lies in the frame, the trimmed window in the zoomed crop, and the largest coordinate at most one step past the crop
+      if (ch < 1 || top < 0 || top + ch > H || out < H || trim < 0 || trim + H > out || sc < 0.0 ||
+          (double)(out - 1) * sc > (double)ch)
+        return r2l_fail(R2L_CORRUPT_E_PARAMS, what + ": zoom factor " + std::to_string(f) + " does not fit the frame");
+      z.ch[f] = (int)ch;
+      z.top[f] = (int)top;
+      z.trim[f] = (int)trim;
+      z.scale[f] = sc;
+    }
+    return r2l_launch_corrupt_zoom(z, r2l_corrupt_grid(3 * chunks, R2L_NT, 8192), stream);
+  }
+  R2LCorruptArgs a;
+  memset(&a, 0, sizeof(a));
+  a.io = io;
+  a.seed = noise_key;
+  a.offset = noise_offset;
+  if (kind == R2L_CORRUPT_GAUSSIAN_BLUR) {
+    if (nparams < 1 || nparams > R2L_CBLUR_R + 1)
+      return r2l_fail(R2L_CORRUPT_E_PARAMS, what + ": 1 to " + std::to_string(R2L_CBLUR_R + 1) + " taps (radius <= " +
+                                                std::to_string(R2L_CBLUR_R) + ")");
+    a.radius = nparams - 1;
+    for (int k = 0; k < nparams; ++k) a.taps[k] = (float)params_host[k];
+    const size_t ntiles = (size_t)N * 3 * ((H + R2L_CBLUR_TH - 1) / R2L_CBLUR_TH) * ((W + R2L_CBLUR_TW - 1) / R2L_CBLUR_TW);
+    return r2l_launch_corrupt_blur(a, r2l_corrupt_grid(ntiles, 1, 8192), stream);
+  }
+  const int want = kind == R2L_CORRUPT_IDENTITY ? 0 : (kind == R2L_CORRUPT_SATURATE ? 2 : 1);
+  if (nparams != want) return r2l_fail(R2L_CORRUPT_E_PARAMS, what + ": takes " + std::to_string(want) + " parameter(s)");
+  a.c0 = want > 0 ? (float)params_host[0] : 0.0f;
+  a.c1 = want > 1 ? (float)params_host[1] : 0.0f;
+  const int grid = r2l_corrupt_grid(chunks, R2L_NT, 8192);
+  switch (kind) {
+    case R2L_CORRUPT_IDENTITY:
+      return r2l_launch_corrupt_identity(a, grid, stream);
+    case R2L_CORRUPT_GAUSSIAN_NOISE:
+      return r2l_launch_corrupt_gaussian_noise(a, grid, stream);
+    case R2L_CORRUPT_SPECKLE_NOISE:
+      return r2l_launch_corrupt_speckle_noise(a, grid, stream);
+    case R2L_CORRUPT_SHOT_NOISE:
+      if (!(params_host[0] > 0.0)) return r2l_fail(R2L_CORRUPT_E_PARAMS, what + ": c must be positive");
+      return r2l_launch_corrupt_shot_noise(a, grid, stream);
+    case R2L_CORRUPT_IMPULSE_NOISE: {
+      const double c = params_host[0];
+      if (c < 0.0 || c > 1.0) return r2l_fail(R2L_CORRUPT_E_PARAMS, what + ": the amount is a probability");
+      const double t = c * 4294967296.0 + 0.5;
+      a.thresh = t >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)t;
+      return r2l_launch_corrupt_impulse_noise(a, grid, stream);
+    }
+    case R2L_CORRUPT_BRIGHTNESS:
+      return r2l_launch_corrupt_brightness(a, grid, stream);
+    case R2L_CORRUPT_SATURATE:
+      return r2l_launch_corrupt_saturate(a, grid, stream);
+    default:  // R2L_CORRUPT_CONTRAST: the plane means into the workspace, then the apply pass
+      if (!workspace || workspace_bytes < r2l_corrupt_workspace_bytes(kind, N, C, H, W))
+        return r2l_fail(R2L_CORRUPT_E_WORKSPACE, what + ": workspace null or smaller than r2l_corrupt_workspace_bytes()");
+      a.means = (float*)workspace;
+      if (int e = r2l_launch_corrupt_mean(a, r2l_corrupt_grid((size_t)N * 3, 1, R2L_MAX_BLOCKS), stream)) return e;
+      return r2l_launch_corrupt_contrast(a, grid, stream);
+  }
+}
+
 // ---- adversarial auxiliary losses (utils/ssim.py, utils/base.py:342-358) -------------------------------
 static void r2l_ssim_gauss(float* g) {  // utils/ssim.py:9-11, float32 like torch.Tensor([...]) / sum
   float w[R2L_SSIM_K], sum = 0.f;
@@ -2368,6 +2502,14 @@ size_t r2l_test_debug_offset(int B, int H, int W) {
   return (size_t)((char*)ws.debug - (char*)0);
 }
 #ifdef R2L_EMUL
+// the Poisson sampler of shot_noise on chosen Philox outputs (tests feed it the smallest and the largest): below lambda = 10 the
+// inversion walk's k from `ou`; from 10 on one PTRS candidate from (ou, ov): its k when accepted, else -1
+float r2l_test_corrupt_poisson(float lam, unsigned ou, unsigned ov) {
+  if (!(lam > 0.0f)) return 0.0f;
+  if (lam < 10.0f) return r2l_corrupt_poisson_walk(lam, ou);
+  float k;
+  return r2l_corrupt_ptrs_try(r2l_corrupt_ptrs_setup(lam), ou, ov, k) ? k : -1.0f;
+}
 // the tile walk of the persistent kernels, replayed on the host: owner[tile] = workgroup id that visits it (or -1), and
 // the number of visits per tile in visits[tile]; returns the largest number of tiles any workgroup takes
 int r2l_test_tile_walk(int B, int H, int W, int nblk, int* owner, int* visits) {
