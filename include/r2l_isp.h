@@ -256,6 +256,37 @@ int r2l_isp_step_bwd_select(const void *raw, int raw_u16, float denom, const flo
                             const double *gathered_sums, void *stream, float *grad_raw, void *raw_grad_scratch,
                             size_t raw_grad_scratch_bytes, unsigned grad_mask);
 
+/* ---- 16-bit output and cotangent (mixed-precision callers: torch.autocast, precision=16 / bf16) --------------------------------
+ * r2l_isp_step_fwd_io = r2l_isp_step_fwd that writes `out` as bfloat16 (io = R2L_IO_BF16) or IEEE float16 (io = R2L_IO_F16):
+ * every element is the float32 value r2l_isp_step_fwd writes, rounded to nearest even -- bit for bit what
+ * torch.Tensor.to(dtype) makes of it.  r2l_isp_step_bwd_io = r2l_isp_step_bwd_select (r2l_isp_step_bwd_raw, r2l_isp_step_bwd)
+ * that reads `grad_out` in that type, widened exactly where it is used.  The arithmetic between is float32, unchanged: the
+ * BatchNorm statistics, the backward sums and the gradients are those of the float32 calls given the widened cotangent, on
+ * the plane passes, which a 16-bit backward takes at every size (as r2l_isp_step_bwd_raw does).  Only the two tensors that cross
+ * the boundary change width: 6 instead of 12 bytes per pixel written by the forward and read -- twice under train-mode
+ * BatchNorm -- by the backward.  io = R2L_IO_F32: exactly r2l_isp_step_fwd resp. r2l_isp_step_bwd_select, no further condition.
+ * A 16-bit call is served where ALL of these hold (r2l_isp_io_supported: 1 or 0, the predicate both calls use):
+ *   no additive layer; W % 4 == 0 and W <= 2048 (the row-streaming forward); no output epilogue (R2L_STEP_EPI_* clear);
+ *   R2L_STEP_KEEP_LUMA set in `phase` of both calls; a device build or the lock-step emulation.
+ * Anything else returns -3 with the reason in r2l_last_error(), as does the serial emulation build (no streaming forward);
+ * an io outside R2L_IO_* returns -1.  `out` and `grad_out` must be 8-byte aligned (a lane moves 4 pixels of a channel as one
+ * 8-byte access; -1 otherwise); `out` of r2l_isp_step_bwd_io is not read on a 16-bit call and may be NULL; grad_additive must be
+ * NULL.  BatchNorm none / train / eval, phases A / B with several ranks and d/d raw (its preconditions: r2l_isp_step_bwd_raw)
+ * work as in the float32 calls.  grad_mask: whatever it selects, a 16-bit call runs the full route (R2L_SELECT_FULL) and fills
+ * all of grad_params; grad_raw must be non-NULL exactly when R2L_GRAD_RAW is set.  Deterministic: no atomics.               */
+enum { R2L_IO_F32 = 0, R2L_IO_BF16 = 1, R2L_IO_F16 = 2 };
+int r2l_isp_io_supported(int io, int raw_u16, int has_additive, int B, int H, int W, int phase);
+int r2l_isp_step_fwd_io(const void *raw, int raw_u16, float denom, const float *const *params_host,
+                        const float *additive, int bn_mode, float *running_mean, float *running_var,
+                        long long *num_batches_tracked, double eps, double momentum, void *out, int io, void *workspace,
+                        size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                        const double *gathered_stats, void *stream);
+int r2l_isp_step_bwd_io(const void *raw, int raw_u16, float denom, const float *additive, const void *grad_out, int io,
+                        const void *out, float *grad_params, float *grad_additive, int bn_mode, void *workspace,
+                        size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                        const double *gathered_sums, void *stream, float *grad_raw, void *raw_grad_scratch,
+                        size_t raw_grad_scratch_bytes, unsigned grad_mask);
+
 /* ---- static pipeline, numpy semantics (processing(), processing/pipeline_numpy.py:70-141, batched):
  * remove_blacklv (:152-158) -> demosaicing_CFA_Bayer_{bilinear,Malvar2004} (:92-95) -> wb (:161-162) ->
  * CCM (:165-167) -> [sharpening_filter (:180-191) | unsharp_masking (:170-177)] -> [gaussian_denoising (:203-209) | median_denoising

@@ -203,6 +203,21 @@ R2L_FS_KERNEL_EPI(r2l_launch_fwd_stream_epi_w1_u16, 1, true)
 R2L_FS_KERNEL_EPI(r2l_launch_fwd_stream_epi_w2_u16, 2, true)
 R2L_FS_KERNEL_EPI(r2l_launch_fwd_stream_epi_w4_u16, 4, true)
 R2L_FS_KERNEL_EPI(r2l_launch_fwd_stream_epi_w8_u16, 8, true)
+// ... writing the output as bfloat16 / float16 (r2l_isp_step_fwd_io: R2L_IO_*; no epilogue)
+#define R2L_FS_KERNEL_IO(name, NW, U16, IO)                                                              \
+  R2L_KERNEL_NT_LDS(name, R2LFwdStreamArgs, (NW) * 64, R2L_FS_LDS_FLOATS(NW), R2L_FS_OCC_NW(NW),          \
+                    r2l_fwd_stream_block<NW, U16, false, false, IO>)
+#define R2L_FS_KERNELS_IO(sfx, IO)                                  \
+  R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w1##sfx, 1, false, IO)     \
+  R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w2##sfx, 2, false, IO)     \
+  R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w4##sfx, 4, false, IO)     \
+  R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w8##sfx, 8, false, IO)     \
+  R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w1_u16##sfx, 1, true, IO)  \
+  R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w2_u16##sfx, 2, true, IO)  \
+  R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w4_u16##sfx, 4, true, IO)  \
+  R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w8_u16##sfx, 8, true, IO)
+R2L_FS_KERNELS_IO(_bf16, R2L_IO_BF16)
+R2L_FS_KERNELS_IO(_f16, R2L_IO_F16)
 // the apply pass of train-mode BatchNorm on the Y' plane the statistics pass kept: independent wavefronts, no LDS
 #ifndef R2L_FA_OCC
 #define R2L_FA_OCC 3
@@ -216,6 +231,13 @@ R2L_FA_KERNEL(r2l_launch_fwd_apply, false, false)
 R2L_FA_KERNEL(r2l_launch_fwd_apply_u16, true, false)
 R2L_FA_KERNEL(r2l_launch_fwd_apply_epi, false, true)
 R2L_FA_KERNEL(r2l_launch_fwd_apply_epi_u16, true, true)
+#define R2L_FA_KERNEL_IO(name, U16, IO)                                             \
+  R2L_KERNEL_NT_LDS(name, R2LFwdStreamArgs, 64 * R2L_FA_NWV, 4, R2L_FA_OCC,         \
+                    r2l_fwd_apply_block<U16, false, false, R2L_FA_NWV, IO>)
+R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_bf16, false, R2L_IO_BF16)
+R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_u16_bf16, true, R2L_IO_BF16)
+R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_f16, false, R2L_IO_F16)
+R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_u16_f16, true, R2L_IO_F16)
 // ... the same walk without output: the BatchNorm statistics from the kept plane (2 wavefronts per workgroup, each with
 // its own work items; <= R2L_MAX_BLOCKS workgroups = partials of the reduction tree)
 #define R2L_FA_STATS_NWV 4
@@ -261,6 +283,23 @@ R2L_BLOCKFN void r2l_bwd1_plane_guv_block(const R2LBwd1GuvArgs& a, int bid, int 
   r2l_bwd1_plane_block<false, false, true>(a.b, bid, nblk, lds, a.guv);
 }
 R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane_guv, R2LBwd1GuvArgs, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2, r2l_bwd1_plane_guv_block)
+// ... reading grad_out as bfloat16 / float16 (r2l_isp_step_bwd_io: the full route, no epilogue)
+template <int IO>
+R2L_BLOCKFN void r2l_bwd1_plane_guv_io_block(const R2LBwd1GuvArgs& a, int bid, int nblk, float* lds) {
+  r2l_bwd1_plane_block<false, false, true, R2L_BPS_FULL, R2L_BPS_PF, IO>(a.b, bid, nblk, lds, a.guv);
+}
+// (16-bit container frames and the gU / gV stores: ONE row of raw / Y' in flight like the reduced routes (R2L_BPS_PF, 10 registers
+// less) -- with two, hipcc took 214 and 226 registers where the float32 siblings take 208 and 222, whatever the place of the
+// widening; the cotangent these forms wait for is half as many bytes.  profiles/half_io_resources.txt)
+#define R2L_BP_KERNELS_IO(sfx, IO)                                                                          \
+  R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane##sfx, R2LBwd1Args, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2,               \
+                    r2l_bwd1_plane_block<false, false, false, R2L_BPS_FULL, R2L_BP_PF, IO>)                 \
+  R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane_u16##sfx, R2LBwd1Args, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2,           \
+                    r2l_bwd1_plane_block<true, false, false, R2L_BPS_FULL, R2L_BPS_PF, IO>)                 \
+  R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane_guv##sfx, R2LBwd1GuvArgs, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2,        \
+                    r2l_bwd1_plane_guv_io_block<IO>)
+R2L_BP_KERNELS_IO(_bf16, R2L_IO_BF16)
+R2L_BP_KERNELS_IO(_f16, R2L_IO_F16)
 R2L_KERNEL_NT_LDS(r2l_launch_bwd1_blur, R2LBwd1Args, R2L_BP_NT, R2L_BP_RED_FLOATS, 3, r2l_bwd1_blur_block)
 R2L_KERNEL_NT_LDS(r2l_launch_bwd1_blur_hp, R2LBwd1Args, R2L_BP_NT, R2L_BP_RED_FLOATS, R2L_HB_OCC, r2l_bwd1_blur_hp_block)
 // the reduced forms r2l_isp_step_bwd_select routes to (R2L_BPS_*: what each keeps).  Without the 38 stencil accumulator pairs
@@ -322,6 +361,13 @@ R2L_BNR_KERNEL(r2l_launch_bnr_planes, false, false)
 R2L_BNR_KERNEL(r2l_launch_bnr_planes_u16, true, false)
 R2L_BNR_KERNEL(r2l_launch_bnr_planes_epi, false, true)
 R2L_BNR_KERNEL(r2l_launch_bnr_planes_epi_u16, true, true)
+#define R2L_BNR_KERNEL_IO(name, U16, IO)                                                                        \
+  R2L_KERNEL_NT_LDS(name, R2LBnrArgs, 64 * R2L_BNR_NWV, R2L_FA_LDS_FLOATS(R2L_BNR_NWV, true), R2L_BNR_OCC,      \
+                    r2l_bnr_planes_block<U16, false, R2L_BNR_NWV, IO>)
+R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_bf16, false, R2L_IO_BF16)
+R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_u16_bf16, true, R2L_IO_BF16)
+R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_f16, false, R2L_IO_F16)
+R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_u16_f16, true, R2L_IO_F16)
 #endif
 R2L_KERNEL_V(r2l_launch_bwd2, R2LBwd2Args, R2L_LDS3(GBwd2), R2L_OCC_BWD2, r2l_bwd2_block<GBwd2, false>)
 R2L_KERNEL_V(r2l_launch_fwd_u16, R2LFwdArgs, R2L_LDS3(GFwd), R2L_OCC_FWD, r2l_fwd_block<GFwd, false, false, true>)
@@ -682,9 +728,12 @@ static bool r2l_fwd_streams(bool additive, int W) {
 static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float* additive,
                             const float* bn_mean_istd, float* out, double* stats, void* workspace,
                             size_t workspace_bytes, int B, int H, int W, int flags, void* stream,
-                            const R2LBnFinalizeArgs* fin = nullptr, const R2LEpi* ep = nullptr) {
+                            const R2LBnFinalizeArgs* fin = nullptr, const R2LEpi* ep = nullptr, int io = R2L_IO_F32) {
+  // io: the type `out` really holds (R2L_IO_*; r2l_isp_step_fwd_io has checked that the streaming kernels serve the call)
   if (int e = r2l_check_dims(B, H, W)) return e;
   if (int e = r2l_check_raw(raw, W, "r2l_isp_fwd")) return e;
+  if (io != R2L_IO_F32 && (!r2l_fwd_streams(additive, W) || (ep && ep->on)))
+    return r2l_fail(-3, "r2l_isp_fwd: internal: a 16-bit output needs the row-streaming forward without an epilogue");
   if (!params || !workspace) return r2l_fail(-1, "r2l_isp_fwd: null pointer");
   if (additive && (H != 256 || W != 256))
     return r2l_fail(-1, "additive_layer is (1,3,256,256): needs 256x256 frames");
@@ -801,7 +850,10 @@ static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float*
       fa.nitems = (int)grid;
       static const launch_t atable[2][2] = {{r2l_launch_fwd_apply, r2l_launch_fwd_apply_u16},
                                             {r2l_launch_fwd_apply_epi, r2l_launch_fwd_apply_epi_u16}};
-      return atable[epi ? 1 : 0][raw.u16 ? 1 : 0](fa, (int)((grid + R2L_FA_NWV - 1) / R2L_FA_NWV), stream);
+      static const launch_t atable_io[2][2] = {{r2l_launch_fwd_apply_bf16, r2l_launch_fwd_apply_u16_bf16},
+                                               {r2l_launch_fwd_apply_f16, r2l_launch_fwd_apply_u16_f16}};
+      const launch_t apply = io != R2L_IO_F32 ? atable_io[io - 1][raw.u16 ? 1 : 0] : atable[epi ? 1 : 0][raw.u16 ? 1 : 0];
+      return apply(fa, (int)((grid + R2L_FA_NWV - 1) / R2L_FA_NWV), stream);
     }
     if (!out && stats) {  // the statistics pass: its own instantiation (no output code, fewer live scalars)
       static const launch_t stable[2][4] = {
@@ -810,6 +862,16 @@ static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float*
           {r2l_launch_fwd_stream_stats_w1_u16, r2l_launch_fwd_stream_stats_w2_u16, r2l_launch_fwd_stream_stats_w4_u16,
            r2l_launch_fwd_stream_stats_w8_u16}};
       return stable[raw.u16 ? 1 : 0][nw](fa, sgrid, stream);
+    }
+    if (io != R2L_IO_F32) {
+#define R2L_FS_ROW_IO(sfx)                                                                                          \
+  {{r2l_launch_fwd_stream_w1##sfx, r2l_launch_fwd_stream_w2##sfx, r2l_launch_fwd_stream_w4##sfx,                    \
+    r2l_launch_fwd_stream_w8##sfx},                                                                                 \
+   {r2l_launch_fwd_stream_w1_u16##sfx, r2l_launch_fwd_stream_w2_u16##sfx, r2l_launch_fwd_stream_w4_u16##sfx,        \
+    r2l_launch_fwd_stream_w8_u16##sfx}}
+      static const launch_t table_io[2][2][4] = {R2L_FS_ROW_IO(_bf16), R2L_FS_ROW_IO(_f16)};
+#undef R2L_FS_ROW_IO
+      return table_io[io - 1][raw.u16 ? 1 : 0][nw](fa, sgrid, stream);
     }
     return table[epi ? 1 : 0][raw.u16 ? 1 : 0][nw](fa, sgrid, stream);
   }
@@ -914,9 +976,14 @@ struct R2LBwdPlan {
 };
 // grad_mask: the R2L_GRAD_* bits a caller of r2l_isp_step_bwd_select asks for, 0 = every parameter gradient; want_raw: d/d raw too.
 // The only reader of the backward's overrides of diagnostic builds (R2L_BWD_*, R2L_GRID_BWD*, the band heights).
+// io16: grad_out is bfloat16 / float16 (r2l_isp_step_bwd_io) -- read by the plane passes only, which such a call therefore
+// takes at every size, on the full route whatever the mask
 static R2LBwdPlan r2l_bwd_plan(unsigned grad_mask, bool want_raw, int raw_u16, bool has_additive, bool epi_on,
-                               bool keep_luma, int B, int H, int W) {
+                               bool keep_luma, int B, int H, int W, bool io16 = false) {
   R2LBwdPlan p = {};
+  if (io16) grad_mask = 0;
+  const bool want_raw_mask = want_raw;  // (the reduced routes' own condition below)
+  want_raw = want_raw || io16;          // "the plane passes at every size, no diagnostic override"
   // (the serial emulation has no row-streaming forward, so nothing is ever saved there and every plan is tile kernels)
   p.saved = keep_luma && r2l_fwd_streams(has_additive, W) && (want_raw || !r2l_env_int("R2L_BWD1_RECOMPUTE", 0));
   // frames that do not tile by 64: Y' recomputed in LDS, kept or not; an additive layer means 256 x 256 frames, which tile exactly
@@ -968,7 +1035,7 @@ static R2LBwdPlan r2l_bwd_plan(unsigned grad_mask, bool want_raw, int raw_u16, b
     p.b2_grid = p.b2_nmain + R2L_B2S_HELPERS;
     p.in_kernel = true;
   }
-  if (want_raw && p.b2_planes) {  // d/d raw from HP and the chroma gradient planes: one item per wavefront
+  if (want_raw_mask && p.b2_planes) {  // d/d raw from HP and the chroma gradient planes: one item per wavefront
     p.raw_band = band_rows(256L * 4 * R2L_BR_OCC, "R2L_BR_BAND");
     p.raw_grid = r2l_plane_grid(B, H, W, p.raw_band, R2L_BR_NWV, 0);
   }
@@ -1003,6 +1070,7 @@ struct R2LBwdCall {
   unsigned grad_mask;  // r2l_bwd_plan's
   int B, H, W;
   void* stream;
+  int io;  // the type behind gout (R2L_IO_*)
 };
 static R2LBwd1Args r2l_bwd1_args(const R2LBwdCall& c, const R2LWorkspace& ws, const R2LBwdPlan& p) {
   R2LBwd1Args a;
@@ -1064,6 +1132,8 @@ static int r2l_bwd_launch(const R2LBwdCall& c, const R2LWorkspace& ws, const R2L
   const int u16 = c.raw.u16 ? 1 : 0, g1 = p.b1_grid;
   void* const stream = c.stream;
   const R2LBwd1Args a1 = r2l_bwd1_args(c, ws, p);
+  if (c.io != R2L_IO_F32 && (p.b1 != R2L_B1_PLANES || p.select || c.ep.on))
+    return r2l_fail(-3, "r2l_isp_step_bwd_io: internal: a 16-bit cotangent needs the full plane route without an epilogue");
   if (p.b1 != R2L_B1_PLANES) {
     typedef int (*launch_t)(const R2LBwd1Args&, int, void*);
     static const launch_t tile[4][2] = {{r2l_launch_bwd1_saved, r2l_launch_bwd1_saved_u16},
@@ -1099,10 +1169,18 @@ static int r2l_bwd_launch(const R2LBwdCall& c, const R2LWorkspace& ws, const R2L
     typedef int (*launch_t)(const R2LBwd1Args&, int, void*);
     static const launch_t plane[2][2] = {{r2l_launch_bwd1_plane, r2l_launch_bwd1_plane_u16},
                                          {r2l_launch_bwd1_plane_epi, r2l_launch_bwd1_plane_epi_u16}};
+    static const launch_t plane_io[2][2] = {{r2l_launch_bwd1_plane_bf16, r2l_launch_bwd1_plane_u16_bf16},
+                                            {r2l_launch_bwd1_plane_f16, r2l_launch_bwd1_plane_u16_f16}};
     // (d/d raw: float32 frames, no epilogue -- r2l_raw_grad_preconditions)
-    if (int e = c.grad_raw ? r2l_launch_bwd1_plane_guv(R2LBwd1GuvArgs{a1, c.guv}, g1, stream)
-                           : plane[c.ep.on ? 1 : 0][u16](a1, g1, stream))
-      return e;
+    int e;
+    if (c.io != R2L_IO_F32)
+      e = c.grad_raw ? (c.io == R2L_IO_BF16 ? r2l_launch_bwd1_plane_guv_bf16(R2LBwd1GuvArgs{a1, c.guv}, g1, stream)
+                                            : r2l_launch_bwd1_plane_guv_f16(R2LBwd1GuvArgs{a1, c.guv}, g1, stream))
+                     : plane_io[c.io - 1][u16](a1, g1, stream);
+    else
+      e = c.grad_raw ? r2l_launch_bwd1_plane_guv(R2LBwd1GuvArgs{a1, c.guv}, g1, stream)
+                     : plane[c.ep.on ? 1 : 0][u16](a1, g1, stream);
+    if (e) return e;
     if (int e = p.blur_hp ? r2l_launch_bwd1_blur_hp(a1, g1, stream) : r2l_launch_bwd1_blur(a1, g1, stream)) return e;
   }
 #endif
@@ -1156,7 +1234,7 @@ static int r2l_isp_bwd_impl(const R2LRaw& raw, const float* params, const float*
     if (int e = r2l_launch_fold(fa, 1, stream)) return e;
   }
   const R2LBwdCall c{raw, params, additive, bn_mean_istd, bn_bwd, grad_out, grad_params, nullptr, nullptr,
-                     R2LEpi{0, 0, 0, 0}, 0, B, H, W, stream};
+                     R2LEpi{0, 0, 0, 0}, 0, B, H, W, stream, R2L_IO_F32};
   return r2l_bwd_launch(c, ws, r2l_bwd_plan(0, false, raw.u16 != nullptr, additive != nullptr, false,
                                             (flags & R2L_F_KEEP_LUMA) != 0, B, H, W));
 }
@@ -1209,11 +1287,12 @@ size_t r2l_isp_step_offset(int which, int B, int H, int W) {
     default: return 0;
   }
 }
-int r2l_isp_step_fwd(const void* raw, int raw_u16, float denom, const float* const* params_host,
-                     const float* additive, int bn_mode, float* running_mean, float* running_var,
-                     long long* num_batches_tracked, double eps, double momentum, float* out, void* workspace,
-                     size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
-                     const double* gathered_stats, void* stream) {
+// r2l_isp_step_fwd and r2l_isp_step_fwd_io: `out` holds elements of type io (R2L_IO_*)
+static int r2l_isp_step_fwd_impl(const void* raw, int raw_u16, float denom, const float* const* params_host,
+                                 const float* additive, int bn_mode, float* running_mean, float* running_var,
+                                 long long* num_batches_tracked, double eps, double momentum, float* out, int io,
+                                 void* workspace, size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                                 const double* gathered_stats, void* stream) {
   const int keep = (phase & R2L_STEP_KEEP_LUMA) ? R2L_F_KEEP_LUMA : 0;
   R2LEpi ep;
   if (int e = r2l_check_dims(B, H, W)) return e;
@@ -1270,21 +1349,34 @@ int r2l_isp_step_fwd(const void* raw, int raw_u16, float denom, const float* con
   // row-streaming forward runs, and the apply pass reads it)
   return r2l_isp_fwd_impl(rw, ws.packed, additive, bn_mode == R2L_BN_NONE ? nullptr : ws.bn, out, nullptr, workspace,
                           workspace_bytes, B, H, W,
-                          R2L_F_FOLDED_VALID | keep | (bn_mode == R2L_BN_TRAIN ? R2L_F_LUMA_VALID : 0), stream, nullptr, &ep);
+                          R2L_F_FOLDED_VALID | keep | (bn_mode == R2L_BN_TRAIN ? R2L_F_LUMA_VALID : 0), stream, nullptr, &ep, io);
+}
+int r2l_isp_step_fwd(const void* raw, int raw_u16, float denom, const float* const* params_host,
+                     const float* additive, int bn_mode, float* running_mean, float* running_var,
+                     long long* num_batches_tracked, double eps, double momentum, float* out, void* workspace,
+                     size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                     const double* gathered_stats, void* stream) {
+  return r2l_isp_step_fwd_impl(raw, raw_u16, denom, params_host, additive, bn_mode, running_mean, running_var,
+                               num_batches_tracked, eps, momentum, out, R2L_IO_F32, workspace, workspace_bytes, B, H, W, nranks,
+                               phase, gathered_stats, stream);
 }
 // BatchNorm's backward sums of a step whose forward kept Y' (R2L_F_KEEP_LUMA on the row-streaming path): recomputed from the raw
 // frame and Y' (r2l_bnr_planes_block) on batches of >= 6 Mi px where the plane passes run -- the forward's output is then
 // not read at all by the backward.  Returns 1 when it did not run (the caller falls back to r2l_bn_bwd_reduce).
+// io: the type behind grad_out (R2L_IO_*); a 16-bit cotangent is read by this pass only, at every size.
 static int r2l_bn_bwd_reduce_planes(const R2LRaw& raw, const float* additive, const float* grad_out, const R2LWorkspace& ws,
-                                    const R2LEpi& ep, float* bn_bwd, int B, int H, int W, int keep, void* stream) {
+                                    const R2LEpi& ep, float* bn_bwd, int B, int H, int W, int keep, void* stream,
+                                    int io = R2L_IO_F32) {
 #ifdef R2L_SERIAL
   (void)raw; (void)additive; (void)grad_out; (void)ws; (void)ep; (void)bn_bwd; (void)B; (void)H; (void)W; (void)keep; (void)stream;
+  (void)io;
   return 1;
 #else
   // (from 6 Mi px: at 64x256x256 = 4 Mi px the whole step, output included, lives in the memory-side cache and reading the output back
   //  is cheaper than recomputing it -- bn_reduce 22.4-23.8 us against 27.1; at 128x256x256 37.2 against 37.5, the step 2 % faster)
-  const bool planes = r2l_bwd_planes_forced() || (size_t)B * H * W >= ((size_t)6 << 20);
+  const bool planes = io != R2L_IO_F32 || r2l_bwd_planes_forced() || (size_t)B * H * W >= ((size_t)6 << 20);
   if (!keep || !r2l_fwd_streams(additive, W) || !planes) return 1;
+  if (io != R2L_IO_F32 && ep.on) return 1;
   R2LBnrArgs a;
   a.s.raw = raw;
   a.s.F = ws.folded;
@@ -1314,6 +1406,8 @@ static int r2l_bn_bwd_reduce_planes(const R2LRaw& raw, const float* additive, co
   a.totals = ws.moments;
   a.bn_bwd = bn_bwd;
   const int g = r2l_plane_grid(B, H, W, a.s.band_h, R2L_BNR_NWV, r2l_env_int("R2L_GRID_BNR", R2L_MAX_BLOCKS));
+  if (io == R2L_IO_BF16) return raw.u16 ? r2l_launch_bnr_planes_u16_bf16(a, g, stream) : r2l_launch_bnr_planes_bf16(a, g, stream);
+  if (io == R2L_IO_F16) return raw.u16 ? r2l_launch_bnr_planes_u16_f16(a, g, stream) : r2l_launch_bnr_planes_f16(a, g, stream);
   return ep.on ? (raw.u16 ? r2l_launch_bnr_planes_epi_u16(a, g, stream) : r2l_launch_bnr_planes_epi(a, g, stream))
                : (raw.u16 ? r2l_launch_bnr_planes_u16(a, g, stream) : r2l_launch_bnr_planes(a, g, stream));
 #endif
@@ -1334,6 +1428,7 @@ struct R2LStepBwd {
   void* stream;
   float *grad_raw, *guv;  // d/d raw and its scratch (the chroma gradient planes), or null
   unsigned grad_mask;     // R2L_GRAD_* bits (r2l_isp_step_bwd_select), 0 = every parameter gradient
+  int io;                 // the type behind grad_out (R2L_IO_*, r2l_isp_step_bwd_io; `out` is then not read)
 };
 static int r2l_isp_step_bwd_impl(const R2LStepBwd& q) {
   const int B = q.B, H = q.H, W = q.W;
@@ -1351,7 +1446,10 @@ static int r2l_isp_step_bwd_impl(const R2LStepBwd& q) {
   if (phase != R2L_STEP_ALL && q.bn_mode != R2L_BN_TRAIN)
     return r2l_fail(-1, "r2l_isp_step_bwd: only train-mode BatchNorm has two phases");
   if (phase == R2L_STEP_B && !q.gathered_sums) return r2l_fail(-1, "r2l_isp_step_bwd: phase B needs the gathered sums");
-  if (q.bn_mode == R2L_BN_TRAIN && !q.out) return r2l_fail(-1, "r2l_isp_step_bwd: train-mode BatchNorm needs the saved output");
+  if (q.bn_mode == R2L_BN_TRAIN && !q.out && q.io == R2L_IO_F32)
+    return r2l_fail(-1, "r2l_isp_step_bwd: train-mode BatchNorm needs the saved output");
+  if (q.io != R2L_IO_F32 && q.grad_additive)
+    return r2l_fail(-3, "r2l_isp_step_bwd_io: a 16-bit cotangent is not served with an additive layer");
   const R2LRaw rw = r2l_raw_any(q.raw, q.raw_u16, q.denom);
   // (before ANY launch: the recomputing BatchNorm sums below read the raw frames)
   if (int e = r2l_check_raw(rw, W, "r2l_isp_step_bwd")) return e;
@@ -1361,7 +1459,9 @@ static int r2l_isp_step_bwd_impl(const R2LStepBwd& q) {
   const float* bn_bwd = q.bn_mode == R2L_BN_TRAIN ? ws.bn_bwd : nullptr;
   if (q.bn_mode == R2L_BN_TRAIN && phase != R2L_STEP_B) {
     float* means = phase == R2L_STEP_ALL ? ws.bn_bwd : nullptr;
-    int e = r2l_bn_bwd_reduce_planes(rw, q.additive, q.grad_out, ws, ep, means, B, H, W, keep, q.stream);
+    int e = r2l_bn_bwd_reduce_planes(rw, q.additive, q.grad_out, ws, ep, means, B, H, W, keep, q.stream, q.io);
+    if (e == 1 && q.io != R2L_IO_F32)
+      return r2l_fail(-3, "r2l_isp_step_bwd_io: internal: the BatchNorm sums of a 16-bit cotangent need the plane pass");
     if (e == 1) e = r2l_bn_bwd_reduce(q.grad_out, q.out, ws.moments, ws.bsums, means, q.workspace, q.workspace_bytes, B, H, W,
                                       R2L_F_FOLDED_VALID, q.stream);
     if (e) return e;
@@ -1375,9 +1475,9 @@ static int r2l_isp_step_bwd_impl(const R2LStepBwd& q) {
     if (q.additive && (H != 256 || W != 256))
       return r2l_fail(-1, "additive_layer is (1,3,256,256): needs 256x256 frames");
     const R2LBwdCall c{rw, ws.packed, q.additive, bn, bn_bwd, q.grad_out, q.grad_params, q.grad_raw, q.guv, ep, q.grad_mask,
-                       B, H, W, q.stream};
+                       B, H, W, q.stream, q.io};
     const R2LBwdPlan p = r2l_bwd_plan(q.grad_mask, q.grad_raw != nullptr, q.raw_u16, q.additive != nullptr, ep.on != 0,
-                                      keep != 0, B, H, W);
+                                      keep != 0, B, H, W, q.io != R2L_IO_F32);
     if (int e = r2l_bwd_launch(c, ws, p)) return e;
   }
   if (q.grad_additive) return r2l_additive_bwd(q.grad_out, q.out, bn, bn_bwd, q.grad_additive, B, H, W, q.stream);
@@ -1414,7 +1514,7 @@ int r2l_isp_step_bwd(const void* raw, int raw_u16, float denom, const float* add
                      const double* gathered_sums, void* stream) {
   return r2l_isp_step_bwd_impl(R2LStepBwd{raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode,
                                           workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, nullptr,
-                                          nullptr, 0});
+                                          nullptr, 0, R2L_IO_F32});
 }
 int r2l_isp_step_bwd_raw(const void* raw, int raw_u16, float denom, const float* additive, const float* grad_out,
                          const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
@@ -1424,7 +1524,7 @@ int r2l_isp_step_bwd_raw(const void* raw, int raw_u16, float denom, const float*
   // (without grad_raw: r2l_isp_step_bwd, the scratch is not looked at)
   const R2LStepBwd q{raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode, workspace,
                      workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw,
-                     grad_raw ? (float*)raw_grad_scratch : nullptr, 0};
+                     grad_raw ? (float*)raw_grad_scratch : nullptr, 0, R2L_IO_F32};
   if (grad_raw)
     if (int e = r2l_raw_grad_preconditions(q, raw_grad_scratch_bytes)) return e;
   // (phase A computes the BatchNorm sums only: the gradient kernels, and with them d/d raw, run in phase B / ALL)
@@ -1442,10 +1542,69 @@ int r2l_isp_step_bwd_select(const void* raw, int raw_u16, float denom, const flo
   if (grad_mask && !grad_params) return r2l_fail(-1, "r2l_isp_step_bwd_select: a gradient is asked for but grad_params is null");
   const R2LStepBwd q{raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode, workspace,
                      workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw, (float*)raw_grad_scratch,
-                     grad_mask};
+                     grad_mask, R2L_IO_F32};
   if (grad_raw)
     if (int e = r2l_raw_grad_preconditions(q, raw_grad_scratch_bytes)) return e;
   // (a mask without a reduced route runs exactly r2l_isp_step_bwd / r2l_isp_step_bwd_raw: r2l_bwd_plan)
+  return r2l_isp_step_bwd_impl(q);
+}
+
+// ---- 16-bit output / cotangent (include/r2l_isp.h: R2L_IO_*) ------------------------------------------------------------------
+// why a 16-bit call is not served, or null: the ONE predicate of r2l_isp_io_supported, r2l_isp_step_fwd_io and r2l_isp_step_bwd_io
+static const char* r2l_io_why(int raw_u16, bool has_additive, int B, int H, int W, int phase) {
+  (void)raw_u16;  // (both frame types are served)
+  if (!R2L_PLANE_PASSES) return "the serial emulation has no row-streaming forward and no plane passes";
+  if (B < 1 || H < 4 || W < 4 || (H & 1) || (W & 1)) return "H and W must be even and >= 4, B >= 1";
+  if (has_additive) return "not with an additive layer";
+  if ((W & 3) || W > 2048) return "needs W % 4 == 0 and W <= 2048";
+  if (r2l_env_int("R2L_FWD_TILED", 0)) return "needs the row-streaming forward (R2L_FWD_TILED is set)";
+  if (phase & R2L_STEP_EPI_MASK) return "not with an output epilogue";
+  if (!(phase & R2L_STEP_KEEP_LUMA)) return "needs R2L_STEP_KEEP_LUMA in `phase` of both calls";
+  return nullptr;
+}
+static int r2l_io_check(const char* who, int io, const void* tensor, int raw_u16, bool has_additive, int B, int H, int W, int phase) {
+  if (io != R2L_IO_BF16 && io != R2L_IO_F16) return r2l_fail(-1, std::string(who) + ": io must be one of R2L_IO_*");
+  if (const char* why = r2l_io_why(raw_u16, has_additive, B, H, W, phase))
+    return r2l_fail(-3, std::string(who) + ": a 16-bit output / cotangent is not served here: " + why);
+  if ((uintptr_t)tensor % 8) return r2l_fail(-1, std::string(who) + ": the 16-bit tensor must be 8-byte aligned");
+  return 0;
+}
+int r2l_isp_io_supported(int io, int raw_u16, int has_additive, int B, int H, int W, int phase) {
+  if (io == R2L_IO_F32) return 1;
+  if (io != R2L_IO_BF16 && io != R2L_IO_F16) return 0;
+  return r2l_io_why(raw_u16, has_additive != 0, B, H, W, phase) ? 0 : 1;
+}
+int r2l_isp_step_fwd_io(const void* raw, int raw_u16, float denom, const float* const* params_host,
+                        const float* additive, int bn_mode, float* running_mean, float* running_var,
+                        long long* num_batches_tracked, double eps, double momentum, void* out, int io, void* workspace,
+                        size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                        const double* gathered_stats, void* stream) {
+  if (io != R2L_IO_F32)
+    if (int e = r2l_io_check("r2l_isp_step_fwd_io", io, out, raw_u16, additive != nullptr, B, H, W, phase)) return e;
+  return r2l_isp_step_fwd_impl(raw, raw_u16, denom, params_host, additive, bn_mode, running_mean, running_var,
+                               num_batches_tracked, eps, momentum, (float*)out, io, workspace, workspace_bytes, B, H, W, nranks,
+                               phase, gathered_stats, stream);
+}
+int r2l_isp_step_bwd_io(const void* raw, int raw_u16, float denom, const float* additive, const void* grad_out, int io,
+                        const void* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
+                        size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                        const double* gathered_sums, void* stream, float* grad_raw, void* raw_grad_scratch,
+                        size_t raw_grad_scratch_bytes, unsigned grad_mask) {
+  if (io == R2L_IO_F32)
+    return r2l_isp_step_bwd_select(raw, raw_u16, denom, additive, (const float*)grad_out, (const float*)out, grad_params,
+                                   grad_additive, bn_mode, workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums,
+                                   stream, grad_raw, raw_grad_scratch, raw_grad_scratch_bytes, grad_mask);
+  if (int e = r2l_io_check("r2l_isp_step_bwd_io", io, grad_out, raw_u16, additive != nullptr, B, H, W, phase)) return e;
+  if (grad_mask & ~(unsigned)(R2L_GRAD_ALL_PARAMS | R2L_GRAD_RAW))
+    return r2l_fail(-1, "r2l_isp_step_bwd_io: unknown bits in grad_mask");
+  if ((grad_raw != nullptr) != ((grad_mask & R2L_GRAD_RAW) != 0))
+    return r2l_fail(-1, "r2l_isp_step_bwd_io: grad_raw goes with R2L_GRAD_RAW in grad_mask");
+  if (grad_mask && !grad_params) return r2l_fail(-1, "r2l_isp_step_bwd_io: a gradient is asked for but grad_params is null");
+  const R2LStepBwd q{raw, raw_u16, denom, additive, (const float*)grad_out, (const float*)out, grad_params, grad_additive,
+                     bn_mode, workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw,
+                     (float*)raw_grad_scratch, grad_mask, io};
+  if (grad_raw)
+    if (int e = r2l_raw_grad_preconditions(q, raw_grad_scratch_bytes)) return e;
   return r2l_isp_step_bwd_impl(q);
 }
 

@@ -403,6 +403,124 @@ R2L_HD float r2l_u2f(unsigned u) {
   return x;
 }
 
+// ---- 16-bit boundary tensors (R2L_IO_BF16 / R2L_IO_F16, include/r2l_isp.h) ---------------------------------------------
+// The forward's output and the backward's cotangent may cross the module boundary as bfloat16 or IEEE float16; everything
+// between the load and the store stays float32.  Narrowing is round-to-nearest-even, bit for bit torch.Tensor.to(dtype):
+// overflow goes to Inf, float16 subnormals are produced and read, a NaN stays a (quiet) NaN of its sign.  The device takes
+// the hardware conversions (v_cvt_pk_bf16_f32, v_cvt_f16_f32 / v_cvt_f32_f16: round-to-nearest-even and float16 subnormals
+// are the kernels' default mode); the host emulations -- g++ has no _Float16 on x86-64 -- the same in integer arithmetic.
+// Checked pattern by pattern against torch by tests/test_half_io.py (the host forms) and by the GPU tests (the device forms).
+R2L_HD unsigned r2l_f32_to_bf16_bits(float x) {
+#ifdef R2L_EMUL
+  const unsigned u = r2l_f2u(x);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;  // NaN: quiet, sign and upper payload kept
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;                  // (a carry out of the mantissa is the next exponent, up to Inf)
+#else
+  const __bf16 b = (__bf16)x;
+  return (unsigned)__builtin_bit_cast(unsigned short, b);
+#endif
+}
+R2L_HD float r2l_bf16_bits_to_f32(unsigned h) { return r2l_u2f((h & 0xffffu) << 16); }
+R2L_HD unsigned r2l_f32_to_f16_bits(float x) {
+#ifdef R2L_EMUL
+  const unsigned u = r2l_f2u(x), sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
+  if (a > 0x7f800000u) return sign | 0x7e00u | ((a >> 13) & 0x1ffu);  // NaN: quiet
+  if (a >= 0x38800000u) {  // >= 2^-14: a normal float16, or past its range
+    unsigned v = a - 0x38000000u;  // exponent re-biased (127 -> 15)
+    v = (v + 0xfffu + ((v >> 13) & 1u)) >> 13;
+    return sign | (v >= 0x7c00u ? 0x7c00u : v);  // 65520 and above round to Inf
+  }
+  if (a <= 0x33000000u) return sign;  // <= 2^-25: zero (2^-25 itself is a tie between 0 and 2^-24, and 0 is even)
+  // subnormal result: m x 2^(e - 150) in units of 2^-24
+  const unsigned e = a >> 23, m = (a & 0x7fffffu) | 0x800000u, sh = 126u - e;  // e = 102 .. 112, sh = 24 .. 14
+  unsigned r = m >> sh;
+  const unsigned rem = m & ((1u << sh) - 1u), half = 1u << (sh - 1u);
+  if (rem > half || (rem == half && (r & 1u))) ++r;  // (r = 0x400 is the smallest normal number: the encoding continues)
+  return sign | r;
+#else
+  const _Float16 h = (_Float16)x;
+  return (unsigned)__builtin_bit_cast(unsigned short, h);
+#endif
+}
+R2L_HD float r2l_f16_bits_to_f32(unsigned h) {
+#ifdef R2L_EMUL
+  const unsigned sign = (h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
+  if (e == 0) return r2l_u2f(sign | r2l_f2u((float)m * 5.9604644775390625e-8f));  // zero / subnormal: m x 2^-24, exact
+  if (e == 31) return r2l_u2f(sign | 0x7f800000u | (m << 13));
+  return r2l_u2f(sign | ((e + 112u) << 23) | (m << 13));
+#else
+  return (float)__builtin_bit_cast(_Float16, (unsigned short)h);
+#endif
+}
+template <int IO>
+R2L_HD unsigned r2l_io_narrow(float x) {
+  return IO == R2L_IO_BF16 ? r2l_f32_to_bf16_bits(x) : r2l_f32_to_f16_bits(x);
+}
+template <int IO>
+R2L_HD float r2l_io_widen(unsigned h) {
+  return IO == R2L_IO_BF16 ? r2l_bf16_bits_to_f32(h) : r2l_f16_bits_to_f32(h);
+}
+// The packed forms: a lane owns 4 adjacent pixels of a row, so one channel of them is 8 bytes -- one store resp. load per lane
+// and channel, pixel 0 in the low half of `lo` (memory order).  Cache policy as the float32 path's: the output goes around the
+// caches (r2l_store_f4_nt), the cotangent is read nontemporally (r2l_load_f4_nt).
+struct alignas(8) r2l_h4 {
+  unsigned lo, hi;
+};
+template <int IO>
+R2L_HD r2l_h4 r2l_io_narrow4(const r2l_f4& v) {
+  r2l_h4 h;
+#ifndef R2L_EMUL
+  if (IO == R2L_IO_BF16) {  // one v_cvt_pk_bf16_f32 per pair
+    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    const f2 a = {v.x, v.y}, b = {v.z, v.w};
+    h.lo = __builtin_bit_cast(unsigned, __builtin_convertvector(a, bf2));
+    h.hi = __builtin_bit_cast(unsigned, __builtin_convertvector(b, bf2));
+    return h;
+  }
+#endif
+  h.lo = r2l_io_narrow<IO>(v.x) | (r2l_io_narrow<IO>(v.y) << 16);
+  h.hi = r2l_io_narrow<IO>(v.z) | (r2l_io_narrow<IO>(v.w) << 16);
+  return h;
+}
+template <int IO>
+R2L_HD r2l_f4 r2l_io_widen4(const r2l_h4& h) {
+  r2l_f4 v;
+  v.x = r2l_io_widen<IO>(h.lo & 0xffffu);
+  v.y = r2l_io_widen<IO>(h.lo >> 16);
+  v.z = r2l_io_widen<IO>(h.hi & 0xffffu);
+  v.w = r2l_io_widen<IO>(h.hi >> 16);
+  return v;
+}
+#ifdef R2L_EMUL
+R2L_HD void r2l_store_h4_nt(unsigned short* p, const r2l_h4& h) { *(r2l_h4*)p = h; }
+R2L_HD r2l_h4 r2l_load_h4_nt(const unsigned short* p) { return *(const r2l_h4*)p; }
+#else
+typedef unsigned r2l_vu2 __attribute__((ext_vector_type(2)));
+R2L_HD void r2l_store_h4_nt(unsigned short* p, const r2l_h4& h) {
+  r2l_vu2 v;
+  v.x = h.lo;
+  v.y = h.hi;
+  __builtin_nontemporal_store(v, (r2l_vu2*)p);
+}
+R2L_HD r2l_h4 r2l_load_h4_nt(const unsigned short* p) {
+  const r2l_vu2 v = __builtin_nontemporal_load((const r2l_vu2*)p);
+  r2l_h4 h;
+  h.lo = v.x;
+  h.hi = v.y;
+  return h;
+}
+#endif
+// element i of a boundary tensor of type IO behind a float pointer (the argument blocks keep their float32 types)
+template <int IO>
+R2L_HD float* r2l_io_at(float* p, size_t i) {
+  return IO == R2L_IO_F32 ? p + i : (float*)((unsigned short*)p + i);
+}
+template <int IO>
+R2L_HD const float* r2l_io_at(const float* p, size_t i) {
+  return IO == R2L_IO_F32 ? p + i : (const float*)((const unsigned short*)p + i);
+}
+
 // ---- packed pairs ---------------------------------------------------------------------------------
 // Two horizontally adjacent pixels share one v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32: on gfx950 a packed
 // f32 instruction issues in the same 4 cycles as a scalar one (measured, tests/probes/valu_probe.hip), and

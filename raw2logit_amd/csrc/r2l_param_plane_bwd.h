@@ -43,27 +43,58 @@
   (R2L_BP_SWAP_FLOATS > R2L_BP_RED_FLOATS_R(R2L_BP_ROWS, R2L_BP_NT) ? R2L_BP_SWAP_FLOATS \
                                                                      : R2L_BP_RED_FLOATS_R(R2L_BP_ROWS, R2L_BP_NT))
 
-struct R2LBpStage {  // grad_out of one row in flight: 3 channels x the lane's 4 pixels
+template <int IO>
+struct R2LBpStageT {  // grad_out of one row in flight: 3 channels x the lane's 4 pixels
   r2l_f4 g[3];
+  R2L_MEMBER r2l_f4 ch(int k) const { return g[k]; }
 };
+// a 16-bit cotangent (R2L_IO_BF16 / R2L_IO_F16) stays packed while in flight -- 6 registers per row instead of 12 -- and is
+// widened where the row is used
+template <int IO>
+struct R2LBpStageH {
+  r2l_h4 g[3];
+  R2L_MEMBER r2l_f4 ch(int k) const { return r2l_io_widen4<IO>(g[k]); }
+};
+template <>
+struct R2LBpStageT<R2L_IO_BF16> : R2LBpStageH<R2L_IO_BF16> {};
+template <>
+struct R2LBpStageT<R2L_IO_F16> : R2LBpStageH<R2L_IO_F16> {};
+typedef R2LBpStageT<R2L_IO_F32> R2LBpStage;
+// the row a step consumes, as float32 (a float32 row: the row itself)
+R2L_HD const R2LBpStage& r2l_bp_widen(const R2LBpStage& s) { return s; }
+template <int IO>
+R2L_HD R2LBpStage r2l_bp_widen(const R2LBpStageH<IO>& s) {
+  R2LBpStage w;
+  R2L_PRAGMA_UNROLL
+  for (int k = 0; k < 3; ++k) w.g[k] = s.ch(k);
+  return w;
+}
 // The LAST reader of a kept plane may take it around the caches (nontemporal loads), so that what it leaves in the 256 MiB memory-side
 // cache is what the next passes want (profiles/r05_nt_stores.txt, 64x512x512, alternating processes):
 //   HP in the sums pass (the step's last kernel): the NEXT step's apply pass 63.5 -> 60.1 us, blur pass 43.3 -> 41.5, statistics -0.9
 //     -- 67 MB less dead weight in the cache when the forward starts.  Adopted.
 //   dL/dY'' in the blur pass, Y' in the blur pass, the raw frames in the sums pass: nothing, nothing, +1 us.  Plain loads.
-template <bool EPI>
+template <bool EPI, int IO = R2L_IO_F32>
 R2L_HD void r2l_bp_fetch_g(const float* gimg, unsigned plane, int y, int H, int W, int x0, const R2LEpi& ep,
-                           R2LBpStage& s) {
+                           R2LBpStageT<IO>& s) {
   const int yc = y < 0 ? 0 : (y >= H ? H - 1 : y);
-  if (EPI) {  // grad_out arrives in the augmented layout the forward's epilogue wrote: element s0 + sr y + sc x (R2LEpi)
+  if constexpr (IO != R2L_IO_F32) {  // 8 bytes per lane and channel, read once: nontemporal as below
+    static_assert(!EPI, "a 16-bit cotangent comes in the ISP's own layout");
+    const unsigned short* p = (const unsigned short*)gimg + (size_t)yc * W + x0;
+    R2L_PRAGMA_UNROLL
+    for (int k = 0; k < 3; ++k) s.g[k] = r2l_load_h4_nt(p + (size_t)k * plane);
+    return;
+  } else if (EPI) {  // grad_out arrives in the augmented layout the forward's epilogue wrote: element s0 + sr y + sc x (R2LEpi)
     const float* p = gimg + (ep.s0 + ep.sr * yc + ep.sc * x0);
     R2L_PRAGMA_UNROLL
     for (int k = 0; k < 3; ++k) s.g[k] = r2l_epi_load4(p + (size_t)k * plane, ep.sc);
     return;
   }
-  const float* p = gimg + (size_t)yc * W + x0;
-  R2L_PRAGMA_UNROLL
-  for (int k = 0; k < 3; ++k) s.g[k] = r2l_load_f4_nt(p + (size_t)k * plane);  // read once: nontemporal (as kernel B1)
+  if constexpr (IO == R2L_IO_F32) {
+    const float* p = gimg + (size_t)yc * W + x0;
+    R2L_PRAGMA_UNROLL
+    for (int k = 0; k < 3; ++k) s.g[k] = r2l_load_f4_nt(p + (size_t)k * plane);  // read once: nontemporal (as kernel B1)
+  }
 }
 
 // ================================================================================================
@@ -101,7 +132,7 @@ R2L_HD void r2l_bnr_lane_sums(const r2l_p2* acc, bool ok, int lane, double* tots
     for (int i = 0; i < 6; ++i) tots[i] += part[i];
   }
 }
-template <bool U16, bool EPI>
+template <bool U16, bool EPI, int IO = R2L_IO_F32>
 R2L_HD void r2l_bnr_item(const R2LBnrArgs& ba, int item, int lane, const float mean[3], const float istd[3], double* tots) {
   const R2LFwdStreamArgs& a = ba.s;
   R2LFoldedRef F = R2L_FOLDED_REF(a.F);
@@ -117,7 +148,7 @@ R2L_HD void r2l_bnr_item(const R2LBnrArgs& ba, int item, int lane, const float m
   const int y1 = (y0 + a.band_h < a.H) ? y0 + a.band_h : a.H;
   const size_t img = (size_t)b * plane;
   const float* ypimg = a.yp_in + img;
-  const float* gimg = ba.gout + (size_t)b * 3 * plane;
+  const float* gimg = r2l_io_at<IO>(ba.gout, (size_t)b * 3 * plane);
   R2LFaState st;
   r2l_p2 acc[6];
   float piv[3] = {0.5f, 0.5f, 0.5f};  // (unused by this mode)
@@ -126,7 +157,7 @@ R2L_HD void r2l_bnr_item(const R2LBnrArgs& ba, int item, int lane, const float m
   constexpr int PF = R2L_BNR_PF;
   R2LFsStage pf[PF];   // raw row q + 1
   R2LFaStage pfy[PF];  // Y' row q + 2
-  R2LBpStage pfg[PF];  // grad_out row q
+  R2LBpStageT<IO> pfg[PF];  // grad_out row q
   R2L_PRAGMA_UNROLL
   for (int i = 0; i < PF; ++i) {
     r2l_fa_fetch_raw<U16>(a, img, r2l_mirror(y0 - 3 + i, a.H), x0, le, re, lane, pf[(2 + i) % PF]);
@@ -144,7 +175,7 @@ R2L_HD void r2l_bnr_item(const R2LBnrArgs& ba, int item, int lane, const float m
   R2L_BNR_LOAD_STEP(4, y0 - 2)
   R2L_BNR_LOAD_STEP(5, y0 - 1)
   R2L_PRAGMA_UNROLL
-  for (int i = 0; i < PF; ++i) r2l_bp_fetch_g<EPI>(gimg, plane, y0 + i, a.H, a.W, x0, a.ep, pfg[i % PF]);
+  for (int i = 0; i < PF; ++i) r2l_bp_fetch_g<EPI, IO>(gimg, plane, y0 + i, a.H, a.W, x0, a.ep, pfg[i % PF]);
   for (int qb = y0; qb < y1; qb += 6) {
     R2L_PROGRESS_PRIO(qb - y0, y1 - y0);
 #define R2L_BNR_STEP(K)                                                                                   \
@@ -154,10 +185,11 @@ R2L_HD void r2l_bnr_item(const R2LBnrArgs& ba, int item, int lane, const float m
     r2l_p2 gk[3][2];                                                                                      \
     R2L_PRAGMA_UNROLL                                                                                     \
     for (int k = 0; k < 3; ++k) {                                                                         \
-      gk[k][0] = r2l_mk2(pfg[K % PF].g[k].x, pfg[K % PF].g[k].y);                                         \
-      gk[k][1] = r2l_mk2(pfg[K % PF].g[k].z, pfg[K % PF].g[k].w);                                         \
+      const r2l_f4 g4_ = pfg[K % PF].ch(k);                                                               \
+      gk[k][0] = r2l_mk2(g4_.x, g4_.y);                                                                   \
+      gk[k][1] = r2l_mk2(g4_.z, g4_.w);                                                                   \
     }                                                                                                     \
-    r2l_bp_fetch_g<EPI>(gimg, plane, q + PF, a.H, a.W, x0, a.ep, pfg[K % PF]); /* (rows past H: clamped, never counted) */ \
+    r2l_bp_fetch_g<EPI, IO>(gimg, plane, q + PF, a.H, a.W, x0, a.ep, pfg[K % PF]); /* (rows past H: clamped, never counted) */ \
     if (r2l_opaque_true())                                                                                \
       r2l_fa_step<K, false, false, true>(a, st, acc, piv, q, y0, false, nullptr, plane, x0, mean, istd, gk, \
                                           q < y1 ? 1.f : 0.f);                                            \
@@ -173,7 +205,7 @@ R2L_HD void r2l_bnr_item(const R2LBnrArgs& ba, int item, int lane, const float m
 #undef R2L_BNR_LOAD_STEP
   r2l_bnr_lane_sums(acc, in_w, lane, tots);
 }
-template <bool U16, bool EPI, int NWV>
+template <bool U16, bool EPI, int NWV, int IO = R2L_IO_F32>
 R2L_BLOCKFN void r2l_bnr_planes_block(const R2LBnrArgs& ba, int bid, int nblk, float* lds) {
   const R2LFwdStreamArgs& a = ba.s;
   constexpr int NT = NWV * 64;
@@ -189,7 +221,7 @@ R2L_BLOCKFN void r2l_bnr_planes_block(const R2LBnrArgs& ba, int bid, int nblk, f
   if (lane < 6) tots[lane] = 0.0;
   R2L_PRAGMA_NOUNROLL
   for (int item = bid * NWV + wave; item < a.nitems; item += nblk * NWV)
-    r2l_bnr_item<U16, EPI>(ba, item, lane, mean, istd, tots);
+    r2l_bnr_item<U16, EPI, IO>(ba, item, lane, mean, istd, tots);
   // ---- the wavefronts' float64 totals -> (high, low) float32 halves per workgroup -> the shared tree (as r2l_fs_stats_finish)
   R2L_LDS_BARRIER();
   if (tid < 6) {
@@ -262,8 +294,8 @@ R2L_HD void r2l_bp_swap(R2LBpAcc& A, float* bank /* this lane's 40 floats, [chun
 #define R2L_BPS_FULL (R2L_BPS_STENCIL | R2L_BPS_GAMMA | R2L_BPS_GYPP)
 // one output row y (K = y mod 6, row parity K & 1); the windows hold V(y-1 .. y+1) and Y'(y-2 .. y+2).  GUV: the chroma
 // gradients gU, gV of the row are stored too (planes gub, gvb: the input of r2l_bwd_raw_plane_block, d/d raw)
-template <int K, bool GUV = false, int SEL = R2L_BPS_FULL>
-R2L_HD void r2l_bp_step(const R2LBwd1Args& a, R2LBpState& st, R2LBpAcc& A, const R2LBpStage& gs, int y, bool store_ok,
+template <int K, bool GUV = false, int SEL = R2L_BPS_FULL, class GS = R2LBpStage>
+R2L_HD void r2l_bp_step(const R2LBwd1Args& a, R2LBpState& st, R2LBpAcc& A, const GS& gs, int y, bool store_ok,
                         float* gyb, int x0, const R2LBnConsts& bc, float* gub = nullptr, float* gvb = nullptr) {
   constexpr int PY = K & 1;
   const int H = a.H;
@@ -298,7 +330,8 @@ R2L_HD void r2l_bp_step(const R2LBwd1Args& a, R2LBpState& st, R2LBpAcc& A, const
     r2l_p2 ggam = r2l_splat2(0.f);
     R2L_PRAGMA_UNROLL
     for (int k = 0; k < 3; ++k) {
-      const float g[4] = {gs.g[k].x, gs.g[k].y, gs.g[k].z, gs.g[k].w};
+      const r2l_f4 g4 = gs.ch(k);
+      const float g[4] = {g4.x, g4.y, g4.z, g4.w};
       R2L_PRAGMA_UNROLL
       for (int p = 0; p < 2; ++p) {
         r2l_p2 rgb = r2l_pmul(r2l_splat2(F.M2[k * 3]), ypp[p]);
@@ -447,7 +480,7 @@ struct R2LBpSelect {
 // pass has no parity banks, no LDS swap, and -- without R2L_BPS_GAMMA either -- no reduction at all: a pure map.  PF_: rows of
 // raw / Y' in flight (the reduced forms that run three wavefronts per SIMD keep one: 10 registers less, R2L_BPS_PF)
 #define R2L_BPS_PF 1
-template <bool U16, bool EPI, bool GUV = false, int SEL = R2L_BPS_FULL, int PF_ = R2L_BP_PF>
+template <bool U16, bool EPI, bool GUV = false, int SEL = R2L_BPS_FULL, int PF_ = R2L_BP_PF, int IO = R2L_IO_F32>
 R2L_BLOCKFN void r2l_bwd1_plane_block(const R2LBwd1Args& a, int bid, int nblk, float* lds, float* guv = nullptr,
                                       const R2LBpSelect* sel = nullptr) {
   static_assert(!GUV || (!U16 && !EPI), "the chroma gradient planes are for float32 frames without an epilogue");
@@ -498,21 +531,21 @@ R2L_BLOCKFN void r2l_bwd1_plane_block(const R2LBwd1Args& a, int bid, int nblk, f
     const int y1 = (y0 + band_h < a.H) ? y0 + band_h : a.H;
     const size_t img = (size_t)b * plane;
     const float* ypimg = a.yp + img;
-    const float* gimg = a.gout + (size_t)b * 3 * plane;
+    const float* gimg = r2l_io_at<IO>(a.gout, (size_t)b * 3 * plane);
     float* gyb = a.gypp + img;
     float* gub = GUV ? guv + img : nullptr;
     float* gvb = GUV ? guv + (size_t)a.B * plane + img : nullptr;
     R2LBpState st;
     R2LFsStage pf[PF];   // raw row q + 1
     R2LFaStage pfy[PF];  // Y' row q + 2
-    R2LBpStage pfg[PFG];  // grad_out row q
+    R2LBpStageT<IO> pfg[PFG];  // grad_out row q
     R2L_PRAGMA_UNROLL
     for (int i = 0; i < PF; ++i) {
       r2l_fa_fetch_raw<U16>(sa, img, r2l_mirror(y0 - 3 + i, a.H), x0, le, re, lane, pf[(2 + i) % PF]);
       r2l_fa_fetch(ypimg, y0 - 2 + i, a.H, a.W, x0, le, re, lane, pfy[(2 + i) % PF]);
     }
     R2L_PRAGMA_UNROLL
-    for (int i = 0; i < PFG; ++i) r2l_bp_fetch_g<EPI>(gimg, plane, y0 + i, a.H, a.W, x0, a.ep, pfg[i % PFG]);  // (first used at K = 0)
+    for (int i = 0; i < PFG; ++i) r2l_bp_fetch_g<EPI, IO>(gimg, plane, y0 + i, a.H, a.W, x0, a.ep, pfg[i % PFG]);  // (first used at K = 0)
 #define R2L_BP_LOAD_STEP(K, q)                                                                          \
   r2l_fs_convert<U16>(sa, F, pf[(K) % PF], le, re, st.v[((K) + 1) % 3]);                                \
   r2l_fa_build(pfy[(K) % PF], (unsigned)((q) + 2) < (unsigned)a.H, le, re, st.yp[((K) + 2) % 6]);       \
@@ -530,8 +563,8 @@ R2L_BLOCKFN void r2l_bwd1_plane_block(const R2LBwd1Args& a, int bid, int nblk, f
   {                                                                                                     \
     const int q = qb + K;                                                                               \
     R2L_BP_LOAD_STEP(K, q)                                                                              \
-    const R2LBpStage g_ = pfg[(K) % PFG];                                                               \
-    r2l_bp_fetch_g<EPI>(gimg, plane, q + PFG, a.H, a.W, x0, a.ep, pfg[(K) % PFG]);                      \
+    const R2LBpStage g_ = r2l_bp_widen(pfg[(K) % PFG]);                                                 \
+    r2l_bp_fetch_g<EPI, IO>(gimg, plane, q + PFG, a.H, a.W, x0, a.ep, pfg[(K) % PFG]);                  \
     if (K && (SEL & R2L_BPS_STENCIL)) r2l_bp_swap(A, bank); /* the bank of this row's parity into the registers */ \
     if (r2l_opaque_true()) r2l_bp_step<K, GUV, SEL>(a, st, A, g_, q, in_w && q < y1, gyb, x0, bc, gub, gvb); \
   }

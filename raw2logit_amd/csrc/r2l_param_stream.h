@@ -215,7 +215,8 @@ R2L_HD void r2l_fs_stencil_plain(const float* r0, const float* r1, const float* 
 // STATS: 0 none; 1 the streaming kernel's form (under `a.stat_partial && store_ok`); 2 branch-free, weighted with smask
 // (1 for the pixels that count, 0 for the others), the pivot taken in the band's first row (`first`); 3 the sums of BatchNorm's
 // backward over grad_out (gk: this row's grad_out as pairs)
-template <bool EPI, int STATS>
+// IO: the type `ob` holds (R2L_IO_*): a 16-bit output is narrowed here, at the store, and nowhere else
+template <bool EPI, int STATS, int IO = R2L_IO_F32>
 R2L_HD void r2l_fs_colour(const R2LFwdStreamArgs& a, R2LFoldedRef F, r2l_p2* acc, float* piv, const r2l_p2 ypp[2],
                           const r2l_p2 u[2], const r2l_p2 v[2], int y, int y0, int x0, float* ob, unsigned plane,
                           bool store_ok, const float mean[3], const float istd[3], float smask = 0.f,
@@ -265,7 +266,10 @@ R2L_HD void r2l_fs_colour(const R2LFwdStreamArgs& a, R2LFoldedRef F, r2l_p2* acc
       s4.y = x[0][1];
       s4.z = x[1][0];
       s4.w = x[1][1];
-      if (!EPI) {
+      if constexpr (IO != R2L_IO_F32) {
+        static_assert(!EPI, "the output epilogue stores float32");
+        r2l_store_h4_nt((unsigned short*)ob + (unsigned)k * plane + off0, r2l_io_narrow4<IO>(s4));  // (around the caches, as below)
+      } else if (!EPI) {
         // the output goes AROUND the caches (nontemporal): 12 B/px that this pass never reads again would otherwise push the raw
         // frames and Y' -- which the neighbouring bands and the backward re-read -- out of the memory-side cache: apply pass
         // 72.8 -> 64.9 us at 64x512x512, bn_reduce (which reads the output later) +0.5 (profiles/r05_nt_stores.txt;
@@ -295,7 +299,7 @@ R2L_HD void r2l_fs_colour(const R2LFwdStreamArgs& a, R2LFoldedRef F, r2l_p2* acc
 
 // K: ring position of the step (window / chroma-ring slots); PYQ: parity of row q.  The driver runs every group of 6 steps
 // in full (r2l_fwd_stream_block) -- rows past the band's end are computed and neither stored nor counted
-template <int NW, bool U16, int K, bool EPI, int PYQ = (K & 1)>
+template <int NW, bool U16, int K, bool EPI, int PYQ = (K & 1), int IO = R2L_IO_F32>
 R2L_HD void r2l_fs_step(const R2LFwdStreamArgs& a, R2LFsState& st, int q, int y0, int y1, bool le, bool re,
                         int wave, int lane, float* ex, r2l_f4* fifo, float* ob, float* ypb, unsigned plane, int x0,
                         bool store_ok, const float mean[3], const float istd[3], float smask) {
@@ -431,7 +435,7 @@ R2L_HD void r2l_fs_step(const R2LFwdStreamArgs& a, R2LFsState& st, int q, int y0
     const r2l_p2 u[2] = {r2l_mk2(fu.x, fu.y), r2l_mk2(fu.z, fu.w)}, v[2] = {r2l_mk2(fv.x, fv.y), r2l_mk2(fv.z, fv.w)};
     // (statistics: the branch-free form, weighted with the lane's 0 / 1 mask -- 6 v_pk_mul_f32 per row step where the
     // conditional form `if (a.stat_partial && store_ok)` is if-converted into 24 v_cndmask_b32)
-    r2l_fs_colour<EPI, 2>(a, F, st.acc, st.piv, ypp, u, v, y, y0, x0, ob, plane, store_ok, mean, istd, smask, y == y0);
+    r2l_fs_colour<EPI, 2, IO>(a, F, st.acc, st.piv, ypp, u, v, y, y0, x0, ob, plane, store_ok, mean, istd, smask, y == y0);
     const unsigned off0 = (unsigned)y * (unsigned)a.W + (unsigned)x0;
     // Y'(y), kept for kernel B1 of the backward: the middle row of the blur's window, stored last (the step's
     // registers are free here; next to the sharpen, or in front of the colour code, the kernel spills)
@@ -557,7 +561,7 @@ R2L_BLOCKFN void r2l_fs_stats_finish(const R2LFwdStreamArgs& a_, int bid, int nb
 
 // SONLY: the statistics pass of train-mode BatchNorm as its own instantiation -- no output, no BatchNorm constants, no
 // epilogue: fewer live scalars (the general kernel parks ~25 of them per row step in vector lanes, v_readlane_b32)
-template <int NW, bool U16, bool EPI = false, bool SONLY = false>
+template <int NW, bool U16, bool EPI = false, bool SONLY = false, int IO = R2L_IO_F32>
 R2L_BLOCKFN void r2l_fwd_stream_block(const R2LFwdStreamArgs& a, int bid, int nblk, float* lds) {
   constexpr int NT = NW * 64;
 #if defined(R2L_EXP_STAMPS) && !defined(R2L_EMUL)
@@ -614,7 +618,7 @@ R2L_BLOCKFN void r2l_fwd_stream_block(const R2LFwdStreamArgs& a, int bid, int nb
     const int y0 = band * a.band_h;
     const int y1 = (y0 + a.band_h < a.H) ? y0 + a.band_h : a.H;
     const size_t img = (size_t)b * plane;
-    float* ob = (!SONLY && a.out) ? a.out + (size_t)b * 3 * plane : nullptr;
+    float* ob = (!SONLY && a.out) ? r2l_io_at<IO>(a.out, (size_t)b * 3 * plane) : nullptr;
     float* ypb = a.yp_out ? a.yp_out + (size_t)b * plane : nullptr;
     R2L_PRAGMA_UNROLL
     for (int i = 0; i < 6; ++i) st.acc[i] = r2l_splat2(0.f);
@@ -668,7 +672,7 @@ R2L_BLOCKFN void r2l_fwd_stream_block(const R2LFwdStreamArgs& a, int bid, int nb
       const int rr_ = (q + 1 + PF < q1) ? q + 1 + PF : q1;                                                      \
       r2l_fs_fetch_bf<U16>(a, img, r2l_mirror(rr_, a.H), x0, le, re, lane, pf[K % PF]);                         \
     }                                                                                                           \
-    r2l_fs_step<NW, U16, K, EPI, (K + 1) & 1>(a, st, q, y0, y1, le, re, wave, lane, ex, fifo,             \
+    r2l_fs_step<NW, U16, K, EPI, (K + 1) & 1, IO>(a, st, q, y0, y1, le, re, wave, lane, ex, fifo,         \
                                                    SONLY ? nullptr : ob, ypb, plane, x0, store_ok, mean, istd, smask); \
     R2L_FS_STEP_STAMP(sb + K)                                                                                   \
   }
@@ -776,7 +780,7 @@ struct R2LFaState {
   float v[3][6];   // V rows (slot = row mod 3)
   float yp[6][8];  // Y' rows (slot = row mod 6)
 };
-template <int K, bool EPI, bool STATS, bool BNR = false>
+template <int K, bool EPI, bool STATS, bool BNR = false, int IO = R2L_IO_F32>
 R2L_HD void r2l_fa_step(const R2LFwdStreamArgs& a, R2LFaState& st, r2l_p2* acc, float* piv, int y, int y0,
                         bool store_ok, float* ob, unsigned plane, int x0, const float mean[3], const float istd[3],
                         const r2l_p2 (*gk)[2] = nullptr, float rowf = 0.f) {
@@ -807,7 +811,7 @@ R2L_HD void r2l_fa_step(const R2LFwdStreamArgs& a, R2LFaState& st, r2l_p2* acc, 
   if (BNR)
     r2l_fs_colour<false, 3>(a, Fc, acc, piv, ypp, u, v, y, y0, x0, nullptr, plane, false, mean, istd, rowf, false, gk);
   else
-    r2l_fs_colour<EPI, STATS ? 2 : 0>(a, Fc, acc, piv, ypp, u, v, y, y0, x0, ob, plane, store_ok, mean, istd,
+    r2l_fs_colour<EPI, STATS ? 2 : 0, IO>(a, Fc, acc, piv, ypp, u, v, y, y0, x0, ob, plane, store_ok, mean, istd,
                                       store_ok ? 1.f : 0.f, K == 0 && y == y0);
 }
 
@@ -820,7 +824,7 @@ R2L_HD void r2l_fa_step(const R2LFwdStreamArgs& a, R2LFaState& st, r2l_p2* acc, 
 // The apply pass runs one wavefront per workgroup and one item per wavefront.
 #define R2L_FA_LDS_FLOATS(NWV, STATS) ((STATS) ? 16 + R2L_FS_RED_FLOATS(NWV) + 12 * (NWV) : 4)
 // one work item = (image, band, strip), strips fastest: neighbouring items share halo rows and strip edges
-template <bool U16, bool EPI, bool STATS>
+template <bool U16, bool EPI, bool STATS, int IO = R2L_IO_F32>
 R2L_HD void r2l_fa_item(const R2LFwdStreamArgs& a, int item, int lane, const float mean[3], const float istd[3],
                         double* tots) {
   R2LFoldedRef F = R2L_FOLDED_REF(a.F);
@@ -837,7 +841,7 @@ R2L_HD void r2l_fa_item(const R2LFwdStreamArgs& a, int item, int lane, const flo
   const int y0 = band * a.band_h;
   const int y1 = (y0 + a.band_h < a.H) ? y0 + a.band_h : a.H;
   const size_t img = (size_t)b * plane;
-  float* ob = STATS ? nullptr : a.out + (size_t)b * 3 * plane;
+  float* ob = STATS ? nullptr : r2l_io_at<IO>(a.out, (size_t)b * 3 * plane);
   if (!STATS) __builtin_assume(ob != nullptr);
   const float* ypimg = a.yp_in + img;
   R2LFaState st;
@@ -875,7 +879,7 @@ R2L_HD void r2l_fa_item(const R2LFwdStreamArgs& a, int item, int lane, const flo
     const int q = qb + K;                                                                               \
     R2L_FA_LOAD_STEP(K, q)                                                                              \
     if (!STATS || r2l_opaque_true())                                                                    \
-      r2l_fa_step<K, EPI, STATS>(a, st, acc, piv, q, y0, in_w && q < y1, ob, plane, x0, mean, istd);    \
+      r2l_fa_step<K, EPI, STATS, false, IO>(a, st, acc, piv, q, y0, in_w && q < y1, ob, plane, x0, mean, istd); \
   }
     R2L_FA_STEP(0)
     R2L_FA_STEP(1)
@@ -888,7 +892,7 @@ R2L_HD void r2l_fa_item(const R2LFwdStreamArgs& a, int item, int lane, const flo
 #undef R2L_FA_LOAD_STEP
   if (STATS) r2l_fs_lane_sums(acc, piv, in_w ? 4.0 * (double)(y1 - y0) : 0.0, in_w, lane, tots);
 }
-template <bool U16, bool EPI, bool STATS, int NWV>
+template <bool U16, bool EPI, bool STATS, int NWV, int IO = R2L_IO_F32>
 R2L_BLOCKFN void r2l_fwd_apply_block(const R2LFwdStreamArgs& a, int bid, int nblk, float* lds) {
   // (the wavefront index as a SCALAR: the work item, its rows and the weight set of a row must not look lane-dependent)
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -905,7 +909,7 @@ R2L_BLOCKFN void r2l_fwd_apply_block(const R2LFwdStreamArgs& a, int bid, int nbl
     // one item per wavefront; NWV wavefronts per workgroup only because the dispatcher starts ~250 workgroups per
     // microsecond: 4,096 single-wavefront workgroups take 15 us to launch (tests/timeline_fwd.py)
     const int item = bid * NWV + wave;
-    if (item < a.nitems) r2l_fa_item<U16, EPI, false>(a, item, lane, mean, istd, nullptr);
+    if (item < a.nitems) r2l_fa_item<U16, EPI, false, IO>(a, item, lane, mean, istd, nullptr);
     R2L_TL_END(a, bid)
   } else {
     float* red = lds + 16;

@@ -324,6 +324,36 @@ def epilogue_supported(raw, module):
     """can the fused kernels write this module's output through an epilogue?  (no additive layer: its gradient is
     summed in the ISP's own layout; rotations by 90 degrees need square frames -- checked per draw)"""
     return module.additive_layer is None
+
+
+# the 16-bit types the fused step can write its output in / read its cotangent in (include/r2l_isp.h: R2L_IO_*)
+IO_F32, IO_BF16, IO_F16 = 0, 1, 2
+IO_CODES = {None: IO_F32, torch.float32: IO_F32, torch.bfloat16: IO_BF16, torch.float16: IO_F16}
+
+
+def io_supported(raw, module, dtype=None, keep=None):
+    """do the fused kernels write this module's output directly as `dtype` (default: module.output_dtype) for these frames
+    (r2l_isp_io_supported, the predicate r2l_isp_step_fwd_io / _bwd_io use)?  float32 / None: always.  A 16-bit type: no
+    additive layer, W % 4 == 0, W <= 2048, and a step whose backward will run (`keep`; default: grad mode is on and the frames or
+    a parameter require grad) -- elsewhere ParametrizedProcessing runs the float32 kernels and casts."""
+    dtype = getattr(module, 'output_dtype', None) if dtype is None else dtype
+    if dtype not in IO_CODES:
+        raise _lib.R2LError(f'output_dtype must be None, torch.float32, torch.bfloat16 or torch.float16, got {dtype!r}')
+    io = IO_CODES[dtype]
+    if io == IO_F32:
+        return True
+    if raw.ndim != 3 or not (raw.dtype == torch.float32 or raw.dtype in U16_DTYPES):
+        return False
+    if keep is None:
+        keep = torch.is_grad_enabled() and (raw.requires_grad or any(p.requires_grad for p in (
+            module.black_level, module.white_balance, module.colour_correction, module.gamma_correct, module.debayer.weight,
+            module.sharpening_filter.weight, module.gaussian_blur.weight)))
+    lib, _ = _lib.library_for(raw)
+    B, H, W = raw.shape
+    return bool(lib.r2l_isp_io_supported(io, int(raw.dtype in U16_DTYPES), int(module.additive_layer is not None), B, H, W,
+                                         _STEP_KEEP_LUMA if keep else 0))
+
+
 def _raw_grad_why(f32, W, has_additive, epi=False):
     """why r2l_isp_step_bwd_raw cannot produce d/d raw for such a call, or None if it can"""
     if epi:
@@ -377,11 +407,13 @@ class _IspFused(torch.autograd.Function):
     gradient the kernels produce.  With several ranks and train-mode BatchNorm each call splits in two around an
     all-gather of 7 resp. 6 doubles (RCCL).  selective (ParametrizedProcessing.selective_backward): the backward hands
     needs_input_grad to the library (r2l_isp_step_bwd_select), which runs reduced passes where only the gamma, blur or raw
-    gradients are asked for; parameters that did not ask get None either way."""
+    gradients are asked for; parameters that did not ask get None either way.  out_dtype (ParametrizedProcessing.output_dtype):
+    torch.bfloat16 / torch.float16 -- `out` is allocated and written in that type and the cotangent is read in it
+    (r2l_isp_step_fwd_io / r2l_isp_step_bwd_io; the caller has asked io_supported); None / torch.float32: the calls above."""
 
     @staticmethod
     def forward(ctx, raw, bl, wb, ccm, gamma, deb, sharp, blur, m1, m2, additive, bn_mode, bn_module, eps,
-                momentum, group, bits=16, grad_mode=True, epilogue=None, selective=False):
+                momentum, group, bits=16, grad_mode=True, epilogue=None, selective=False, out_dtype=None):
         raw, denom = _raw_arg(raw, bits)
         params = (bl, wb, ccm, gamma, deb, sharp, blur, m1, m2)
         sizes = (4, 3, 9, 1, 81, 9, 25, 9, 9)
@@ -412,7 +444,11 @@ class _IspFused(torch.autograd.Function):
         if epi and (additive is not None or ((epilogue[2] & 1) and H != W)):
             raise _lib.R2LError('this call cannot take an output epilogue (no additive layer; square frames for a rotation '
                                 'by 90 degrees): apply the augmentation to the output instead')
-        out = torch.empty((B, 3, W, H) if (epi and (epilogue[2] & 1)) else (B, 3, H, W), dtype=torch.float32, device=dev)
+        if out_dtype not in IO_CODES:
+            raise _lib.R2LError(f'output dtype must be None, torch.float32, torch.bfloat16 or torch.float16, got {out_dtype!r}')
+        io = IO_CODES[out_dtype]
+        out = torch.empty((B, 3, W, H) if (epi and (epilogue[2] & 1)) else (B, 3, H, W),
+                          dtype=out_dtype if io else torch.float32, device=dev)
         rm = rv = nbt = None
         if bn_mode == BN_TRAIN:
             rm, rv, nbt = _bn_buffers(bn_module, dev)
@@ -427,6 +463,12 @@ class _IspFused(torch.autograd.Function):
         keep = _STEP_KEEP_LUMA if (grad_mode and any(ctx.needs_input_grad[:8])) else 0
 
         def call(phase, gathered):
+            if io:
+                lib.check(lib.r2l_isp_step_fwd_io(ptr(raw), int(denom is not None), denom or 1.0, table, ptr(additive),
+                                                  bn_mode, ptr(rm), ptr(rv), ptr(nbt), float(eps), mom, ptr(out), io, ptr(ws),
+                                                  nws, B, H, W, nranks, phase | keep | epi, ptr(gathered), stream),
+                          'r2l_isp_step_fwd_io')
+                return
             lib.check(lib.r2l_isp_step_fwd(ptr(raw), int(denom is not None), denom or 1.0, table, ptr(additive),
                                            bn_mode, ptr(rm), ptr(rv), ptr(nbt), float(eps), mom, ptr(out), ptr(ws),
                                            nws, B, H, W, nranks, phase | keep | epi, ptr(gathered), stream),
@@ -452,6 +494,7 @@ class _IspFused(torch.autograd.Function):
         ctx.save_for_backward(raw, additive, out)
         ctx.ws = ws
         ctx.selective = bool(selective)
+        ctx.io = io
         ctx.raw_why = _raw_grad_why(denom is None, W, additive is not None, bool(epi)) if ctx.needs_input_grad[0] else None
         return out
 
@@ -462,7 +505,12 @@ class _IspFused(torch.autograd.Function):
         if need_r and ctx.raw_why is not None:
             raise _lib.R2LError(ctx.raw_why + '; gradients w.r.t. such raw frames are defined on the staged path '
                                 '(ParametrizedProcessing routes them there)')
-        gout = _f32c(gout, 'grad_out')
+        if ctx.io:
+            if gout.dtype != out.dtype:
+                raise TypeError(f'grad_out must be {out.dtype} like the output, got {gout.dtype}')
+            gout = gout if gout.is_contiguous() else gout.contiguous()
+        else:
+            gout = _f32c(gout, 'grad_out')
         B, H, W = raw.shape
         lib, stream = _lib.library_for(raw)
         ws, nws = ctx.ws, ctx.ws.numel()
@@ -482,6 +530,13 @@ class _IspFused(torch.autograd.Function):
         mask = grad_mask(ctx.needs_input_grad) if ctx.selective else 0
 
         def call(phase, gathered):
+            if ctx.io:      # (the library runs the full route for any mask; grad_raw goes with GRAD_RAW)
+                m = mask or ((GRAD_RAW if need_r else 0) | (127 if (need_p or need_r) else 0))
+                lib.check(lib.r2l_isp_step_bwd_io(ptr(raw), int(denom is not None), denom or 1.0, ptr(additive), ptr(gout),
+                                                  ctx.io, ptr(out), ptr(gp), ptr(gadd), ctx.bn_mode, ptr(ws), nws, B, H, W,
+                                                  ctx.nranks, phase | ctx.keep, ptr(gathered), stream, ptr(graw),
+                                                  ptr(scratch), nscr, m), 'r2l_isp_step_bwd_io')
+                return
             if mask:
                 lib.check(lib.r2l_isp_step_bwd_select(ptr(raw), int(denom is not None), denom or 1.0, ptr(additive), ptr(gout),
                                                       ptr(out), ptr(gp), ptr(gadd), ctx.bn_mode, ptr(ws), nws, B, H, W,
@@ -510,19 +565,20 @@ class _IspFused(torch.autograd.Function):
             for i, ((_, off, n), shape) in enumerate(zip(PARAM_LAYOUT, ctx.shapes)):
                 if ctx.needs_input_grad[1 + i]:
                     grads[i] = gp[off:off + n].view(shape)
-        return (graw, *grads, None, None, gadd, None, None, None, None, None, None, None, None, None)
+        return (graw, *grads, None, None, gadd, None, None, None, None, None, None, None, None, None, None)
 
 
-def isp_fused(raw, module, bn_mode=BN_NONE, group=None, epilogue=None):
+def isp_fused(raw, module, bn_mode=BN_NONE, group=None, epilogue=None, out_dtype=None):
     """fused forward of a ParametrizedProcessing-shaped module (parameters by the reference's names).  epilogue =
-    (hflip, vflip, k): the output leaves the kernels as rot90^k(vflip(hflip(out)))."""
+    (hflip, vflip, k): the output leaves the kernels as rot90^k(vflip(hflip(out))).  out_dtype = torch.bfloat16 / torch.float16:
+    the kernels write the output in that type (where io_supported says so; no epilogue then)."""
     bn = module.batch_norm
     return _IspFused.apply(raw, module.black_level, module.white_balance, module.colour_correction,
                            module.gamma_correct, module.debayer.weight, module.sharpening_filter.weight,
                            module.gaussian_blur.weight, module.M_RGB_2_YUV, module.M_YUV_2_RGB,
                            module.additive_layer, bn_mode, bn, bn.eps if bn is not None else 1e-5,
                            bn.momentum if bn is not None else None, group, getattr(module, 'raw_bits', 16),
-                           torch.is_grad_enabled(), epilogue, bool(getattr(module, 'selective_backward', False)))
+                           torch.is_grad_enabled(), epilogue, bool(getattr(module, 'selective_backward', False)), out_dtype)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -14,6 +14,8 @@ and backward as two graphs around static-buffer copies, is SLOWER than eager on 
     g.replay()                                    # g.out, p.grad of every parameter, the running statistics: updated
     g = StepGraph(processor, raw, None, loss=lambda rgb: criterion(head(rgb), target), loss_modules=(head,))
 
+A processor with `output_dtype` set (a bfloat16 / float16 output) is captured like any other: `cotangent` is then a tensor of that type.
+
 The processor must not have run on another stream before (its AccumulateGrad nodes are created by the warm-up here, on
 the capture's side stream).
 

@@ -223,12 +223,21 @@ class ParametrizedProcessing(nn.Module):
     fused backward computes only the gradients autograd asks for (r2l_isp_step_bwd_select): with nothing but ``gamma_correct``
     and / or ``gaussian_blur.weight`` trainable (train.py's --adv_parameters with one name), or a frozen processor under frames
     that require grad (with ``fused_raw_grad``), reduced passes run instead of all 155 sums; any other set of trainable
-    parameters takes the full backward unchanged.  Parameters that do not require grad get no gradient either way."""
+    parameters takes the full backward unchanged.  Parameters that do not require grad get no gradient either way.
+    ``output_dtype`` (opt-in, default None = float32) -- ``torch.bfloat16`` or ``torch.float16``: the module returns
+    ``float32_result.to(output_dtype)``, for a task model that runs under torch.autocast / precision=16 and hands back a
+    cotangent of that type.  Where the fused kernels serve such a call (functional.io_supported: a step whose backward will
+    run, no additive layer, W % 4 == 0, W <= 2048, no armed output epilogue, ``track_stages`` False) they write the 16-bit
+    output and read the 16-bit cotangent themselves -- 6 instead of 12 bytes per pixel each, no cast passes; everywhere else
+    the float32 path runs and torch casts.  Both give bit-identical values; the arithmetic, the parameters, ``.stages`` and
+    BatchNorm's statistics stay float32 (``.half()`` on the module still raises).  Anything but None or those three dtypes
+    raises R2LError.  Opt-in until measured in real workloads."""
 
     raw_bits = 16
     supports_output_epilogue = True
     fused_raw_grad = False
     selective_backward = False
+    output_dtype = None
 
     def __init__(self, camera_parameters=None, track_stages=False, batch_norm_output=True):
         super().__init__()
@@ -296,12 +305,19 @@ class ParametrizedProcessing(nn.Module):
         # of their output stores; on the staged path, or where the kernels cannot take it, the moves run as the separate
         # permutation kernel right here -- either way the caller gets the augmented batch
         epilogue = d.pop('_epilogue', None)
+        # `output_dtype` (opt-in): the fused kernels write bfloat16 / float16 themselves where they serve the call (never with
+        # an epilogue, which stores float32); elsewhere the float32 result is cast at the end -- the same values either way
+        odt = self.output_dtype
+        if odt not in F_.IO_CODES:
+            raise F_._lib.R2LError(f'output_dtype must be None, torch.float32, torch.bfloat16 or torch.float16, got {odt!r}')
+        io16 = odt if (F_.IO_CODES[odt] and epilogue is None and not self.track_stages and raw.dtype != torch.float64
+                       and F_.io_supported(raw, self, odt)) else None
         # `fused_raw_grad = True` (opt-in): frames that require grad take the fused kernels too where they can produce
         # d/d raw (float32 frames, W % 4 == 0, W <= 2048, no additive layer); the epilogue then runs after them
         needs_raw_grad = raw.requires_grad and torch.is_grad_enabled()
         fused_raw = needs_raw_grad and not self.track_stages and self.fused_raw_grad and F_.raw_grad_supported(raw, self)
         if fused_raw:
-            rgb = self._fused_forward(raw)
+            rgb = self._fused_forward(raw, None, io16)
             d['stages'] = _LazyStages(self, raw)
         elif self.track_stages or needs_raw_grad:
             from ..staged import staged_forward
@@ -313,7 +329,7 @@ class ParametrizedProcessing(nn.Module):
             odd = bool(epilogue is not None and (epilogue[2] & 1))
             fuse = epilogue is not None and F_.epilogue_supported(raw, self) and \
                 (not odd or (getattr(self, 'fuse_rot90', False) and raw.shape[-1] == raw.shape[-2]))
-            rgb = self._fused_forward(raw, epilogue if fuse else None)
+            rgb = self._fused_forward(raw, epilogue if fuse else None, io16)
             d['stages'] = _LazyStages(self, raw)
             if fuse:
                 epilogue = None
@@ -325,11 +341,14 @@ class ParametrizedProcessing(nn.Module):
             for stage in self.stages.values():
                 stage.retain_grad()
 
+        if odt is not None and rgb.dtype != odt:
+            rgb = rgb.to(odt)       # (autograd widens the cotangent; the stages stay float32)
+
         self.buffer['processed_rgb'] = rgb
 
         return rgb
 
-    def _fused_forward(self, raw, epilogue=None):
+    def _fused_forward(self, raw, epilogue=None, out_dtype=None):
         bn = self.batch_norm
         if bn is None:
             mode = F_.BN_NONE
@@ -337,4 +356,4 @@ class ParametrizedProcessing(nn.Module):
             mode = F_.BN_TRAIN      # batch statistics; running statistics are updated on the device
         else:
             mode = F_.BN_EVAL
-        return F_.isp_fused(raw, self, mode, self.process_group, epilogue)
+        return F_.isp_fused(raw, self, mode, self.process_group, epilogue, out_dtype)
