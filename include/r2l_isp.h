@@ -473,7 +473,8 @@ int r2l_corrupt(const float *x, float *y, int N, int C, int H, int W, int kind, 
  *                  keep_for_backward: also leave dS/d(mu2, E[y^2], E[xy]) of every pixel in the workspace
  *   r2l_ssim_bwd   grad_img2 = grad_ssim[0] * d mean-SSIM / d img2   (grad_ssim: device float scalar);
  *                  workspace_has_dmaps: the workspace is the one a keep_for_backward forward filled (else the
- *                  maps are recomputed first)
+ *                  maps are recomputed first).  grad_img2 may be img2 itself (in place): every element of img2
+ *                  is read by the lane that overwrites it, before it does, and by no other
  *   r2l_l2_fwd     ((x - y) ** 2).sum() (utils/base.py:342-343) -> sum double[1]; n elements, n % 4 == 0
  *   r2l_l2_bwd     grad_y = grad_sum[0] * 2 (y - x)
  * Images are (B,C,H,W) float32; workspace from r2l_aux_workspace_bytes().                              */

@@ -2573,6 +2573,20 @@ static int r2l_aux_check(const void* a, const void* b, int B, int C, int H, int 
     return r2l_fail(-1, std::string(who) + ": bad dimensions");
   return 0;
 }
+// workgroups of the two persistent SSIM kernels: one per 64x64 tile up to 512, which then walk the rest.  Diagnostic builds
+// take R2L_GRID_AUX instead (at most R2L_MAX_BLOCKS: the partials), so that tests can run the walk on a few dozen tiles.
+static int r2l_ssim_grid(int B, int C, int H, int W) {
+  const int ntiles = B * C * ((H + R2L_SSIM_T - 1) / R2L_SSIM_T) * ((W + R2L_SSIM_T - 1) / R2L_SSIM_T);
+  const int g = r2l_env_int("R2L_GRID_AUX", ntiles < 512 ? ntiles : 512);
+  return g < R2L_MAX_BLOCKS ? g : R2L_MAX_BLOCKS;
+}
+// workgroups of the grid-stride L2 kernel: one per 512 lanes x 4 floats up to `cap` (R2L_GRID_AUX: as above)
+static int r2l_l2_grid(size_t n, size_t cap) {
+  size_t g = (n / 4 + R2L_NT - 1) / R2L_NT;
+  if (g > cap) g = cap;
+  g = (size_t)r2l_env_int("R2L_GRID_AUX", (int)g);
+  return (int)(g < cap ? g : cap);
+}
 static int r2l_ssim_launch(const float* img1, const float* img2, float* partial, float* dmaps, int mode, int B,
                            int C, int H, int W, void* stream, int* grid_out) {
   R2LSsimArgs a;
@@ -2585,8 +2599,7 @@ static int r2l_ssim_launch(const float* img1, const float* img2, float* partial,
   a.H = H;
   a.W = W;
   a.mode = mode;
-  const int ntiles = B * C * ((H + R2L_SSIM_T - 1) / R2L_SSIM_T) * ((W + R2L_SSIM_T - 1) / R2L_SSIM_T);
-  *grid_out = ntiles < 512 ? ntiles : 512;
+  *grid_out = r2l_ssim_grid(B, C, H, W);
   return r2l_launch_ssim(a, *grid_out, stream);
 }
 int r2l_ssim_fwd(const float* img1, const float* img2, double* ssim_mean, void* workspace, size_t workspace_bytes,
@@ -2612,8 +2625,7 @@ int r2l_ssim_bwd(const float* img1, const float* img2, const float* grad_ssim, f
   if (!workspace_has_dmaps) {
     if (int e = r2l_ssim_launch(img1, img2, nullptr, dmaps, 2, B, C, H, W, stream, &grid)) return e;
   } else {
-    const int ntiles = B * C * ((H + R2L_SSIM_T - 1) / R2L_SSIM_T) * ((W + R2L_SSIM_T - 1) / R2L_SSIM_T);
-    grid = ntiles < 512 ? ntiles : 512;
+    grid = r2l_ssim_grid(B, C, H, W);
   }
   R2LSsimBwdArgs b;
   b.img1 = img1;
@@ -2633,20 +2645,17 @@ int r2l_l2_fwd(const float* x, const float* y, double* sum, void* workspace, siz
   if (!x || !y || !sum || !workspace) return r2l_fail(-1, "r2l_l2_fwd: null pointer");
   if (n == 0 || (n & 3)) return r2l_fail(-1, "r2l_l2_fwd: the element count must be a positive multiple of 4");
   if (workspace_bytes < sizeof(float) * R2L_MAX_BLOCKS) return r2l_fail(-2, "r2l_l2_fwd: workspace too small");
-  size_t g = (n / 4 + R2L_NT - 1) / R2L_NT;
-  if (g > R2L_MAX_BLOCKS) g = R2L_MAX_BLOCKS;
+  const int g = r2l_l2_grid(n, R2L_MAX_BLOCKS);
   R2LL2Args a{x, y, nullptr, nullptr, (float*)workspace, n};
-  if (int e = r2l_launch_l2(a, (int)g, stream)) return e;
-  R2LReduceRowsArgs r{a.partial, sum, (int)g, 1.0, nullptr};
+  if (int e = r2l_launch_l2(a, g, stream)) return e;
+  R2LReduceRowsArgs r{a.partial, sum, g, 1.0, nullptr};
   return r2l_launch_reduce_rows(r, 1, stream);
 }
 int r2l_l2_bwd(const float* x, const float* y, const float* grad_sum, float* grad_y, size_t n, void* stream) {
   if (!x || !y || !grad_sum || !grad_y) return r2l_fail(-1, "r2l_l2_bwd: null pointer");
   if (n == 0 || (n & 3)) return r2l_fail(-1, "r2l_l2_bwd: the element count must be a positive multiple of 4");
-  size_t g = (n / 4 + R2L_NT - 1) / R2L_NT;
-  if (g > 4096) g = 4096;
   R2LL2Args a{x, y, grad_sum, grad_y, nullptr, n};
-  return r2l_launch_l2(a, (int)g, stream);
+  return r2l_launch_l2(a, r2l_l2_grid(n, 4096), stream);
 }
 
 #ifdef R2L_TEST_HOOKS
