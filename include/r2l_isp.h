@@ -367,6 +367,30 @@ int r2l_static_fwd_opts(const void *raw, int frames, float denom, float *out, in
                         const double *options_host, const float *mean_std_host, void *workspace,
                         size_t workspace_bytes, void *stream);
 
+/* ---- 16-bit output of the static chains (a task model under torch.autocast / precision=16 behind StaticProcessing) ---------------
+ * r2l_static_fwd_io = r2l_static_fwd_opts that writes `out` as bfloat16 (out_io = R2L_IO_BF16) or IEEE float16 (R2L_IO_F16):
+ * every element is the float32 value r2l_static_fwd_opts writes -- computed in float64 / float32, rounded to float32 and, with
+ * mean_std_host, normalised in float32 exactly as there -- rounded once more, to nearest even: bit for bit what
+ * torch.Tensor.to(dtype) makes of the float32 result.  6 instead of 12 bytes per pixel stored.  options_host and mean_std_host
+ * may be NULL as in r2l_static_fwd_opts.  out_io = R2L_IO_F32: exactly r2l_static_fwd_opts, no further condition.
+ * A 16-bit call is served where ONE launch of a row-streaming kernel runs the chain:
+ *   demosaic bilinear or Malvar2004; W % 4 == 0 and W <= 2048 (1024 behind unsharp_masking);
+ *   the short chain (no sharpening, no denoising) on float32, 16-bit-container and float64 frames;
+ *   sharpening_filter / unsharp_masking and / or gaussian_denoising / median_denoising (3x3) on float32 and 16-bit-container
+ *   frames; a device build or the lock-step emulation.
+ * r2l_static_io_supported returns NULL where the call is served and otherwise the reason (a static string): Menon2007,
+ * fft_denoising, the 5x5 median (plane passes), other widths (tile kernels, plane passes), float64 frames on a luma chain, the
+ * serial emulation build.  It is the predicate r2l_static_fwd_io itself uses: an unserved 16-bit call returns -3 with that
+ * reason in r2l_last_error() and writes nothing; the caller then runs the float32 call and narrows.  An out_io outside R2L_IO_*
+ * returns -1, as does a 16-bit `out` that is not 8-byte aligned (a lane moves 4 pixels of a channel as one 8-byte store).
+ * The served chains need no workspace.                                                                                        */
+const char *r2l_static_io_supported(int frames, int H, int W, int debayer, int sharpening, int denoising,
+                                    const double *options_host);
+int r2l_static_fwd_io(const void *raw, int frames, float denom, void *out, int out_io, int B, int H, int W,
+                      const double *camera_host, int debayer, int sharpening, int denoising, double gamma,
+                      const double *options_host, const float *mean_std_host, void *workspace, size_t workspace_bytes,
+                      void *stream);
+
 /* ---- staged execution (track_stages=True, pipeline_torch.py:197-221): one entry point per materialised
  * stage, each with its VJP, so that autograd can hold every stage tensor (retain_grad) and d/d raw exists.
  * Tensors are (B,3,H,W) float32.  Weight gradients are float32 arrays; workspace from

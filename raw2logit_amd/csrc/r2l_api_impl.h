@@ -408,6 +408,23 @@ R2L_STREAM_KERNEL(r2l_launch_static_luma_bilinear_u16, 0, R2L_RAW_U16, true, R2L
 R2L_STREAM_KERNEL(r2l_launch_static_luma_malvar_u16, 1, R2L_RAW_U16, true, R2L_STREAM_OCC_MALVAR)
 R2L_STREAM_KERNEL(r2l_launch_static_luma_bilinear_f64, 0, R2L_RAW_F64, true, 3)
 R2L_STREAM_KERNEL(r2l_launch_static_luma_malvar_f64, 1, R2L_RAW_F64, true, 2)
+#ifndef R2L_SERIAL
+// ... the whole short chain writing bfloat16 / float16 (r2l_static_fwd_io: R2L_IO_*), at their float32 siblings' occupancy
+#define R2L_STREAM_KERNEL_IO(name, DEB, RAWK, IO, OCC)                                                   \
+  R2L_BLOCKFN void name##_block(const R2LStaticStreamArgs& sa, int bid, int nblk, float* lds) {          \
+    r2l_static_stream_block<DEB, RAWK, false, IO>(sa, bid, nblk, lds);                                   \
+  }                                                                                                      \
+  R2L_KERNEL_NT(name, R2LStaticStreamArgs, name##_block, R2L_STREAM_NT, OCC)
+#define R2L_STREAM_KERNELS_IO(sfx, IO)                                                                              \
+  R2L_STREAM_KERNEL_IO(r2l_launch_static_stream_bilinear##sfx, 0, R2L_RAW_F32, IO, R2L_STREAM_OCC_BILINEAR)         \
+  R2L_STREAM_KERNEL_IO(r2l_launch_static_stream_malvar##sfx, 1, R2L_RAW_F32, IO, R2L_STREAM_OCC_MALVAR)             \
+  R2L_STREAM_KERNEL_IO(r2l_launch_static_stream_bilinear_u16##sfx, 0, R2L_RAW_U16, IO, R2L_STREAM_OCC_BILINEAR)     \
+  R2L_STREAM_KERNEL_IO(r2l_launch_static_stream_malvar_u16##sfx, 1, R2L_RAW_U16, IO, R2L_STREAM_OCC_MALVAR)         \
+  R2L_STREAM_KERNEL_IO(r2l_launch_static_stream_bilinear_f64##sfx, 0, R2L_RAW_F64, IO, 3)                           \
+  R2L_STREAM_KERNEL_IO(r2l_launch_static_stream_malvar_f64##sfx, 1, R2L_RAW_F64, IO, 2)
+R2L_STREAM_KERNELS_IO(_bf16, R2L_IO_BF16)
+R2L_STREAM_KERNELS_IO(_f16, R2L_IO_F16)
+#endif
 R2L_KERNEL(r2l_launch_plane_filter, R2LPlaneArgs, r2l_plane_filter_block, 4)
 R2L_KERNEL(r2l_launch_spec_mask, R2LSpecMaskArgs, r2l_spec_mask_block, 4)
 R2L_KERNEL(r2l_launch_static_finish, R2LStaticFinishArgs, r2l_static_finish_block, 4)
@@ -425,19 +442,19 @@ R2L_KERNEL(r2l_launch_static_menon, R2LMenonArgs, r2l_static_menon_block, 4)
 // (the workgroup size and the LDS size follow the frame width at launch time: 64 threads and 16.1 KB per strip)
 #define R2L_MAX_DEVICES 64
 #ifdef R2L_LOCKSTEP
-#define R2L_CHAIN_KERNEL(name, RAWK, DEB, SH, DN)                                                             \
+#define R2L_CHAIN_KERNEL_IO(name, RAWK, DEB, SH, DN, IO)                                                      \
   static int name(const R2LStaticChainArgs& a, int grid, void* stream) {                                      \
     (void)stream;                                                                                             \
     r2l_ls_note(#name);                                                                                       \
     r2l_ls::launch(#name, grid, a.nw * 64, 2 * (size_t)R2L_CHAIN_LDS_DOUBLES(a.nw, SH), &a,                   \
-                   [&](int b_, float* lds_) { r2l_static_chain_block<RAWK, DEB, SH, DN>(a, b_, grid, lds_); }); \
+                   [&](int b_, float* lds_) { r2l_static_chain_block<RAWK, DEB, SH, DN, IO>(a, b_, grid, lds_); }); \
     return 0;                                                                                                 \
   }
 #else
-#define R2L_CHAIN_KERNEL(name, RAWK, DEB, SH, DN)                                                             \
+#define R2L_CHAIN_KERNEL_IO(name, RAWK, DEB, SH, DN, IO)                                                      \
   __global__ __launch_bounds__((SH) ? 256 : 512, (SH) ? R2L_CHAIN_OCC_SH : R2L_CHAIN_OCC) void name##_kernel(const R2LStaticChainArgs a) { \
     extern __shared__ __attribute__((aligned(16))) float r2l_chain_lds[];                                     \
-    r2l_static_chain_block<RAWK, DEB, SH, DN>(a, (int)blockIdx.x, (int)gridDim.x, r2l_chain_lds);             \
+    r2l_static_chain_block<RAWK, DEB, SH, DN, IO>(a, (int)blockIdx.x, (int)gridDim.x, r2l_chain_lds);         \
   }                                                                                                           \
   static int name(const R2LStaticChainArgs& a, int grid, void* stream) {                                      \
     const size_t lds_bytes = sizeof(double) * R2L_CHAIN_LDS_DOUBLES(a.nw, SH);                                \
@@ -459,19 +476,24 @@ R2L_KERNEL(r2l_launch_static_menon, R2LMenonArgs, r2l_static_menon_block, 4)
     R2L_LAUNCH(name, a.nw * 64, lds_bytes)                                                                    \
   }
 #endif
-// [16-bit / float64 frames] x [Malvar2004] x [unsharp_masking] x [median_denoising]
-#define R2L_CHAIN_KERNELS(sfx, RAWK)                                               \
-  R2L_CHAIN_KERNEL(r2l_launch_static_chain##sfx, RAWK, 0, 0, 0)                    \
-  R2L_CHAIN_KERNEL(r2l_launch_static_chain_median##sfx, RAWK, 0, 0, 1)             \
-  R2L_CHAIN_KERNEL(r2l_launch_static_chain_unsharp##sfx, RAWK, 0, 1, 0)            \
-  R2L_CHAIN_KERNEL(r2l_launch_static_chain_unsharp_median##sfx, RAWK, 0, 1, 1)     \
-  R2L_CHAIN_KERNEL(r2l_launch_static_chain_malvar##sfx, RAWK, 1, 0, 0)             \
-  R2L_CHAIN_KERNEL(r2l_launch_static_chain_malvar_median##sfx, RAWK, 1, 0, 1)      \
-  R2L_CHAIN_KERNEL(r2l_launch_static_chain_malvar_unsharp##sfx, RAWK, 1, 1, 0)     \
-  R2L_CHAIN_KERNEL(r2l_launch_static_chain_malvar_unsharp_median##sfx, RAWK, 1, 1, 1)
+// [16-bit / float64 frames] x [Malvar2004] x [unsharp_masking] x [median_denoising] x [16-bit output: float32 / 16-bit frames]
+#define R2L_CHAIN_KERNELS_IO(sfx, RAWK, IO)                                                   \
+  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain##sfx, RAWK, 0, 0, 0, IO)                        \
+  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_median##sfx, RAWK, 0, 0, 1, IO)                 \
+  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_unsharp##sfx, RAWK, 0, 1, 0, IO)                \
+  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_unsharp_median##sfx, RAWK, 0, 1, 1, IO)         \
+  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_malvar##sfx, RAWK, 1, 0, 0, IO)                 \
+  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_malvar_median##sfx, RAWK, 1, 0, 1, IO)          \
+  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_malvar_unsharp##sfx, RAWK, 1, 1, 0, IO)         \
+  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_malvar_unsharp_median##sfx, RAWK, 1, 1, 1, IO)
+#define R2L_CHAIN_KERNELS(sfx, RAWK) R2L_CHAIN_KERNELS_IO(sfx, RAWK, R2L_IO_F32)
 R2L_CHAIN_KERNELS(, R2L_RAW_F32)
 R2L_CHAIN_KERNELS(_u16, R2L_RAW_U16)
 R2L_CHAIN_KERNELS(_f64, R2L_RAW_F64)
+R2L_CHAIN_KERNELS_IO(_bf16, R2L_RAW_F32, R2L_IO_BF16)
+R2L_CHAIN_KERNELS_IO(_u16_bf16, R2L_RAW_U16, R2L_IO_BF16)
+R2L_CHAIN_KERNELS_IO(_f16, R2L_RAW_F32, R2L_IO_F16)
+R2L_CHAIN_KERNELS_IO(_u16_f16, R2L_RAW_U16, R2L_IO_F16)
 #endif
 R2L_KERNEL(r2l_launch_static_short, R2LStaticArgs, r2l_static_short_block<GStatic>,
            R2L_STATIC_SHORT_LDS_FLOATS)
@@ -1910,7 +1932,8 @@ static int r2l_static_menon_impl(const R2LStaticArgs& a, int B, int H, int W, in
 static int r2l_static_fwd_impl(const R2LRaw& raw, float* out, int B, int H, int W, const double* camera_host,
                                int debayer, int sharpening, int denoising, double gamma, void* workspace,
                                size_t workspace_bytes, void* stream, const float* mean_std_host = nullptr,
-                               const R2LStaticOpts& opt = R2LStaticOpts()) {
+                               const R2LStaticOpts& opt = R2LStaticOpts(), int io = R2L_IO_F32) {
+  // (io != R2L_IO_F32: `out` points to 2-byte elements and r2l_static_io_why has said that a 16-bit kernel serves the call)
   if (int e = r2l_check_dims(B, H, W)) return e;
   if (int e = r2l_check_raw(raw, W, "r2l_static_fwd")) return e;
   if (mean_std_host)
@@ -1928,8 +1951,11 @@ static int r2l_static_fwd_impl(const R2LRaw& raw, float* out, int B, int H, int 
   if (const char* why = r2l_static_opts_problem(opt, sharpening, denoising)) return r2l_fail(-4, std::string("r2l_static_fwd: ") + why);
   R2LStaticArgs a;
   r2l_static_setup(a, raw, out, B, H, W, camera_host, debayer, sharpening, denoising, gamma, mean_std_host, opt);
-  if (debayer == R2L_DEBAYER_MENON2007)
+  const char* const no_io = "r2l_static_fwd_io: no 16-bit form of the kernels this call takes (r2l_static_io_supported)";
+  if (debayer == R2L_DEBAYER_MENON2007) {
+    if (io != R2L_IO_F32) return r2l_fail(-3, no_io);
     return r2l_static_menon_impl(a, B, H, W, sharpening, denoising, opt, workspace, workspace_bytes, stream);
+  }
   const int ntiles = B * ((H + GStatic::TH - 1) / GStatic::TH) * ((W + GStatic::TW - 1) / GStatic::TW);
 #ifndef R2L_SERIAL
   if (r2l_static_is_chain(W, debayer, sharpening, denoising, opt.median_kernel_size)) {
@@ -1958,9 +1984,18 @@ static int r2l_static_fwd_impl(const R2LRaw& raw, float* out, int B, int H, int 
    {{r2l_launch_static_chain_malvar##sfx, r2l_launch_static_chain_malvar_median##sfx},                              \
     {r2l_launch_static_chain_malvar_unsharp##sfx, r2l_launch_static_chain_malvar_unsharp_median##sfx}}}
     static const launch_t table[3][2][2][2] = {R2L_CHAIN_ROW(), R2L_CHAIN_ROW(_u16), R2L_CHAIN_ROW(_f64)};
+    static const launch_t table_io[2][2][2][2][2] = {{R2L_CHAIN_ROW(_bf16), R2L_CHAIN_ROW(_u16_bf16)},
+                                                     {R2L_CHAIN_ROW(_f16), R2L_CHAIN_ROW(_u16_f16)}};
 #undef R2L_CHAIN_ROW
+    if (io != R2L_IO_F32) {
+      if (kind == 2) return r2l_fail(-3, no_io);
+      return table_io[io == R2L_IO_F16][kind][deb][sh][dn](ca, (int)grid, stream);
+    }
     return table[kind][deb][sh][dn](ca, (int)grid, stream);
   }
+  if (io != R2L_IO_F32 && (a.full || (W & 3) || (!raw.f64 && r2l_env_int("R2L_STATIC_TILED", 0)))) return r2l_fail(-3, no_io);
+#else
+  if (io != R2L_IO_F32) return r2l_fail(-3, no_io);
 #endif
   if (!r2l_static_is_fused(W, debayer, sharpening, denoising, raw.f64 != nullptr, opt.median_kernel_size)) {
     // luma-plane passes: raw -> Y | sharpen | denoise | raw + Y'' -> RGB
@@ -2061,6 +2096,18 @@ static int r2l_static_fwd_impl(const R2LRaw& raw, float* out, int B, int H, int 
     sa.nitems = (int)nitems;
     const int wpb = R2L_STREAM_NT / 64;
     const int grid = (int)((nitems + wpb - 1) / wpb);
+#ifndef R2L_SERIAL
+    if (io != R2L_IO_F32) {
+      typedef int (*launch_t)(const R2LStaticStreamArgs&, int, void*);
+#define R2L_STREAM_ROW(sfx)                                                                          \
+  {{r2l_launch_static_stream_bilinear##sfx, r2l_launch_static_stream_malvar##sfx},                   \
+   {r2l_launch_static_stream_bilinear_u16##sfx, r2l_launch_static_stream_malvar_u16##sfx},           \
+   {r2l_launch_static_stream_bilinear_f64##sfx, r2l_launch_static_stream_malvar_f64##sfx}}
+      static const launch_t table_io[2][3][2] = {R2L_STREAM_ROW(_bf16), R2L_STREAM_ROW(_f16)};
+#undef R2L_STREAM_ROW
+      return table_io[io == R2L_IO_F16][raw.u16 ? 1 : (raw.f64 ? 2 : 0)][debayer == R2L_DEBAYER_MALVAR2004](sa, grid, stream);
+    }
+#endif
     if (raw.u16)
       return debayer == R2L_DEBAYER_MALVAR2004 ? r2l_launch_static_stream_malvar_u16(sa, grid, stream)
                                                : r2l_launch_static_stream_bilinear_u16(sa, grid, stream);
@@ -2188,7 +2235,7 @@ int r2l_static_fwd_u16(const unsigned short* raw, float denom, float* out, int B
 static int r2l_static_fwd_any(const void* raw, int frames, float denom, float* out, int B, int H, int W,
                               const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
                               const float* mean_std_host, const R2LStaticOpts& opt, void* workspace, size_t workspace_bytes,
-                              void* stream);
+                              void* stream, int io = R2L_IO_F32);
 int r2l_static_fwd_norm(const void* raw, int frames, float denom, float* out, int B, int H, int W,
                         const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
                         const float* mean_std_host, void* workspace, size_t workspace_bytes, void* stream) {
@@ -2214,7 +2261,7 @@ int r2l_static_fwd_opts(const void* raw, int frames, float denom, float* out, in
 static int r2l_static_fwd_any(const void* raw, int frames, float denom, float* out, int B, int H, int W,
                               const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
                               const float* mean_std_host, const R2LStaticOpts& opt, void* workspace, size_t workspace_bytes,
-                              void* stream) {
+                              void* stream, int io) {
   R2LRaw rw;
   if (frames == R2L_FRAMES_F32)
     rw = r2l_raw_f32((const float*)raw);
@@ -2225,7 +2272,68 @@ static int r2l_static_fwd_any(const void* raw, int frames, float denom, float* o
   else
     return r2l_fail(-1, "r2l_static_fwd_norm: frames must be R2L_FRAMES_F32, _U16 or _F64");
   return r2l_static_fwd_impl(rw, out, B, H, W, camera_host, debayer, sharpening, denoising, gamma, workspace,
-                             workspace_bytes, stream, mean_std_host, opt);
+                             workspace_bytes, stream, mean_std_host, opt, io);
+}
+
+// ---- 16-bit output of the static chains (include/r2l_isp.h: r2l_static_fwd_io) -------------------------------------------------
+// why a 16-bit call is not served, or null: the ONE predicate of r2l_static_io_supported and r2l_static_fwd_io.  Served: what
+// runs as one launch of a row-streaming kernel (r2l_static_stream.h, r2l_static_chain.h) on frames up to 2048 columns
+static const char* r2l_static_io_why(int frames, int H, int W, int debayer, int sharpening, int denoising, int median_size) {
+  if (frames != R2L_FRAMES_F32 && frames != R2L_FRAMES_U16 && frames != R2L_FRAMES_F64) return "frames must be one of R2L_FRAMES_*";
+  if (H < 4 || W < 4 || (H & 1) || (W & 1)) return "H and W must be even and >= 4";
+#ifdef R2L_SERIAL
+  (void)debayer; (void)sharpening; (void)denoising; (void)median_size;
+  return "the serial emulation has no 16-bit form of the static kernels";
+#else
+  if (debayer == R2L_DEBAYER_MENON2007) return "menon2007 runs as plane passes, which store float32";
+  if (debayer != R2L_DEBAYER_BILINEAR && debayer != R2L_DEBAYER_MALVAR2004) return "unknown debayer";
+  if (sharpening != R2L_SHARPEN_NONE && sharpening != R2L_SHARPEN_FILTER && sharpening != R2L_SHARPEN_UNSHARP) return "unknown sharpening";
+  if (denoising != R2L_DENOISE_NONE && denoising != R2L_DENOISE_GAUSSIAN && denoising != R2L_DENOISE_MEDIAN && denoising != R2L_DENOISE_FFT)
+    return "unknown denoising";
+  if (denoising == R2L_DENOISE_FFT) return "fft_denoising runs as plane passes, which store float32";
+  if (denoising == R2L_DENOISE_MEDIAN && median_size != 3) return "the 5x5 median runs as a plane pass, which stores float32";
+  if (W & 3) return "needs W % 4 == 0 (the row-streaming kernels)";
+  if (W > 2048) return "needs W <= 2048";
+  if (sharpening == R2L_SHARPEN_NONE && denoising == R2L_DENOISE_NONE) {
+    if (frames != R2L_FRAMES_F64 && r2l_env_int("R2L_STATIC_TILED", 0)) return "needs the row-streaming kernels (R2L_STATIC_TILED is set)";
+    return nullptr;
+  }
+  if (!r2l_static_is_chain(W, debayer, sharpening, denoising, median_size))
+    return sharpening == R2L_SHARPEN_UNSHARP && W > 1024 ? "behind unsharp_masking the luma-chain kernel needs W <= 1024"
+                                                         : "needs the row-streaming kernels (R2L_STATIC_TILED is set)";
+  if (frames == R2L_FRAMES_F64) return "float64 frames on a luma chain store float32";
+  return nullptr;
+#endif
+}
+static int r2l_static_median_size(const double* options_host) {
+  if (!options_host) return 3;
+  const double m = options_host[R2L_SOPT_MEDIAN_SIZE];
+  return (m == (double)(int)m) ? (int)m : -1;
+}
+const char* r2l_static_io_supported(int frames, int H, int W, int debayer, int sharpening, int denoising, const double* options_host) {
+  return r2l_static_io_why(frames, H, W, debayer, sharpening, denoising, r2l_static_median_size(options_host));
+}
+int r2l_static_fwd_io(const void* raw, int frames, float denom, void* out, int out_io, int B, int H, int W,
+                      const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
+                      const double* options_host, const float* mean_std_host, void* workspace, size_t workspace_bytes,
+                      void* stream) {
+  if (out_io == R2L_IO_F32)
+    return r2l_static_fwd_opts(raw, frames, denom, (float*)out, B, H, W, camera_host, debayer, sharpening, denoising, gamma,
+                               options_host, mean_std_host, workspace, workspace_bytes, stream);
+  if (out_io != R2L_IO_BF16 && out_io != R2L_IO_F16) return r2l_fail(-1, "r2l_static_fwd_io: out_io must be one of R2L_IO_*");
+  if (const char* why = r2l_static_io_why(frames, H, W, debayer, sharpening, denoising, r2l_static_median_size(options_host)))
+    return r2l_fail(-3, std::string("r2l_static_fwd_io: a 16-bit output is not served here: ") + why);
+  if ((uintptr_t)out % 8) return r2l_fail(-1, "r2l_static_fwd_io: the 16-bit output must be 8-byte aligned");
+  R2LStaticOpts o;
+  if (options_host) {
+    o.sharp_radius = options_host[R2L_SOPT_SHARP_RADIUS];
+    o.sharp_amount = options_host[R2L_SOPT_SHARP_AMOUNT];
+    o.gaussian_sigma = options_host[R2L_SOPT_GAUSSIAN_SIGMA];
+    o.fft_fraction = options_host[R2L_SOPT_FFT_FRACTION];
+    o.median_kernel_size = r2l_static_median_size(options_host);
+  }
+  return r2l_static_fwd_any(raw, frames, denom, (float*)out, B, H, W, camera_host, debayer, sharpening, denoising, gamma,
+                            mean_std_host, o, workspace, workspace_bytes, stream, out_io);
 }
 
 // ---- staged (track_stages=True) entry points -------------------------------------------------------

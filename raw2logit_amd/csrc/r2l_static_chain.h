@@ -102,7 +102,7 @@ R2L_HD R2LStaticArgsK r2l_chain_consts() {
 #endif
 }
 
-template <int DEB, int SH, int DN, int K0>
+template <int DEB, int SH, int DN, int K0, int IO = R2L_IO_F32>
 R2L_HD void r2l_chain_step(const R2LStaticArgs& a_, R2LChainState<DEB, SH, DN>& st, int q_, int y0, int y1, bool le,
                            bool re, int NW, int wave, int lane, double* ex, r2l_d2* fifo, float* outb, size_t plane,
                            int x0, bool store_ok) {
@@ -294,6 +294,9 @@ R2L_HD void r2l_chain_step(const R2LStaticArgs& a_, R2LChainState<DEB, SH, DN>& 
         }
       }
       r2l_static_normalize<4>(a, x);
+      if constexpr (IO != R2L_IO_F32) {  // 16-bit output (r2l_static_fwd_io): one 8-byte store per channel
+        r2l_stream_store_row<IO>(outb, plane, (size_t)y * a_.W + x0, x, store_ok);
+      } else
       if (store_ok) {
         const size_t off = (size_t)y * a_.W + x0;
         R2L_PRAGMA_UNROLL
@@ -366,6 +369,9 @@ R2L_HD void r2l_chain_step(const R2LStaticArgs& a_, R2LChainState<DEB, SH, DN>& 
       }
     }
     r2l_static_normalize<4>(a, x);
+    if constexpr (IO != R2L_IO_F32) {
+      r2l_stream_store_row<IO>(outb, plane, (size_t)y * a_.W + x0, x, store_ok);
+    } else
     if (store_ok) {
       const size_t off = (size_t)y * a_.W + x0;
       R2L_PRAGMA_UNROLL
@@ -381,7 +387,7 @@ R2L_HD void r2l_chain_step(const R2LStaticArgs& a_, R2LChainState<DEB, SH, DN>& 
   }
 }
 
-template <int RAWK, int DEB, int SH, int DN>
+template <int RAWK, int DEB, int SH, int DN, int IO = R2L_IO_F32>
 R2L_BLOCKFN void r2l_static_chain_block(const R2LStaticChainArgs& ca, int bid, int nblk, float* lds_f) {
   (void)nblk;
   const R2LStaticArgs& a = ca.s;
@@ -398,7 +404,7 @@ R2L_BLOCKFN void r2l_static_chain_block(const R2LStaticChainArgs& ca, int bid, i
   const bool le = x0 == 0, re = x0 + 4 >= a.W;
   const size_t plane = (size_t)a.H * a.W;
   const size_t img = (size_t)b * plane;
-  float* outb = a.out + (size_t)b * 3 * plane;
+  float* outb = r2l_io_at<IO>(a.out, (size_t)b * 3 * plane);
   R2LChainState<DEB, SH, DN> st;
   R2L_PRAGMA_UNROLL
   for (int i = 0; i < (DN == 0 ? 6 : 3); ++i)
@@ -456,7 +462,7 @@ R2L_BLOCKFN void r2l_static_chain_block(const R2LStaticChainArgs& ca, int bid, i
     const int q = qb + K;                                                                                         \
     r2l_stream_convert_row<RAWK, LANES>(a, pf[K % PF], le, re, st.rw[(K + LA) % NR]);                             \
     if (BF || q + PF < q1) R2L_CHAIN_FETCH(q + LA + PF, pf[K % PF])                                               \
-    r2l_chain_step<DEB, SH, DN, K>(a, st, q, y0, y1, le, re, NW, wave, lane, ex, fifo, outb, plane, x0, store_ok); \
+    r2l_chain_step<DEB, SH, DN, K, IO>(a, st, q, y0, y1, le, re, NW, wave, lane, ex, fifo, outb, plane, x0, store_ok); \
   }
     R2L_CHAIN_STEP(0)
     R2L_CHAIN_STEP(1)

@@ -257,7 +257,22 @@ R2L_HD double r2l_widen(float x) {
 #endif
 }
 
-// WB * CCM, clip, gamma and the three 16-byte stores of one output row (4 pixels of this lane)
+// WB * CCM, clip, gamma and the three 16-byte stores of one output row (4 pixels of this lane).
+// IO = R2L_IO_BF16 / R2L_IO_F16 (r2l_static_fwd_io): `outb` points to 2-byte elements, and the float32 values -- rounded and
+// normalised exactly as below -- are narrowed once more, to nearest even, and leave as one 8-byte store per channel
+template <int IO>
+R2L_HD void r2l_stream_store_row(float* outb, size_t plane, size_t off, const float x[3][4], bool ok = true) {
+  R2L_PRAGMA_UNROLL
+  for (int k = 0; k < 3; ++k) {
+    r2l_f4 st;
+    st.x = x[k][0];
+    st.y = x[k][1];
+    st.z = x[k][2];
+    st.w = x[k][3];
+    if (ok) r2l_store_h4_nt((unsigned short*)outb + (size_t)k * plane + off, r2l_io_narrow4<IO>(st));
+  }
+}
+template <int IO = R2L_IO_F32>
 R2L_HD void r2l_stream_finish_row(const R2LStaticArgs& a, const double d[4][3], float* outb, size_t plane,
                                   size_t off, bool ok = true) {
   float x[3][4];
@@ -269,6 +284,10 @@ R2L_HD void r2l_stream_finish_row(const R2LStaticArgs& a, const double d[4][3], 
     x[k][c] = r2l_clip_gamma(rgb, a.inv_gamma);
   }
   r2l_static_normalize<4>(a, x);
+  if constexpr (IO != R2L_IO_F32) {
+    r2l_stream_store_row<IO>(outb, plane, off, x, ok);
+    return;
+  }
   R2L_PRAGMA_UNROLL
   for (int k = 0; k < 3; ++k) {
     r2l_f4 st;
@@ -503,8 +522,9 @@ R2L_HD void r2l_stream_malvar_rowT(const double* w0, const double* w1, const dou
 #define R2L_STREAM_PF_MALVAR 2
 #endif
 // one lane's work item: image b, column strip seg (256 columns), row band
-template <int DEB, int RAWK, bool LUMA>
+template <int DEB, int RAWK, bool LUMA, int IO = R2L_IO_F32>
 R2L_HD void r2l_static_stream_item(const R2LStaticStreamArgs& sa, int item, int lane) {
+  static_assert(IO == R2L_IO_F32 || !LUMA, "the luma-plane passes store float32");
   const R2LStaticArgs& a = sa.s;
   constexpr int HALO = DEB ? 2 : 1, NR = 2 * HALO + 1;
   constexpr bool LANES = (DEB == 0) && R2L_HAVE_LANE_SHIFTS && RAWK != R2L_RAW_F64;
@@ -520,7 +540,7 @@ R2L_HD void r2l_static_stream_item(const R2LStaticStreamArgs& sa, int item, int 
   const bool le = x0 == 0, re = x0 + 4 >= a.W;
   const size_t plane = (size_t)a.H * a.W;
   const size_t img = (size_t)b * plane;  // element offset of image b
-  float* outb = a.out + (size_t)b * 3 * plane;
+  float* outb = r2l_io_at<IO>(a.out, (size_t)b * 3 * plane);
   // Malvar2004 on float32 / 16-bit frames: a float32 window (r2l_stream_malvar_row_shared widens it)
   constexpr bool WF32 = (DEB == 1) && RAWK != R2L_RAW_F64;
   typename R2LWinType<WF32>::type win[NR][8];
@@ -580,7 +600,7 @@ R2L_HD void r2l_static_stream_item(const R2LStaticStreamArgs& sa, int item, int 
         else if (LUMA)
           r2l_stream_luma_in_row(a, d, sa.luma_in + img, outb, plane, (size_t)y * a.W + x0);
         else
-          r2l_stream_finish_row(a, d, outb, plane, (size_t)y * a.W + x0);
+          r2l_stream_finish_row<IO>(a, d, outb, plane, (size_t)y * a.W + x0);
       }
     }
   }
@@ -599,7 +619,7 @@ R2L_HD void r2l_static_stream_item(const R2LStaticStreamArgs& sa, int item, int 
 #define R2L_STREAM_BF_PF_MALVAR 5
 #endif
 // (strip edges through scalar loads + lane shifts: measured slower, profiles/r04_ab_static_se.txt)
-template <int DEB, int RAWK>
+template <int DEB, int RAWK, int IO = R2L_IO_F32>
 R2L_HD void r2l_static_stream_item_bf(const R2LStaticStreamArgs& sa, int item, int lane) {
   const R2LStaticArgs& a = sa.s;
   constexpr int HALO = DEB ? 2 : 1, NR = 2 * HALO + 1;
@@ -617,7 +637,7 @@ R2L_HD void r2l_static_stream_item_bf(const R2LStaticStreamArgs& sa, int item, i
   const bool le = x0 == 0, re = x0 + 4 >= a.W;
   const size_t plane = (size_t)a.H * a.W;
   const size_t img = (size_t)b * plane;
-  float* outb = a.out + (size_t)b * 3 * plane;
+  float* outb = r2l_io_at<IO>(a.out, (size_t)b * 3 * plane);
   // (float32 window for bilinear too: 24 registers instead of 48, widened exactly where used -- what makes room for the
   // deeper prefetch ring at three wavefronts per SIMD)
   typedef float WT;
@@ -678,7 +698,7 @@ R2L_HD void r2l_static_stream_item_bf(const R2LStaticStreamArgs& sa, int item, i
                                           win[(k + 4) % NR], d);
       }
       const int yc = y < y1 ? y : y1 - 1;  // (rows past the band's end: computed, not stored)
-      r2l_stream_finish_row(a, d, outb, plane, (size_t)yc * a.W + x0, in_w && y < y1);
+      r2l_stream_finish_row<IO>(a, d, outb, plane, (size_t)yc * a.W + x0, in_w && y < y1);
     }
   }
 }
@@ -687,7 +707,7 @@ R2L_HD void r2l_static_stream_item_bf(const R2LStaticStreamArgs& sa, int item, i
 #undef R2L_BF_CONVERT
 
 #define R2L_STREAM_NT 256  // 4 independent wavefronts per workgroup
-template <int DEB, int RAWK, bool LUMA>
+template <int DEB, int RAWK, bool LUMA, int IO = R2L_IO_F32>
 R2L_BLOCKFN void r2l_static_stream_block(const R2LStaticStreamArgs& sa, int bid, int nblk, float* lds) {
   (void)lds;
   (void)nblk;
@@ -698,10 +718,10 @@ R2L_BLOCKFN void r2l_static_stream_block(const R2LStaticStreamArgs& sa, int bid,
   if constexpr (!LUMA && RAWK != R2L_RAW_F64 && DEB == 1) {
     // (the wavefront index as a SCALAR: the work item and its rows must not look lane-dependent)
     const int witem = bid * (R2L_STREAM_NT / 64) + __builtin_amdgcn_readfirstlane(tid >> 6);
-    if (witem < sa.nitems) r2l_static_stream_item_bf<DEB, RAWK>(sa, witem, tid & 63);
+    if (witem < sa.nitems) r2l_static_stream_item_bf<DEB, RAWK, IO>(sa, witem, tid & 63);
     return;
   }
 #endif
-  if (item < sa.nitems) r2l_static_stream_item<DEB, RAWK, LUMA>(sa, item, tid & 63);
+  if (item < sa.nitems) r2l_static_stream_item<DEB, RAWK, LUMA, IO>(sa, item, tid & 63);
   R2L_PHASE_END
 }

@@ -594,8 +594,14 @@ STATIC_OPTION_DEFAULTS = dict(sharp_radius=1.0, sharp_amount=1.0, gaussian_sigma
 
 def static_pipeline(raw, camera_parameters, debayer='bilinear', sharpening='sharpening_filter',
                     denoising='gaussian_denoising', gamma=2.2, bits=16, mean_std=None, sharp_radius=1.0, sharp_amount=1.0,
-                    median_kernel_size=3, gaussian_sigma=0.5, fft_fraction=0.3):
+                    median_kernel_size=3, gaussian_sigma=0.5, fft_fraction=0.3, out_dtype=None):
     """(B,H,W) raw on the GPU -> (B,3,H,W) float32, numpy semantics of the reference.
+
+    out_dtype = torch.bfloat16 / torch.float16 (opt-in; None and torch.float32: today's call): the result is
+    float32_result.to(out_dtype) bit for bit.  Where one row-streaming kernel runs the chain (r2l_static_io_supported:
+    bilinear / Malvar2004, W % 4 == 0, W <= 2048, no fft_denoising, no 5x5 median, float64 frames on the short chain only) that
+    kernel rounds its float32 values to the 16-bit type itself and stores 6 instead of 12 bytes per pixel (r2l_static_fwd_io);
+    everywhere else the float32 call runs and torch casts.
 
     sharp_radius, sharp_amount, median_kernel_size, gaussian_sigma, fft_fraction: processing()'s numeric arguments
     (pipeline_numpy.py:70-73, used at :117-122), launch arguments of the kernels (r2l_static_fwd_opts).  What the kernels'
@@ -638,12 +644,24 @@ def static_pipeline(raw, camera_parameters, debayer='bilinear', sharpening='shar
     cam = (ctypes.c_double * 16)(*[float(v) for v in list(bl) + list(wb) + list(ccm)])
     B, H, W = raw.shape
     lib, stream = _lib.library_for(raw)
-    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=raw.device)
+    if out_dtype not in IO_CODES:
+        raise _lib.R2LError(f'output_dtype must be None, torch.float32, torch.bfloat16 or torch.float16, got {out_dtype!r}')
     codes = (_DEBAYER[debayer], _SHARPEN.get(sharpening, 0), _DENOISE.get(denoising, 0))
     opts = dict(sharp_radius=sharp_radius, sharp_amount=sharp_amount, gaussian_sigma=gaussian_sigma,
                 fft_fraction=fft_fraction, median_kernel_size=median_kernel_size)
     custom = opts != STATIC_OPTION_DEFAULTS
     frames = 2 if f64 else (0 if denom is None else 1)
+    if IO_CODES[out_dtype] != IO_F32:
+        ov = (ctypes.c_double * 5)(float(sharp_radius), float(sharp_amount), float(gaussian_sigma), float(fft_fraction),
+                                   float(median_kernel_size)) if custom else None
+        if lib.r2l_static_io_supported(frames, H, W, *codes, ov) is None:        # (NULL: served; otherwise the reason)
+            out = torch.empty((B, 3, H, W), dtype=out_dtype, device=raw.device)
+            ms = (ctypes.c_float * 6)(*[float(v) for v in mean_std]) if mean_std is not None else None
+            lib.check(lib.r2l_static_fwd_io(ptr(raw), frames, float(denom or 1.0), ptr(out), IO_CODES[out_dtype], B, H, W, cam,
+                                            *codes, float(gamma), ov, ms, None, 0, stream), 'r2l_static_fwd_io')
+            return out
+        # no 16-bit form of the kernels this call takes: today's float32 call below, narrowed by torch -- the same values
+    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=raw.device)
     if custom:
         ov = (ctypes.c_double * 5)(float(sharp_radius), float(sharp_amount), float(gaussian_sigma), float(fft_fraction),
                                    float(median_kernel_size))         # R2L_SOPT_* order (include/r2l_isp.h)
@@ -666,7 +684,25 @@ def static_pipeline(raw, camera_parameters, debayer='bilinear', sharpening='shar
         lib.check(lib.r2l_static_fwd(ptr(raw), *tail), 'r2l_static_fwd')
     else:
         lib.check(lib.r2l_static_fwd_u16(ptr(raw), denom, *tail), 'r2l_static_fwd_u16')
-    return out
+    return out if IO_CODES[out_dtype] == IO_F32 else out.to(out_dtype)
+
+
+def static_io_why(raw, debayer='bilinear', sharpening='sharpening_filter', denoising='gaussian_denoising', **options):
+    """why the static kernels do not write a 16-bit output themselves for these frames and this chain (r2l_static_io_supported,
+    the predicate r2l_static_fwd_io uses), or None where they do.  options: static_pipeline's numeric arguments."""
+    unknown = set(options) - set(STATIC_OPTION_DEFAULTS)
+    if unknown:
+        raise TypeError(f'unknown static options {sorted(unknown)} (have: {sorted(STATIC_OPTION_DEFAULTS)})')
+    if raw.ndim != 3:
+        return 'needs dims (B, H, W)'
+    o = {**STATIC_OPTION_DEFAULTS, **options}
+    ov = (ctypes.c_double * 5)(float(o['sharp_radius']), float(o['sharp_amount']), float(o['gaussian_sigma']),
+                               float(o['fft_fraction']), float(o['median_kernel_size']))
+    frames = 2 if raw.dtype == torch.float64 else (1 if raw.dtype in U16_DTYPES else 0)
+    lib, _ = _lib.library_for(raw)
+    why = lib.r2l_static_io_supported(frames, raw.shape[1], raw.shape[2], _DEBAYER.get(debayer, -1), _SHARPEN.get(sharpening, 0),
+                                      _DENOISE.get(denoising, 0), ov)
+    return why.decode() if why is not None else None
 
 
 def normalize(rgb, mean_std):

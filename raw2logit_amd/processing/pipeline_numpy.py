@@ -74,9 +74,17 @@ class StaticProcessing(nn.Module):
 
     Equals RawProcessingPipeline applied to every frame followed by the optional T.Normalize(mean, std)
     of train.py:157-171 (fused into the pipeline's kernels: r2l_static_fwd_norm).  No trainable parameters, no gradient.  Frames may be float32 in [0,1] or the
-    sensor's 16-bit containers (uint16 / int16 tensors, divided by 2**raw_bits - 1 inside the kernel)."""
+    sensor's 16-bit containers (uint16 / int16 tensors, divided by 2**raw_bits - 1 inside the kernel).
+
+    ``output_dtype`` (opt-in, default None = float32) -- ``torch.bfloat16`` or ``torch.float16``: the module returns
+    ``float32_result.to(output_dtype)`` bit for bit (Normalize included), for a task model that runs under torch.autocast /
+    precision=16.  Where one row-streaming kernel runs the chain (functional.static_io_why: bilinear / Malvar2004, W % 4 == 0,
+    W <= 2048, no fft_denoising, no 5x5 median, float64 frames on the short chain only) it stores the 16-bit values itself -- 6
+    instead of 12 bytes per pixel, no cast pass; everywhere else the float32 kernels run and torch casts.  Anything but None or
+    those three dtypes raises R2LError."""
 
     raw_bits = 16
+    output_dtype = None
 
     def __init__(self, camera_parameters, debayer='bilinear', sharpening='sharpening_filter',
                  denoising='gaussian_denoising', gamma=2.2, mean=None, std=None, **options):
@@ -103,9 +111,14 @@ class StaticProcessing(nn.Module):
         assert raw.ndim == 3, f"needs dims (B, H, W), got {raw.shape}"
         self.stages = {}
         self.buffer = {}
+        odt = self.output_dtype
+        if odt not in F_.IO_CODES:
+            raise F_._lib.R2LError(f'output_dtype must be None, torch.float32, torch.bfloat16 or torch.float16, got {odt!r}')
+        # (unset: exactly the call of a module without the attribute)
+        io = dict(out_dtype=odt) if F_.IO_CODES[odt] != F_.IO_F32 else {}
         rgb = F_.static_pipeline(raw, self.camera_parameters, self.debayer, self.sharpening,
                                  self.denoising, self.gamma, bits=self.raw_bits, mean_std=self._mean_std_host(),
-                                 **getattr(self, 'options', {}))
+                                 **getattr(self, 'options', {}), **io)
         self.buffer['processed_rgb'] = rgb
         return rgb
 
