@@ -1671,56 +1671,6 @@ int r2l_raw2rgb_bwd(const float* grad_out, float* grad_raw, double* grad_black_l
   return 0;
 }
 
-// chains the single-launch kernels cover: the short chain (any demosaic) and bilinear + sharpening_filter +
-// gaussian_denoising; everything else runs as luma-plane passes and needs two float64 planes of workspace
-// chains the row-streaming luma-chain kernel covers (r2l_static_chain.h): bilinear + [sharpening_filter] +
-// [gaussian_denoising], frames up to 2048 columns, W % 4 == 0
-static bool r2l_static_is_chain(int W, int debayer, int sharpening, int denoising, int median_size = 3) {
-  if (debayer == R2L_DEBAYER_MENON2007) return false;
-  if (denoising == R2L_DENOISE_MEDIAN && median_size != 3) return false;  // the 5x5 median runs as a luma-plane pass
-#ifdef R2L_SERIAL
-  (void)W; (void)debayer; (void)sharpening; (void)denoising;
-  return false;  // (lane shifts and wave-level exchange: not expressible in the one-lane-at-a-time emulation)
-#else
-  if (r2l_env_int("R2L_STATIC_TILED", 0)) return false;
-  (void)debayer;  // every demosaic, sharpening and denoising the library knows -- but for the chain without a luma stage
-  // (behind unsharp_masking the chroma waits 7 rows for its luma: 28 KB of LDS per 256-column strip, 4 strips at most)
-  return (W & 3) == 0 && W <= (sharpening == R2L_SHARPEN_UNSHARP ? 1024 : 2048) && denoising != R2L_DENOISE_FFT &&
-         !(sharpening == R2L_SHARPEN_NONE && denoising == R2L_DENOISE_NONE);
-#endif
-}
-static bool r2l_static_is_fused(int W, int debayer, int sharpening, int denoising, bool f64_frames = false, int median_size = 3) {
-  if (debayer == R2L_DEBAYER_MENON2007) return false;  // always plane passes (r2l_static_menon.h)
-  if (denoising == R2L_DENOISE_FFT) return false;
-  if (denoising == R2L_DENOISE_MEDIAN && median_size != 3) return false;
-  if (sharpening == R2L_SHARPEN_NONE && denoising == R2L_DENOISE_NONE) return true;
-  if (r2l_static_is_chain(W, debayer, sharpening, denoising)) return true;
-  if (f64_frames) return false;  // the tile kernel of the default chain stages float32 frames in LDS
-  return debayer == R2L_DEBAYER_BILINEAR && sharpening == R2L_SHARPEN_FILTER && denoising == R2L_DENOISE_GAUSSIAN;
-}
-static void r2l_stream_shape(R2LStaticStreamArgs& sa, int B, int H, int W, int debayer) {
-  // One wavefront per (image, 256-column strip, row band), dealt in that order, so the ~3,000 wavefronts resident
-  // at any moment work on ADJACENT bands.  Short bands keep that active region of the frames and of the output
-  // compact in HBM (a few tens of MiB instead of a slice of every image of the batch), which is worth far more
-  // than the halo rows every band re-reads (they come from L2): same-buffer A/B on 256x1024x1024, bilinear,
-  // 128 rows per band 862 us, 32 rows 830, 16 rows 800, 8 rows 735-756, 5 rows 754, 4 rows 778, 2 rows 1012.
-  // Malvar (4 halo rows, 5-row window) is flat between 24 and 48 rows per band -- and, round 5, 6 % FASTER at 10 rows (two
-  // full groups of its 5-step unrolled loop): 883 -> 826 us on 256x1024x1024, same buffers (profiles/r05_static_ab.txt;
-  // 9 rows 835, 13 rows 848, 15 rows 836, 5 rows 867, 6 rows -- 4 wasted steps of 10 -- 1000): the same compactness, at
-  // 40 % more fetched rows.  Rounds 1-4 had only swept 24 .. 48.
-  // Round 2, other frame widths (profiles/r02_j_stream_bands.txt): 6-row bands are as good on 1024-wide frames
-  // (0.711 vs 0.709 of the HBM peak) and better on 512- and 256-wide ones (0.718 vs 0.692, 0.724 vs 0.700).
-  sa.nseg = (W + 255) / 256;
-  const int rows = (debayer == R2L_DEBAYER_MALVAR2004) ? 10 : 6;
-  long nband = (H + rows - 1) / rows;
-  nband = r2l_env_int("R2L_STREAM_BANDS", (int)nband);
-  if (nband > H / 2) nband = H / 2;
-  if (nband < 1) nband = 1;
-  sa.band_h = (int)((H + nband - 1) / nband);
-  sa.nband = (H + sa.band_h - 1) / sa.band_h;
-  (void)B;
-}
-
 // ---- fft_denoising: the two transforms.  Device build: rocFFT plans (real <-> Hermitian, float64, rows of length W),
 // cached per (W, rows); the work buffer comes out of the caller's workspace like everything else.
 struct R2LFftPlans {
@@ -1815,118 +1765,337 @@ static int r2l_fft_exec(rocfft_plan plan, void* in, void* outp, void* work, size
   return st == rocfft_status_success ? 0 : r2l_fail(-10, "rocfft_execute failed");
 }
 #endif
-// workspace of the fft_denoising chain behind the two luma planes: linear RGB planes, spectrum, rocFFT work buffer
-struct R2LFftLayout {
-  size_t rgb_off, spec_off, work_off, total, rows;
-  R2LFftPlans plans;
-};
-static int r2l_fft_layout(int B, int H, int W, R2LFftLayout& L) {
-  const size_t px = (size_t)B * H * W;
-  L.rows = (size_t)3 * B * H;
-  L.rgb_off = r2l_align_up(2 * sizeof(double) * px);
-  L.spec_off = L.rgb_off + r2l_align_up(3 * sizeof(double) * px);
-  L.work_off = L.spec_off + r2l_align_up(2 * sizeof(double) * L.rows * (size_t)(W / 2 + 1));
-#ifndef R2L_EMUL
-  if (int e = r2l_fft_plans(W, L.rows, L.plans)) return e;
-#endif
-  L.total = L.work_off + r2l_align_up(L.plans.work_bytes);
-  return 0;
+// ---- the static chains: one plan (r2l_static_plan), one launcher (r2l_static_launch) ------------------------------------------
+// processing()'s numeric arguments out of the C ABI's array (NULL: the reference's defaults).  A median size that is no integer
+// becomes `bad_median`: -1, which r2l_static_opts_problem refuses -- but for r2l_static_workspace_bytes_opts, which sizes it as 3
+static R2LStaticOpts r2l_static_opts(const double* options_host, int bad_median = -1) {
+  R2LStaticOpts o;
+  if (!options_host) return o;
+  o.sharp_radius = options_host[R2L_SOPT_SHARP_RADIUS];
+  o.sharp_amount = options_host[R2L_SOPT_SHARP_AMOUNT];
+  o.gaussian_sigma = options_host[R2L_SOPT_GAUSSIAN_SIGMA];
+  o.fft_fraction = options_host[R2L_SOPT_FFT_FRACTION];
+  const double m = options_host[R2L_SOPT_MEDIAN_SIZE];
+  o.median_kernel_size = (m == (double)(int)m) ? (int)m : bad_median;
+  return o;
 }
 
-// ---- Menon2007 chains (r2l_static_menon.h): the (B,3,H,W) float64 image + five (B,H,W) planes; behind them, for fft_denoising,
-// the spectrum and rocFFT's work buffer
-struct R2LMenonLayout {
-  size_t spec_off, work_off, total, rows;
-  R2LFftPlans plans;
+// the kernels that serve a call
+enum {
+  R2L_ROUTE_MENON,   // Menon2007: plane passes (r2l_static_menon.h) on a float64 image + five planes of workspace
+  R2L_ROUTE_CHAIN,   // one launch of the row-streaming luma-chain kernel (r2l_static_chain.h)
+  R2L_ROUTE_PLANES,  // luma-plane passes: raw -> Y | sharpen | denoise | raw + Y'' -> RGB, on two float64 planes of workspace
+  R2L_ROUTE_FULL,    // the tile kernel of the default chain (bilinear + sharpening_filter + gaussian_denoising)
+  R2L_ROUTE_STREAM,  // the short chain, row-streaming (r2l_static_stream.h)
+  R2L_ROUTE_SHORT    // the short chain's tile kernel
 };
-static int r2l_menon_layout(int B, int H, int W, bool fft, R2LMenonLayout& L) {
-  const size_t px = (size_t)B * H * W;
-  L.rows = (size_t)3 * B * H;
-  L.spec_off = r2l_align_up(8 * sizeof(double) * px);
-  L.work_off = L.total = L.spec_off;
-  if (fft) {
-    L.work_off = L.spec_off + r2l_align_up(2 * sizeof(double) * L.rows * (size_t)(W / 2 + 1));
-#ifndef R2L_EMUL
-    if (int e = r2l_fft_plans(W, L.rows, L.plans)) return e;
+typedef int (*R2LStreamLaunch)(const R2LStaticStreamArgs&, int, void*);
+#define R2L_STREAM_ROW(name, sfx)                                                                \
+  {{name##_bilinear##sfx, name##_malvar##sfx}, {name##_bilinear_u16##sfx, name##_malvar_u16##sfx}, \
+   {name##_bilinear_f64##sfx, name##_malvar_f64##sfx}}
+// [output: float32 | bfloat16 | float16][frames: float32 | 16-bit | float64][bilinear | Malvar2004]
+static const R2LStreamLaunch r2l_static_stream_table[][3][2] = {R2L_STREAM_ROW(r2l_launch_static_stream, ),
+#ifndef R2L_SERIAL
+                                                                R2L_STREAM_ROW(r2l_launch_static_stream, _bf16),
+                                                                R2L_STREAM_ROW(r2l_launch_static_stream, _f16)
 #endif
-    L.total = L.work_off + r2l_align_up(L.plans.work_bytes);
+};
+static const R2LStreamLaunch r2l_static_luma_table[3][2] = R2L_STREAM_ROW(r2l_launch_static_luma, );
+#undef R2L_STREAM_ROW
+#ifndef R2L_SERIAL
+typedef int (*R2LChainLaunch)(const R2LStaticChainArgs&, int, void*);
+#define R2L_CHAIN_ROW(sfx)                                                                                          \
+  {{{r2l_launch_static_chain##sfx, r2l_launch_static_chain_median##sfx},                                            \
+    {r2l_launch_static_chain_unsharp##sfx, r2l_launch_static_chain_unsharp_median##sfx}},                           \
+   {{r2l_launch_static_chain_malvar##sfx, r2l_launch_static_chain_malvar_median##sfx},                              \
+    {r2l_launch_static_chain_malvar_unsharp##sfx, r2l_launch_static_chain_malvar_unsharp_median##sfx}}}
+// [output][frames][Malvar2004][unsharp_masking][median_denoising]; float64 frames with a 16-bit output: none
+static const R2LChainLaunch r2l_static_chain_table[3][3][2][2][2] = {{R2L_CHAIN_ROW(), R2L_CHAIN_ROW(_u16), R2L_CHAIN_ROW(_f64)},
+                                                                     {R2L_CHAIN_ROW(_bf16), R2L_CHAIN_ROW(_u16_bf16)},
+                                                                     {R2L_CHAIN_ROW(_f16), R2L_CHAIN_ROW(_u16_f16)}};
+#undef R2L_CHAIN_ROW
+#endif
+
+// What a static call launches and what it needs, decided from the shape of the call alone: r2l_static_fwd_impl hands it to
+// r2l_static_launch, the workspace queries report `workspace_bytes`, r2l_static_io_supported reports `no_io`
+struct R2LStaticPlan {
+  int route;               // R2L_ROUTE_*
+  bool fft;                // fft_denoising behind MENON / PLANES: the linear image low-passed along its rows, then clip and gamma
+  int ops[2];              // MENON / PLANES: the plane filter (r2l_static_planes.h) of the sharpening and of the denoising stage, 0: none
+  double fft_fraction;
+  const char* refused;     // why the call cannot run at all (-4), or null
+  const char* no_io;       // why a 16-bit output is not served (-3), or null
+  int err;                 // rocFFT could not plan the transforms (its text is in r2l_err)
+  bool too_large;          // more workgroups than a launch takes
+  // workspace of MENON: the (B,3,H,W) float64 image + five (B,H,W) planes; of PLANES: two planes, for fft_denoising the image
+  // behind them; behind either, for fft_denoising, the spectrum and rocFFT's work buffer
+  size_t rgb_off, spec_off, work_off, rows, workspace_bytes;
+  R2LFftPlans fft_plans;
+  // bands of `band_h` rows in `nseg` 256-column strips (CHAIN: the wavefronts of a workgroup), work items, workgroups
+  int nseg, nband, band_h, nitems, grid;
+  R2LStreamLaunch stream;  // STREAM: the whole chain; PLANES: its LUMA instantiation
+#ifndef R2L_SERIAL
+  R2LChainLaunch chain;
+#endif
+};
+// frames: R2L_FRAMES_*; io: R2L_IO_* of the output.  The only reader of the static chains' overrides of diagnostic builds
+// (R2L_STATIC_TILED, R2L_CHAIN_BAND, R2L_STREAM_BANDS, R2L_GRID_STATIC*).  sized = false: without rocFFT's work buffer in
+// `workspace_bytes` -- for callers that ask for `no_io` alone and must not open the library
+static R2LStaticPlan r2l_static_plan(int frames, int B, int H, int W, int debayer, int sharpening, int denoising,
+                                     const R2LStaticOpts& opt, int io, bool sized = true) {
+  R2LStaticPlan p = {};
+  const bool f64 = frames == R2L_FRAMES_F64, menon = debayer == R2L_DEBAYER_MENON2007, malvar = debayer == R2L_DEBAYER_MALVAR2004;
+  const bool unsharp = sharpening == R2L_SHARPEN_UNSHARP, median = denoising == R2L_DENOISE_MEDIAN;
+  const bool luma = sharpening != R2L_SHARPEN_NONE || denoising != R2L_DENOISE_NONE;  // (R2LStaticArgs::full)
+  const bool med5 = median && opt.median_kernel_size != 3;  // the 5x5 median runs as a luma-plane pass
+  const bool quads = (W & 3) == 0;
+  const bool tiled = r2l_env_int("R2L_STATIC_TILED", 0) != 0;
+  p.fft = denoising == R2L_DENOISE_FFT;
+  p.fft_fraction = opt.fft_fraction;
+  p.ops[0] = sharpening == R2L_SHARPEN_FILTER ? 1 : (unsharp ? 4 : 0);
+  p.ops[1] = denoising == R2L_DENOISE_GAUSSIAN ? 2 : (median ? (opt.median_kernel_size == 5 ? 5 : 3) : 0);
+#ifdef R2L_SERIAL
+  const bool chain = false;  // (lane shifts and wave-level exchange: not expressible in the one-lane-at-a-time emulation)
+#else
+  // the luma-chain kernel: every demosaic but Menon2007, every sharpening and denoising but fft_denoising and the 5x5 median, at
+  // least one of them; W % 4 == 0, frames up to 2048 columns (behind unsharp_masking the chroma waits 7 rows for its luma: 28 KB
+  // of LDS per 256-column strip, 4 strips at most)
+  const bool chain = !menon && !med5 && !tiled && quads && W <= (unsharp ? 1024 : 2048) && !p.fft && luma;
+#endif
+  // the tile kernel of the default chain stages float32 frames in LDS
+  const bool full = !f64 && debayer == R2L_DEBAYER_BILINEAR && sharpening == R2L_SHARPEN_FILTER && denoising == R2L_DENOISE_GAUSSIAN;
+  p.route = menon                               ? R2L_ROUTE_MENON
+            : chain                             ? R2L_ROUTE_CHAIN
+            : (p.fft || med5 || (luma && !full)) ? R2L_ROUTE_PLANES
+            : luma                              ? R2L_ROUTE_FULL
+            : (quads && (f64 || !tiled))        ? R2L_ROUTE_STREAM
+                                                : R2L_ROUTE_SHORT;
+  if (menon && (!quads || H < 4 || W < 4))
+    p.refused = "r2l_static_fwd: menon2007 runs as plane passes, which need W % 4 == 0 (and frames of at least 4 x 4)";
+  if (p.route == R2L_ROUTE_PLANES && !quads) p.refused = "r2l_static_fwd: this chain runs as plane passes, which need W % 4 == 0";
+
+  // a 16-bit output: what runs as one launch of a row-streaming kernel on frames up to 2048 columns
+  p.no_io = [&]() -> const char* {
+    if (frames != R2L_FRAMES_F32 && frames != R2L_FRAMES_U16 && frames != R2L_FRAMES_F64) return "frames must be one of R2L_FRAMES_*";
+    if (H < 4 || W < 4 || (H & 1) || (W & 1)) return "H and W must be even and >= 4";
+#ifdef R2L_SERIAL
+    return "the serial emulation has no 16-bit form of the static kernels";
+#else
+    if (menon) return "menon2007 runs as plane passes, which store float32";
+    if (debayer != R2L_DEBAYER_BILINEAR && !malvar) return "unknown debayer";
+    if (sharpening != R2L_SHARPEN_NONE && sharpening != R2L_SHARPEN_FILTER && !unsharp) return "unknown sharpening";
+    if (denoising != R2L_DENOISE_NONE && denoising != R2L_DENOISE_GAUSSIAN && !median && !p.fft) return "unknown denoising";
+    if (p.fft) return "fft_denoising runs as plane passes, which store float32";
+    if (med5) return "the 5x5 median runs as a plane pass, which stores float32";
+    if (!quads) return "needs W % 4 == 0 (the row-streaming kernels)";
+    if (W > 2048) return "needs W <= 2048";
+    if (p.route == R2L_ROUTE_STREAM) return nullptr;
+    if (p.route != R2L_ROUTE_CHAIN)
+      return unsharp && W > 1024 ? "behind unsharp_masking the luma-chain kernel needs W <= 1024"
+                                 : "needs the row-streaming kernels (R2L_STATIC_TILED is set)";
+    return f64 ? "float64 frames on a luma chain store float32" : nullptr;
+#endif
+  }();
+  if (B < 1 || H < 1 || W < 1) return p;
+
+  const size_t px = (size_t)B * H * W;
+  if (p.route == R2L_ROUTE_MENON || p.route == R2L_ROUTE_PLANES) {
+    p.rows = (size_t)3 * B * H;
+    p.rgb_off = menon ? 0 : r2l_align_up(2 * sizeof(double) * px);
+    p.spec_off = menon ? r2l_align_up(8 * sizeof(double) * px) : p.rgb_off + r2l_align_up(3 * sizeof(double) * px);
+    p.workspace_bytes = menon ? p.spec_off : 2 * sizeof(double) * px;
+    if (p.fft) {
+      p.work_off = p.spec_off + r2l_align_up(2 * sizeof(double) * p.rows * (size_t)(W / 2 + 1));
+#ifndef R2L_EMUL
+      if (sized) p.err = r2l_fft_plans(W, p.rows, p.fft_plans);
+#else
+      (void)sized;
+#endif
+      p.workspace_bytes = p.err ? 0 : p.work_off + r2l_align_up(p.fft_plans.work_bytes);
+    }
+  }
+  // (the launch shape: of frames r2l_check_dims lets through, whose counts fit the arithmetic below)
+  if ((size_t)H * W > ((size_t)1 << 29) || px > ((size_t)1 << 40)) return p;
+
+  const int kind = frames == R2L_FRAMES_U16 ? 1 : (f64 ? 2 : 0), out = p.no_io ? R2L_IO_F32 : io;
+  long grid = 0;
+  switch (p.route) {
+    case R2L_ROUTE_MENON: {
+      const size_t g = (px + R2L_NT - 1) / R2L_NT;
+      grid = g > 16384 ? 16384 : (long)g;
+      break;
+    }
+    case R2L_ROUTE_CHAIN: {
+#ifndef R2L_SERIAL
+      // Bands: every band re-computes 7 rows of halo, so tall bands are cheaper (256x1024x1024: 64 rows 1134 us,
+      // 128 rows 1112, 256 rows 1086; profiles/r02_f_chain_bands.txt) -- as tall as leaves ~1024 workgroups (two
+      // rounds of two per CU), but not below 64 rows
+      long nband = (1024 + B - 1) / B;
+      if (nband > H / 64) nband = H / 64;
+      if (const int rows = r2l_env_int("R2L_CHAIN_BAND", 0)) nband = (H + rows - 1) / rows;
+      if (nband < 1) nband = 1;
+      p.band_h = (int)((H + nband - 1) / nband);
+      p.band_h += p.band_h & 1;  // bands start on even rows
+      p.nband = (H + p.band_h - 1) / p.band_h;
+      p.nseg = W <= 256 ? 1 : (W <= 512 ? 2 : (W <= 1024 ? 4 : 8));
+      grid = (long)B * p.nband;
+      p.chain = r2l_static_chain_table[out][kind][malvar][unsharp][median];
+#endif
+      break;
+    }
+    case R2L_ROUTE_PLANES:
+    case R2L_ROUTE_STREAM: {
+      // One wavefront per (image, 256-column strip, row band), dealt in that order, so the ~3,000 wavefronts resident
+      // at any moment work on ADJACENT bands.  Short bands keep that active region of the frames and of the output
+      // compact in HBM (a few tens of MiB instead of a slice of every image of the batch), which is worth far more
+      // than the halo rows every band re-reads (they come from L2): same-buffer A/B on 256x1024x1024, bilinear,
+      // 128 rows per band 862 us, 32 rows 830, 16 rows 800, 8 rows 735-756, 5 rows 754, 4 rows 778, 2 rows 1012.
+      // Malvar (4 halo rows, 5-row window) is flat between 24 and 48 rows per band -- and, round 5, 6 % FASTER at 10 rows (two
+      // full groups of its 5-step unrolled loop): 883 -> 826 us on 256x1024x1024, same buffers (profiles/r05_static_ab.txt;
+      // 9 rows 835, 13 rows 848, 15 rows 836, 5 rows 867, 6 rows -- 4 wasted steps of 10 -- 1000): the same compactness, at
+      // 40 % more fetched rows.  Rounds 1-4 had only swept 24 .. 48.
+      // Round 2, other frame widths (profiles/r02_j_stream_bands.txt): 6-row bands are as good on 1024-wide frames
+      // (0.711 vs 0.709 of the HBM peak) and better on 512- and 256-wide ones (0.718 vs 0.692, 0.724 vs 0.700).
+      p.nseg = (W + 255) / 256;
+      const int rows = malvar ? 10 : 6;
+      long nband = r2l_env_int("R2L_STREAM_BANDS", (H + rows - 1) / rows);
+      if (nband > H / 2) nband = H / 2;
+      if (nband < 1) nband = 1;
+      p.band_h = (int)((H + nband - 1) / nband);
+      p.nband = (H + p.band_h - 1) / p.band_h;
+      const long nitems = (long)B * p.nseg * p.nband;
+      const int wpb = R2L_STREAM_NT / 64;
+      p.nitems = (int)nitems;
+      grid = (nitems + wpb - 1) / wpb;
+      p.too_large = nitems > (1L << 30);
+      p.stream = p.route == R2L_ROUTE_PLANES ? r2l_static_luma_table[kind][malvar] : r2l_static_stream_table[out][kind][malvar];
+      break;
+    }
+    default: {  // persistent 64 x 64 tile walkers
+      const long ntiles = (long)B * ((H + GStatic::TH - 1) / GStatic::TH) * ((W + GStatic::TW - 1) / GStatic::TW);
+      grid = r2l_tile_grid(ntiles > R2L_MAX_BLOCKS ? R2L_MAX_BLOCKS : (int)ntiles,
+                           p.route == R2L_ROUTE_FULL ? r2l_env_int("R2L_GRID_STATIC_FULL", 256) : r2l_env_int("R2L_GRID_STATIC", 1024));
+    }
+  }
+  p.too_large = p.too_large || grid > (1L << 30);
+  p.grid = (int)grid;
+  return p;
+}
+
+// ---- what the launcher's routes share -----------------------------------------------------------------------------------------
+static int r2l_static_grid(size_t items) {  // the flat kernels: R2L_NT items per workgroup, grid-stride beyond 16384 workgroups
+  const size_t g = (items + R2L_NT - 1) / R2L_NT;
+  return g > 16384 ? 16384 : (int)g;
+}
+// the luma plane `cur` through the plan's plane filters, each into the other plane of the pair; `cur` names the result
+static int r2l_static_plane_filters(const R2LStaticPlan& p, const R2LStaticArgs& a, double*& cur, double* other, void* stream) {
+  for (int i = 0; i < 2; ++i) {
+    if (!p.ops[i]) continue;
+    R2LPlaneArgs pa;
+    pa.src = cur;
+    pa.dst = other;
+    pa.B = a.B;
+    pa.H = a.H;
+    pa.W = a.W;
+    pa.op = p.ops[i];
+    for (int k = 0; k < 5; ++k) pa.gk[k] = a.gk[k];
+    for (int k = 0; k < 5; ++k) pa.uk[k] = a.uk[k];
+    pa.amount = a.amount;
+    if (int e = r2l_launch_plane_filter(pa, r2l_static_grid((size_t)a.B * a.H * a.W / 2), stream)) return e;
+    other = cur;
+    cur = pa.dst;
   }
   return 0;
 }
-static int r2l_static_menon_impl(const R2LStaticArgs& a, int B, int H, int W, int sharpening, int denoising,
-                                 const R2LStaticOpts& opt, void* workspace, size_t workspace_bytes, void* stream) {
-  if ((W & 3) || H < 4 || W < 4)
-    return r2l_fail(-4, "r2l_static_fwd: menon2007 runs as plane passes, which need W % 4 == 0 (and frames of at least 4 x 4)");
-  const bool fft = denoising == R2L_DENOISE_FFT;
-  R2LMenonLayout L;
-  if (int e = r2l_menon_layout(B, H, W, fft, L)) return e;
-  if (!workspace || workspace_bytes < L.total)
-    return r2l_fail(-2, "r2l_static_fwd: workspace too small (r2l_static_workspace_bytes)");
-  const size_t px = (size_t)B * H * W;
-  R2LMenonArgs ma;
-  ma.s = a;
-  ma.rgb = (double*)workspace;
-  ma.gh = ma.rgb + 3 * px;
-  ma.gv = ma.gh + px;
-  ma.ch = ma.gv + px;
-  ma.cv = ma.ch + px;
-  ma.m = ma.cv + px;
-  ma.luma = ma.gh;
-  const int ops[2] = {sharpening == R2L_SHARPEN_FILTER ? 1 : (sharpening == R2L_SHARPEN_UNSHARP ? 4 : 0),
-                      denoising == R2L_DENOISE_GAUSSIAN ? 2 : (denoising == R2L_DENOISE_MEDIAN ? (opt.median_kernel_size == 5 ? 5 : 3) : 0)};
-  ma.want_luma = (ops[0] || ops[1]) ? 1 : 0;
-  for (int i = 0; i < 9; ++i) ma.M1[i] = R2L_YUV_FROM_RGB[i];
-  size_t g = (px + R2L_NT - 1) / R2L_NT;
-  if (g > 16384) g = 16384;
-  for (int st = 0; st <= 7; ++st) {
-    ma.stage = st;
-    if (int e = r2l_launch_static_menon(ma, (int)g, stream)) return e;
-  }
-  if (ma.want_luma) {
-    double* cur = ma.gh;     // G_H / G_V are dead behind stage 1: the luma plane and its ping-pong partner
-    double* other = ma.gv;
-    for (int i = 0; i < 2; ++i) {
-      if (!ops[i]) continue;
-      R2LPlaneArgs pa;
-      pa.src = cur;
-      pa.dst = other;
-      pa.B = B;
-      pa.H = H;
-      pa.W = W;
-      pa.op = ops[i];
-      for (int k = 0; k < 5; ++k) pa.gk[k] = a.gk[k];
-      for (int k = 0; k < 5; ++k) pa.uk[k] = a.uk[k];
-      pa.amount = a.amount;
-      size_t gp = (px / 2 + R2L_NT - 1) / R2L_NT;
-      if (gp > 16384) gp = 16384;
-      if (int e = r2l_launch_plane_filter(pa, (int)gp, stream)) return e;
-      double* t = cur;
-      cur = other;
-      other = t;
-    }
-    ma.stage = 8;
-    ma.luma = cur;
-    if (int e = r2l_launch_static_menon(ma, (int)g, stream)) return e;
-  }
-  if (fft) {
-    const int cut0 = (int)(W * opt.fft_fraction), cut1 = (int)(W * (1 - opt.fft_fraction));
+// fft_denoising, then the rest of the chain: the linear image at rgb_off low-passed along its rows -- bins
+// int(c * keep_fraction) <= k < int(c * (1 - keep_fraction)) zeroed (pipeline_numpy.py:229-230; default 0.3) -- then clip, gamma
+static int r2l_static_lowpass_finish(const R2LStaticPlan& p, const R2LStaticArgs& a, void* workspace, void* stream) {
+  double* rgb = (double*)((char*)workspace + p.rgb_off);
+  if (p.fft) {
+    const int cut0 = (int)(a.W * p.fft_fraction), cut1 = (int)(a.W * (1 - p.fft_fraction));
 #ifdef R2L_EMUL
-    r2l_fft_lowpass_rows_host(ma.rgb, L.rows, W, cut0, cut1);
+    r2l_fft_lowpass_rows_host(rgb, p.rows, a.W, cut0, cut1);
 #else
-    double* spec = (double*)((char*)workspace + L.spec_off);
-    void* work = (char*)workspace + L.work_off;
-    if (int e = r2l_fft_exec(L.plans.fwd, ma.rgb, spec, work, L.plans.work_bytes, stream)) return e;
-    R2LSpecMaskArgs sm{spec, L.rows, W, cut0, cut1};
-    size_t gm = (L.rows * (size_t)(W / 2 + 1) + R2L_NT - 1) / R2L_NT;
-    if (gm > 16384) gm = 16384;
-    if (int e = r2l_launch_spec_mask(sm, (int)gm, stream)) return e;
-    if (int e = r2l_fft_exec(L.plans.inv, spec, ma.rgb, work, L.plans.work_bytes, stream)) return e;
+    double* spec = (double*)((char*)workspace + p.spec_off);
+    void* work = (char*)workspace + p.work_off;
+    if (int e = r2l_fft_exec(p.fft_plans.fwd, rgb, spec, work, p.fft_plans.work_bytes, stream)) return e;
+    R2LSpecMaskArgs sm{spec, p.rows, a.W, cut0, cut1};
+    if (int e = r2l_launch_spec_mask(sm, r2l_static_grid(p.rows * (size_t)(a.W / 2 + 1)), stream)) return e;
+    if (int e = r2l_fft_exec(p.fft_plans.inv, spec, rgb, work, p.fft_plans.work_bytes, stream)) return e;
 #endif
   }
-  R2LStaticFinishArgs fa{a, ma.rgb};
-  size_t gf = (px / 4 + R2L_NT - 1) / R2L_NT;
-  if (gf > 16384) gf = 16384;
-  return r2l_launch_static_finish(fa, (int)gf, stream);
+  R2LStaticFinishArgs fa{a, rgb};
+  return r2l_launch_static_finish(fa, r2l_static_grid((size_t)a.B * a.H * a.W / 4), stream);
+}
+
+// a plan that is neither refused nor too large, and a workspace of its workspace_bytes
+static int r2l_static_launch(const R2LStaticPlan& p, const R2LStaticArgs& a, void* workspace, void* stream) {
+  const size_t px = (size_t)a.B * a.H * a.W;
+  switch (p.route) {
+    case R2L_ROUTE_MENON: {
+      R2LMenonArgs ma;
+      ma.s = a;
+      ma.rgb = (double*)workspace;
+      ma.gh = ma.rgb + 3 * px;
+      ma.gv = ma.gh + px;
+      ma.ch = ma.gv + px;
+      ma.cv = ma.ch + px;
+      ma.m = ma.cv + px;
+      ma.luma = ma.gh;
+      ma.want_luma = (p.ops[0] || p.ops[1]) ? 1 : 0;
+      for (int i = 0; i < 9; ++i) ma.M1[i] = R2L_YUV_FROM_RGB[i];
+      for (int st = 0; st <= 7; ++st) {
+        ma.stage = st;
+        if (int e = r2l_launch_static_menon(ma, p.grid, stream)) return e;
+      }
+      if (ma.want_luma) {
+        double* cur = ma.gh;  // G_H / G_V are dead behind stage 1: the luma plane and its ping-pong partner
+        if (int e = r2l_static_plane_filters(p, a, cur, ma.gv, stream)) return e;
+        ma.stage = 8;
+        ma.luma = cur;
+        if (int e = r2l_launch_static_menon(ma, p.grid, stream)) return e;
+      }
+      return r2l_static_lowpass_finish(p, a, workspace, stream);
+    }
+#ifndef R2L_SERIAL
+    case R2L_ROUTE_CHAIN: {
+      R2LStaticChainArgs ca;
+      ca.s = a;
+      ca.nband = p.nband;
+      ca.band_h = p.band_h;
+      ca.nw = p.nseg;
+      return p.chain(ca, p.grid, stream);
+    }
+#endif
+    case R2L_ROUTE_PLANES:
+    case R2L_ROUTE_STREAM: {
+      R2LStaticStreamArgs sa;
+      sa.s = a;
+      sa.nseg = p.nseg;
+      sa.nband = p.nband;
+      sa.band_h = p.band_h;
+      sa.nitems = p.nitems;
+      sa.luma_out = nullptr;
+      sa.luma_in = nullptr;
+      sa.lin_out = nullptr;
+      if (p.route == R2L_ROUTE_STREAM) return p.stream(sa, p.grid, stream);
+      double* cur = (double*)workspace;
+      sa.luma_out = cur;
+      if (int e = p.stream(sa, p.grid, stream)) return e;
+      if (int e = r2l_static_plane_filters(p, a, cur, (double*)workspace + px, stream)) return e;
+      sa.luma_out = nullptr;
+      sa.luma_in = cur;
+      if (!p.fft) return p.stream(sa, p.grid, stream);
+      // fft_denoising: the sharpened RGB as float64 planes instead of the output
+      sa.lin_out = (double*)((char*)workspace + p.rgb_off);
+      if (int e = p.stream(sa, p.grid, stream)) return e;
+      return r2l_static_lowpass_finish(p, a, workspace, stream);
+    }
+    case R2L_ROUTE_FULL:
+      return r2l_launch_static_full(a, p.grid, stream);
+    default:
+      return r2l_launch_static_short(a, p.grid, stream);
+  }
 }
 
 static int r2l_static_fwd_impl(const R2LRaw& raw, float* out, int B, int H, int W, const double* camera_host,
@@ -1951,174 +2120,16 @@ static int r2l_static_fwd_impl(const R2LRaw& raw, float* out, int B, int H, int 
   if (const char* why = r2l_static_opts_problem(opt, sharpening, denoising)) return r2l_fail(-4, std::string("r2l_static_fwd: ") + why);
   R2LStaticArgs a;
   r2l_static_setup(a, raw, out, B, H, W, camera_host, debayer, sharpening, denoising, gamma, mean_std_host, opt);
-  const char* const no_io = "r2l_static_fwd_io: no 16-bit form of the kernels this call takes (r2l_static_io_supported)";
-  if (debayer == R2L_DEBAYER_MENON2007) {
-    if (io != R2L_IO_F32) return r2l_fail(-3, no_io);
-    return r2l_static_menon_impl(a, B, H, W, sharpening, denoising, opt, workspace, workspace_bytes, stream);
-  }
-  const int ntiles = B * ((H + GStatic::TH - 1) / GStatic::TH) * ((W + GStatic::TW - 1) / GStatic::TW);
-#ifndef R2L_SERIAL
-  if (r2l_static_is_chain(W, debayer, sharpening, denoising, opt.median_kernel_size)) {
-    R2LStaticChainArgs ca;
-    ca.s = a;
-    // Bands: every band re-computes 7 rows of halo, so tall bands are cheaper (256x1024x1024: 64 rows 1134 us,
-    // 128 rows 1112, 256 rows 1086; profiles/r02_f_chain_bands.txt) -- as tall as leaves ~1024 workgroups (two
-    // rounds of two per CU), but not below 64 rows
-    long nband = (1024 + B - 1) / B;
-    if (nband > H / 64) nband = H / 64;
-    nband = r2l_env_int("R2L_CHAIN_BAND", 0) ? (H + r2l_env_int("R2L_CHAIN_BAND", 64) - 1) / r2l_env_int("R2L_CHAIN_BAND", 64) : nband;
-    if (nband < 1) nband = 1;
-    ca.band_h = (int)((H + nband - 1) / nband);
-    ca.band_h += ca.band_h & 1;  // bands start on even rows
-    ca.nband = (H + ca.band_h - 1) / ca.band_h;
-    const long grid = (long)B * ca.nband;
-    if (grid > (1L << 30)) return r2l_fail(-1, "r2l_static_fwd: batch too large");
-    ca.nw = W <= 256 ? 1 : (W <= 512 ? 2 : (W <= 1024 ? 4 : 8));
-    const int kind = raw.u16 ? 1 : (raw.f64 ? 2 : 0);
-    const int deb = debayer == R2L_DEBAYER_MALVAR2004 ? 1 : 0, dn = denoising == R2L_DENOISE_MEDIAN ? 1 : 0;
-    typedef int (*launch_t)(const R2LStaticChainArgs&, int, void*);
-    const int sh = sharpening == R2L_SHARPEN_UNSHARP ? 1 : 0;
-#define R2L_CHAIN_ROW(sfx)                                                                                          \
-  {{{r2l_launch_static_chain##sfx, r2l_launch_static_chain_median##sfx},                                            \
-    {r2l_launch_static_chain_unsharp##sfx, r2l_launch_static_chain_unsharp_median##sfx}},                           \
-   {{r2l_launch_static_chain_malvar##sfx, r2l_launch_static_chain_malvar_median##sfx},                              \
-    {r2l_launch_static_chain_malvar_unsharp##sfx, r2l_launch_static_chain_malvar_unsharp_median##sfx}}}
-    static const launch_t table[3][2][2][2] = {R2L_CHAIN_ROW(), R2L_CHAIN_ROW(_u16), R2L_CHAIN_ROW(_f64)};
-    static const launch_t table_io[2][2][2][2][2] = {{R2L_CHAIN_ROW(_bf16), R2L_CHAIN_ROW(_u16_bf16)},
-                                                     {R2L_CHAIN_ROW(_f16), R2L_CHAIN_ROW(_u16_f16)}};
-#undef R2L_CHAIN_ROW
-    if (io != R2L_IO_F32) {
-      if (kind == 2) return r2l_fail(-3, no_io);
-      return table_io[io == R2L_IO_F16][kind][deb][sh][dn](ca, (int)grid, stream);
-    }
-    return table[kind][deb][sh][dn](ca, (int)grid, stream);
-  }
-  if (io != R2L_IO_F32 && (a.full || (W & 3) || (!raw.f64 && r2l_env_int("R2L_STATIC_TILED", 0)))) return r2l_fail(-3, no_io);
-#else
-  if (io != R2L_IO_F32) return r2l_fail(-3, no_io);
-#endif
-  if (!r2l_static_is_fused(W, debayer, sharpening, denoising, raw.f64 != nullptr, opt.median_kernel_size)) {
-    // luma-plane passes: raw -> Y | sharpen | denoise | raw + Y'' -> RGB
-    if (W & 3) return r2l_fail(-4, "r2l_static_fwd: this chain runs as plane passes, which need W % 4 == 0");
-    const size_t plane_bytes = sizeof(double) * (size_t)B * H * W;
-    const bool fft = denoising == R2L_DENOISE_FFT;
-    R2LFftLayout L;
-    if (fft)
-      if (int e = r2l_fft_layout(B, H, W, L)) return e;
-    if (!workspace || workspace_bytes < (fft ? L.total : 2 * plane_bytes))
-      return r2l_fail(-2, "r2l_static_fwd: workspace too small (r2l_static_workspace_bytes)");
-    double* p0 = (double*)workspace;
-    double* p1 = p0 + (size_t)B * H * W;
-    R2LStaticStreamArgs sa;
-    sa.s = a;
-    r2l_stream_shape(sa, B, H, W, debayer);
-    const long nitems = (long)B * sa.nseg * sa.nband;
-    if (nitems > (1L << 30)) return r2l_fail(-1, "r2l_static_fwd: batch too large");
-    sa.nitems = (int)nitems;
-    const int wpb = R2L_STREAM_NT / 64;
-    const int sgrid = (int)((nitems + wpb - 1) / wpb);
-    auto stream_pass = [&](const R2LStaticStreamArgs& x) {
-      if (raw.u16)
-        return debayer == R2L_DEBAYER_MALVAR2004 ? r2l_launch_static_luma_malvar_u16(x, sgrid, stream)
-                                                 : r2l_launch_static_luma_bilinear_u16(x, sgrid, stream);
-      if (raw.f64)
-        return debayer == R2L_DEBAYER_MALVAR2004 ? r2l_launch_static_luma_malvar_f64(x, sgrid, stream)
-                                                 : r2l_launch_static_luma_bilinear_f64(x, sgrid, stream);
-      return debayer == R2L_DEBAYER_MALVAR2004 ? r2l_launch_static_luma_malvar(x, sgrid, stream)
-                                               : r2l_launch_static_luma_bilinear(x, sgrid, stream);
-    };
-    sa.luma_out = p0;
-    sa.luma_in = nullptr;
-    sa.lin_out = nullptr;
-    if (int e = stream_pass(sa)) return e;
-    double* cur = p0;
-    double* other = p1;
-    const int ops[2] = {sharpening == R2L_SHARPEN_FILTER ? 1 : (sharpening == R2L_SHARPEN_UNSHARP ? 4 : 0),
-                        denoising == R2L_DENOISE_GAUSSIAN ? 2 : (denoising == R2L_DENOISE_MEDIAN ? (opt.median_kernel_size == 5 ? 5 : 3) : 0)};
-    for (int i = 0; i < 2; ++i) {
-      if (!ops[i]) continue;
-      R2LPlaneArgs pa;
-      pa.src = cur;
-      pa.dst = other;
-      pa.B = B;
-      pa.H = H;
-      pa.W = W;
-      pa.op = ops[i];
-      for (int k = 0; k < 5; ++k) pa.gk[k] = a.gk[k];
-      for (int k = 0; k < 5; ++k) pa.uk[k] = a.uk[k];
-      pa.amount = a.amount;
-      size_t g = ((size_t)B * H * W / 2 + R2L_NT - 1) / R2L_NT;
-      if (g > 16384) g = 16384;
-      if (int e = r2l_launch_plane_filter(pa, (int)g, stream)) return e;
-      double* t = cur;
-      cur = other;
-      other = t;
-    }
-    sa.luma_out = nullptr;
-    sa.luma_in = cur;
-    if (!fft) return stream_pass(sa);
-    // fft_denoising: sharpened RGB as float64 planes -> low-pass along the columns -> clip, gamma
-    double* rgb = (double*)((char*)workspace + L.rgb_off);
-    double* spec = (double*)((char*)workspace + L.spec_off);
-    sa.lin_out = rgb;
-    if (int e = stream_pass(sa)) return e;
-    // int(c * keep_fraction), int(c * (1 - keep_fraction)) (pipeline_numpy.py:229-230; default 0.3)
-    const int cut0 = (int)(W * opt.fft_fraction), cut1 = (int)(W * (1 - opt.fft_fraction));
-#ifdef R2L_EMUL
-    (void)spec;
-    r2l_fft_lowpass_rows_host(rgb, L.rows, W, cut0, cut1);
-#else
-    void* work = (char*)workspace + L.work_off;
-    if (int e = r2l_fft_exec(L.plans.fwd, rgb, spec, work, L.plans.work_bytes, stream)) return e;
-    R2LSpecMaskArgs ma{spec, L.rows, W, cut0, cut1};
-    size_t gm = (L.rows * (size_t)(W / 2 + 1) + R2L_NT - 1) / R2L_NT;
-    if (gm > 16384) gm = 16384;
-    if (int e = r2l_launch_spec_mask(ma, (int)gm, stream)) return e;
-    if (int e = r2l_fft_exec(L.plans.inv, spec, rgb, work, L.plans.work_bytes, stream)) return e;
-#endif
-    R2LStaticFinishArgs fa{a, rgb};
-    size_t gf = ((size_t)B * H * W / 4 + R2L_NT - 1) / R2L_NT;
-    if (gf > 16384) gf = 16384;
-    return r2l_launch_static_finish(fa, (int)gf, stream);
-  }
-  if (a.full) {
-    const int grid = r2l_tile_grid(ntiles, r2l_env_int("R2L_GRID_STATIC_FULL", 256));
-    return r2l_launch_static_full(a, grid, stream);
-  }
-  if ((W & 3) == 0 && (raw.f64 || !r2l_env_int("R2L_STATIC_TILED", 0))) {
-    R2LStaticStreamArgs sa;
-    sa.s = a;
-    sa.luma_out = nullptr;
-    sa.luma_in = nullptr;
-    r2l_stream_shape(sa, B, H, W, debayer);
-    const long nitems = (long)B * sa.nseg * sa.nband;
-    if (nitems > (1L << 30)) return r2l_fail(-1, "r2l_static_fwd: batch too large");
-    sa.nitems = (int)nitems;
-    const int wpb = R2L_STREAM_NT / 64;
-    const int grid = (int)((nitems + wpb - 1) / wpb);
-#ifndef R2L_SERIAL
-    if (io != R2L_IO_F32) {
-      typedef int (*launch_t)(const R2LStaticStreamArgs&, int, void*);
-#define R2L_STREAM_ROW(sfx)                                                                          \
-  {{r2l_launch_static_stream_bilinear##sfx, r2l_launch_static_stream_malvar##sfx},                   \
-   {r2l_launch_static_stream_bilinear_u16##sfx, r2l_launch_static_stream_malvar_u16##sfx},           \
-   {r2l_launch_static_stream_bilinear_f64##sfx, r2l_launch_static_stream_malvar_f64##sfx}}
-      static const launch_t table_io[2][3][2] = {R2L_STREAM_ROW(_bf16), R2L_STREAM_ROW(_f16)};
-#undef R2L_STREAM_ROW
-      return table_io[io == R2L_IO_F16][raw.u16 ? 1 : (raw.f64 ? 2 : 0)][debayer == R2L_DEBAYER_MALVAR2004](sa, grid, stream);
-    }
-#endif
-    if (raw.u16)
-      return debayer == R2L_DEBAYER_MALVAR2004 ? r2l_launch_static_stream_malvar_u16(sa, grid, stream)
-                                               : r2l_launch_static_stream_bilinear_u16(sa, grid, stream);
-    if (raw.f64)
-      return debayer == R2L_DEBAYER_MALVAR2004 ? r2l_launch_static_stream_malvar_f64(sa, grid, stream)
-                                               : r2l_launch_static_stream_bilinear_f64(sa, grid, stream);
-    return debayer == R2L_DEBAYER_MALVAR2004 ? r2l_launch_static_stream_malvar(sa, grid, stream)
-                                             : r2l_launch_static_stream_bilinear(sa, grid, stream);
-  }
-  const int grid = r2l_tile_grid(ntiles, r2l_env_int("R2L_GRID_STATIC", 1024));
-  return r2l_launch_static_short(a, grid, stream);
+  const int frames = raw.u16 ? R2L_FRAMES_U16 : (raw.f64 ? R2L_FRAMES_F64 : R2L_FRAMES_F32);
+  const R2LStaticPlan p = r2l_static_plan(frames, B, H, W, debayer, sharpening, denoising, opt, io);
+  if (io != R2L_IO_F32 && p.no_io)
+    return r2l_fail(-3, "r2l_static_fwd_io: no 16-bit form of the kernels this call takes (r2l_static_io_supported)");
+  if (p.refused) return r2l_fail(-4, p.refused);
+  if (p.err) return p.err;
+  if (p.workspace_bytes && (!workspace || workspace_bytes < p.workspace_bytes))
+    return r2l_fail(-2, "r2l_static_fwd: workspace too small (r2l_static_workspace_bytes)");
+  if (p.too_large) return r2l_fail(-1, "r2l_static_fwd: batch too large");
+  return r2l_static_launch(p, a, workspace, stream);
 }
 
 int r2l_isp_fwd(const float* raw, const float* params, const float* additive,
@@ -2184,35 +2195,19 @@ int r2l_raw2rgb_fwd_u16(const unsigned short* raw, float denom, const float* bla
   return r2l_raw2rgb_fwd_impl(r2l_raw_u16(raw, denom), black_level, out, B, H, W, reduce_size, out_channels,
                               stream);
 }
-static size_t r2l_static_ws(int B, int H, int W, int debayer, int sharpening, int denoising, bool f64, int median_size = 3) {
-  if (B < 1 || H < 1 || W < 1) return 0;
-  if (debayer == R2L_DEBAYER_MENON2007) {
-    R2LMenonLayout L;
-    if (r2l_menon_layout(B, H, W, denoising == R2L_DENOISE_FFT, L)) return 0;
-    return L.total;
-  }
-  if (r2l_static_is_fused(W, debayer, sharpening, denoising, f64, median_size)) return 0;
-  if (denoising == R2L_DENOISE_FFT) {
-    R2LFftLayout L;
-    if (r2l_fft_layout(B, H, W, L)) return 0;
-    return L.total;
-  }
-  return 2 * sizeof(double) * (size_t)B * H * W;
+static size_t r2l_static_ws(int frames, int B, int H, int W, int debayer, int sharpening, int denoising,
+                            const R2LStaticOpts& opt = R2LStaticOpts()) {
+  return r2l_static_plan(frames, B, H, W, debayer, sharpening, denoising, opt, R2L_IO_F32).workspace_bytes;
 }
 size_t r2l_static_workspace_bytes(int B, int H, int W, int debayer, int sharpening, int denoising) {
-  return r2l_static_ws(B, H, W, debayer, sharpening, denoising, false);
+  return r2l_static_ws(R2L_FRAMES_F32, B, H, W, debayer, sharpening, denoising);
 }
 size_t r2l_static_workspace_bytes_f64(int B, int H, int W, int debayer, int sharpening, int denoising) {
-  return r2l_static_ws(B, H, W, debayer, sharpening, denoising, true);
+  return r2l_static_ws(R2L_FRAMES_F64, B, H, W, debayer, sharpening, denoising);
 }
 size_t r2l_static_workspace_bytes_opts(int frames, int B, int H, int W, int debayer, int sharpening, int denoising,
                                        const double* options_host) {
-  int med = 3;
-  if (options_host) {
-    const double m = options_host[R2L_SOPT_MEDIAN_SIZE];
-    med = (m == (double)(int)m) ? (int)m : 3;
-  }
-  return r2l_static_ws(B, H, W, debayer, sharpening, denoising, frames == R2L_FRAMES_F64, med);
+  return r2l_static_ws(frames, B, H, W, debayer, sharpening, denoising, r2l_static_opts(options_host, 3));
 }
 int r2l_static_fwd_f64(const double* raw, float* out, int B, int H, int W, const double* camera_host,
                        int debayer, int sharpening, int denoising, double gamma, void* workspace,
@@ -2246,17 +2241,8 @@ int r2l_static_fwd_opts(const void* raw, int frames, float denom, float* out, in
                         const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
                         const double* options_host, const float* mean_std_host, void* workspace, size_t workspace_bytes,
                         void* stream) {
-  R2LStaticOpts o;
-  if (options_host) {
-    o.sharp_radius = options_host[R2L_SOPT_SHARP_RADIUS];
-    o.sharp_amount = options_host[R2L_SOPT_SHARP_AMOUNT];
-    o.gaussian_sigma = options_host[R2L_SOPT_GAUSSIAN_SIGMA];
-    o.fft_fraction = options_host[R2L_SOPT_FFT_FRACTION];
-    const double m = options_host[R2L_SOPT_MEDIAN_SIZE];
-    o.median_kernel_size = (m == (double)(int)m) ? (int)m : -1;
-  }
   return r2l_static_fwd_any(raw, frames, denom, out, B, H, W, camera_host, debayer, sharpening, denoising, gamma, mean_std_host,
-                            o, workspace, workspace_bytes, stream);
+                            r2l_static_opts(options_host), workspace, workspace_bytes, stream);
 }
 static int r2l_static_fwd_any(const void* raw, int frames, float denom, float* out, int B, int H, int W,
                               const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
@@ -2276,42 +2262,12 @@ static int r2l_static_fwd_any(const void* raw, int frames, float denom, float* o
 }
 
 // ---- 16-bit output of the static chains (include/r2l_isp.h: r2l_static_fwd_io) -------------------------------------------------
-// why a 16-bit call is not served, or null: the ONE predicate of r2l_static_io_supported and r2l_static_fwd_io.  Served: what
-// runs as one launch of a row-streaming kernel (r2l_static_stream.h, r2l_static_chain.h) on frames up to 2048 columns
-static const char* r2l_static_io_why(int frames, int H, int W, int debayer, int sharpening, int denoising, int median_size) {
-  if (frames != R2L_FRAMES_F32 && frames != R2L_FRAMES_U16 && frames != R2L_FRAMES_F64) return "frames must be one of R2L_FRAMES_*";
-  if (H < 4 || W < 4 || (H & 1) || (W & 1)) return "H and W must be even and >= 4";
-#ifdef R2L_SERIAL
-  (void)debayer; (void)sharpening; (void)denoising; (void)median_size;
-  return "the serial emulation has no 16-bit form of the static kernels";
-#else
-  if (debayer == R2L_DEBAYER_MENON2007) return "menon2007 runs as plane passes, which store float32";
-  if (debayer != R2L_DEBAYER_BILINEAR && debayer != R2L_DEBAYER_MALVAR2004) return "unknown debayer";
-  if (sharpening != R2L_SHARPEN_NONE && sharpening != R2L_SHARPEN_FILTER && sharpening != R2L_SHARPEN_UNSHARP) return "unknown sharpening";
-  if (denoising != R2L_DENOISE_NONE && denoising != R2L_DENOISE_GAUSSIAN && denoising != R2L_DENOISE_MEDIAN && denoising != R2L_DENOISE_FFT)
-    return "unknown denoising";
-  if (denoising == R2L_DENOISE_FFT) return "fft_denoising runs as plane passes, which store float32";
-  if (denoising == R2L_DENOISE_MEDIAN && median_size != 3) return "the 5x5 median runs as a plane pass, which stores float32";
-  if (W & 3) return "needs W % 4 == 0 (the row-streaming kernels)";
-  if (W > 2048) return "needs W <= 2048";
-  if (sharpening == R2L_SHARPEN_NONE && denoising == R2L_DENOISE_NONE) {
-    if (frames != R2L_FRAMES_F64 && r2l_env_int("R2L_STATIC_TILED", 0)) return "needs the row-streaming kernels (R2L_STATIC_TILED is set)";
-    return nullptr;
-  }
-  if (!r2l_static_is_chain(W, debayer, sharpening, denoising, median_size))
-    return sharpening == R2L_SHARPEN_UNSHARP && W > 1024 ? "behind unsharp_masking the luma-chain kernel needs W <= 1024"
-                                                         : "needs the row-streaming kernels (R2L_STATIC_TILED is set)";
-  if (frames == R2L_FRAMES_F64) return "float64 frames on a luma chain store float32";
-  return nullptr;
-#endif
-}
-static int r2l_static_median_size(const double* options_host) {
-  if (!options_host) return 3;
-  const double m = options_host[R2L_SOPT_MEDIAN_SIZE];
-  return (m == (double)(int)m) ? (int)m : -1;
+// why a 16-bit call is not served, or null: the plan's answer, for r2l_static_io_supported and r2l_static_fwd_io alike
+static const char* r2l_static_io_why(int frames, int H, int W, int debayer, int sharpening, int denoising, const R2LStaticOpts& opt) {
+  return r2l_static_plan(frames, 1, H, W, debayer, sharpening, denoising, opt, R2L_IO_BF16, false).no_io;
 }
 const char* r2l_static_io_supported(int frames, int H, int W, int debayer, int sharpening, int denoising, const double* options_host) {
-  return r2l_static_io_why(frames, H, W, debayer, sharpening, denoising, r2l_static_median_size(options_host));
+  return r2l_static_io_why(frames, H, W, debayer, sharpening, denoising, r2l_static_opts(options_host));
 }
 int r2l_static_fwd_io(const void* raw, int frames, float denom, void* out, int out_io, int B, int H, int W,
                       const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
@@ -2321,17 +2277,10 @@ int r2l_static_fwd_io(const void* raw, int frames, float denom, void* out, int o
     return r2l_static_fwd_opts(raw, frames, denom, (float*)out, B, H, W, camera_host, debayer, sharpening, denoising, gamma,
                                options_host, mean_std_host, workspace, workspace_bytes, stream);
   if (out_io != R2L_IO_BF16 && out_io != R2L_IO_F16) return r2l_fail(-1, "r2l_static_fwd_io: out_io must be one of R2L_IO_*");
-  if (const char* why = r2l_static_io_why(frames, H, W, debayer, sharpening, denoising, r2l_static_median_size(options_host)))
+  const R2LStaticOpts o = r2l_static_opts(options_host);
+  if (const char* why = r2l_static_io_why(frames, H, W, debayer, sharpening, denoising, o))
     return r2l_fail(-3, std::string("r2l_static_fwd_io: a 16-bit output is not served here: ") + why);
   if ((uintptr_t)out % 8) return r2l_fail(-1, "r2l_static_fwd_io: the 16-bit output must be 8-byte aligned");
-  R2LStaticOpts o;
-  if (options_host) {
-    o.sharp_radius = options_host[R2L_SOPT_SHARP_RADIUS];
-    o.sharp_amount = options_host[R2L_SOPT_SHARP_AMOUNT];
-    o.gaussian_sigma = options_host[R2L_SOPT_GAUSSIAN_SIGMA];
-    o.fft_fraction = options_host[R2L_SOPT_FFT_FRACTION];
-    o.median_kernel_size = r2l_static_median_size(options_host);
-  }
   return r2l_static_fwd_any(raw, frames, denom, (float*)out, B, H, W, camera_host, debayer, sharpening, denoising, gamma,
                             mean_std_host, o, workspace, workspace_bytes, stream, out_io);
 }
