@@ -287,6 +287,31 @@ int r2l_isp_step_bwd_io(const void *raw, int raw_u16, float denom, const float *
                         const double *gathered_sums, void *stream, float *grad_raw, void *raw_grad_scratch,
                         size_t raw_grad_scratch_bytes, unsigned grad_mask);
 
+/* ---- channels-last output and cotangent (task models run in torch.channels_last) ----------------------------------------------
+ * r2l_isp_step_fwd_layout / r2l_isp_step_bwd_layout = the _io calls with the memory layout of `out` resp. `grad_out` as well.
+ * R2L_LAYOUT_NCHW: the ISP's own planar (B,3,H,W) -- exactly the _io call, no further condition (the _io entry points forward
+ * here).  R2L_LAYOUT_NHWC: the element of image b, channel k, pixel (y, x) lies at 3 (b H W + y W + x) + k, i.e. a (B,3,H,W)
+ * tensor with torch.channels_last strides; every value is the one the planar call writes resp. reads, bit for bit, in all
+ * three element types (float32 included).  An NHWC call is served where r2l_isp_io_supported serves a 16-bit call
+ * (r2l_isp_layout_supported: 1 or 0; no additive layer, W % 4 == 0, W <= 2048, no R2L_STEP_EPI_*, R2L_STEP_KEEP_LUMA in both
+ * calls, a device build or the lock-step emulation) and behaves like one: the backward takes the plane passes and the
+ * recomputing BatchNorm sums at every size and the full route for any grad_mask, grad_additive must be NULL, `out` of the
+ * backward is not read.  An unserved call returns -3 with the reason in r2l_last_error() and writes nothing; a layout outside
+ * the enum returns -1; a lane moves its 4 pixels x 3 channels as 12 consecutive elements, so an NHWC `out` / `grad_out` must be
+ * 16-byte aligned in float32 and 8-byte aligned in 16 bits (-1 otherwise).  Deterministic: no atomics.                       */
+enum { R2L_LAYOUT_NCHW = 0, R2L_LAYOUT_NHWC = 1 };
+int r2l_isp_layout_supported(int io, int layout, int raw_u16, int has_additive, int B, int H, int W, int phase);
+int r2l_isp_step_fwd_layout(const void *raw, int raw_u16, float denom, const float *const *params_host,
+                            const float *additive, int bn_mode, float *running_mean, float *running_var,
+                            long long *num_batches_tracked, double eps, double momentum, void *out, int io, int layout,
+                            void *workspace, size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                            const double *gathered_stats, void *stream);
+int r2l_isp_step_bwd_layout(const void *raw, int raw_u16, float denom, const float *additive, const void *grad_out, int io,
+                            int layout, const void *out, float *grad_params, float *grad_additive, int bn_mode,
+                            void *workspace, size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                            const double *gathered_sums, void *stream, float *grad_raw, void *raw_grad_scratch,
+                            size_t raw_grad_scratch_bytes, unsigned grad_mask);
+
 /* ---- static pipeline, numpy semantics (processing(), processing/pipeline_numpy.py:70-141, batched):
  * remove_blacklv (:152-158) -> demosaicing_CFA_Bayer_{bilinear,Malvar2004} (:92-95) -> wb (:161-162) ->
  * CCM (:165-167) -> [sharpening_filter (:180-191) | unsharp_masking (:170-177)] -> [gaussian_denoising (:203-209) | median_denoising

@@ -92,6 +92,17 @@ _SIGNATURES = {
                                            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, _c_float_p,
                                            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint]),
+    'r2l_isp_layout_supported': (ctypes.c_int, [ctypes.c_int] * 8),
+    'r2l_isp_step_fwd_layout': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.POINTER(ctypes.c_void_p),
+                                               _c_float_p, ctypes.c_int, _c_float_p, _c_float_p, ctypes.c_void_p,
+                                               ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    'r2l_isp_step_bwd_layout': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, _c_float_p, ctypes.c_void_p,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_void_p, _c_float_p, _c_float_p,
+                                               ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                               _c_float_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint]),
     'r2l_additive_bwd': (ctypes.c_int, [_c_float_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p,
                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     'r2l_isp_fwd_u16': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, _c_float_p, _c_float_p, _c_float_p,

@@ -218,6 +218,10 @@ R2L_FS_KERNEL_EPI(r2l_launch_fwd_stream_epi_w8_u16, 8, true)
   R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w8_u16##sfx, 8, true, IO)
 R2L_FS_KERNELS_IO(_bf16, R2L_IO_BF16)
 R2L_FS_KERNELS_IO(_f16, R2L_IO_F16)
+// ... writing it channels-last (r2l_isp_step_fwd_layout: R2L_LAYOUT_NHWC; float32 and 16 bits, no epilogue)
+R2L_FS_KERNELS_IO(_nhwc, R2L_IO_F32 | R2L_IO_NHWC)
+R2L_FS_KERNELS_IO(_bf16_nhwc, R2L_IO_BF16 | R2L_IO_NHWC)
+R2L_FS_KERNELS_IO(_f16_nhwc, R2L_IO_F16 | R2L_IO_NHWC)
 // the apply pass of train-mode BatchNorm on the Y' plane the statistics pass kept: independent wavefronts, no LDS
 #ifndef R2L_FA_OCC
 #define R2L_FA_OCC 3
@@ -238,6 +242,12 @@ R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_bf16, false, R2L_IO_BF16)
 R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_u16_bf16, true, R2L_IO_BF16)
 R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_f16, false, R2L_IO_F16)
 R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_u16_f16, true, R2L_IO_F16)
+R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_nhwc, false, R2L_IO_F32 | R2L_IO_NHWC)
+R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_u16_nhwc, true, R2L_IO_F32 | R2L_IO_NHWC)
+R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_bf16_nhwc, false, R2L_IO_BF16 | R2L_IO_NHWC)
+R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_u16_bf16_nhwc, true, R2L_IO_BF16 | R2L_IO_NHWC)
+R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_f16_nhwc, false, R2L_IO_F16 | R2L_IO_NHWC)
+R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_u16_f16_nhwc, true, R2L_IO_F16 | R2L_IO_NHWC)
 // ... the same walk without output: the BatchNorm statistics from the kept plane (2 wavefronts per workgroup, each with
 // its own work items; <= R2L_MAX_BLOCKS workgroups = partials of the reduction tree)
 #define R2L_FA_STATS_NWV 4
@@ -300,6 +310,9 @@ R2L_BLOCKFN void r2l_bwd1_plane_guv_io_block(const R2LBwd1GuvArgs& a, int bid, i
                     r2l_bwd1_plane_guv_io_block<IO>)
 R2L_BP_KERNELS_IO(_bf16, R2L_IO_BF16)
 R2L_BP_KERNELS_IO(_f16, R2L_IO_F16)
+R2L_BP_KERNELS_IO(_nhwc, R2L_IO_F32 | R2L_IO_NHWC)
+R2L_BP_KERNELS_IO(_bf16_nhwc, R2L_IO_BF16 | R2L_IO_NHWC)
+R2L_BP_KERNELS_IO(_f16_nhwc, R2L_IO_F16 | R2L_IO_NHWC)
 R2L_KERNEL_NT_LDS(r2l_launch_bwd1_blur, R2LBwd1Args, R2L_BP_NT, R2L_BP_RED_FLOATS, 3, r2l_bwd1_blur_block)
 R2L_KERNEL_NT_LDS(r2l_launch_bwd1_blur_hp, R2LBwd1Args, R2L_BP_NT, R2L_BP_RED_FLOATS, R2L_HB_OCC, r2l_bwd1_blur_hp_block)
 // the reduced forms r2l_isp_step_bwd_select routes to (R2L_BPS_*: what each keeps).  Without the 38 stencil accumulator pairs
@@ -368,6 +381,12 @@ R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_bf16, false, R2L_IO_BF16)
 R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_u16_bf16, true, R2L_IO_BF16)
 R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_f16, false, R2L_IO_F16)
 R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_u16_f16, true, R2L_IO_F16)
+R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_nhwc, false, R2L_IO_F32 | R2L_IO_NHWC)
+R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_u16_nhwc, true, R2L_IO_F32 | R2L_IO_NHWC)
+R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_bf16_nhwc, false, R2L_IO_BF16 | R2L_IO_NHWC)
+R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_u16_bf16_nhwc, true, R2L_IO_BF16 | R2L_IO_NHWC)
+R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_f16_nhwc, false, R2L_IO_F16 | R2L_IO_NHWC)
+R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_u16_f16_nhwc, true, R2L_IO_F16 | R2L_IO_NHWC)
 #endif
 R2L_KERNEL_V(r2l_launch_bwd2, R2LBwd2Args, R2L_LDS3(GBwd2), R2L_OCC_BWD2, r2l_bwd2_block<GBwd2, false>)
 R2L_KERNEL_V(r2l_launch_fwd_u16, R2LFwdArgs, R2L_LDS3(GFwd), R2L_OCC_FWD, r2l_fwd_block<GFwd, false, false, true>)
@@ -743,6 +762,10 @@ static int r2l_check_raw(const R2LRaw& raw, int W, const char* who) {
 // streaming forward without output (r2l_isp_step_fwd sets it in train mode)
 #define R2L_F_SPLIT_STATS 2048
 #define R2L_F_INTERNAL (R2L_F_LUMA_VALID | R2L_F_SPLIT_STATS)
+// The implementations' `io` = element type (R2L_IO_*) | R2L_IO_NHWC for a channels-last tensor (r2l_common.h).  Every value but
+// R2L_IO_F32 takes the routes a 16-bit call takes; its row in their launch tables (r2l_io_check has seen the value):
+#define R2L_IO_SLOTS 5
+static int r2l_io_slot(int io) { return (io & R2L_IO_NHWC) ? 2 + R2L_IO_ELEM(io) : io - 1; }
 // where the row-streaming forward (r2l_param_stream.h) runs -- and with R2L_F_KEEP_LUMA leaves Y' for kernel B1
 static bool r2l_fwd_streams(bool additive, int W) {
   return R2L_PLANE_PASSES && !additive && (W & 3) == 0 && W <= 2048 && !r2l_env_int("R2L_FWD_TILED", 0);
@@ -751,11 +774,11 @@ static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float*
                             const float* bn_mean_istd, float* out, double* stats, void* workspace,
                             size_t workspace_bytes, int B, int H, int W, int flags, void* stream,
                             const R2LBnFinalizeArgs* fin = nullptr, const R2LEpi* ep = nullptr, int io = R2L_IO_F32) {
-  // io: the type `out` really holds (R2L_IO_*; r2l_isp_step_fwd_io has checked that the streaming kernels serve the call)
+  // io: what `out` really holds (R2L_IO_* | R2L_IO_NHWC; r2l_isp_step_fwd_layout has checked that the streaming kernels serve the call)
   if (int e = r2l_check_dims(B, H, W)) return e;
   if (int e = r2l_check_raw(raw, W, "r2l_isp_fwd")) return e;
   if (io != R2L_IO_F32 && (!r2l_fwd_streams(additive, W) || (ep && ep->on)))
-    return r2l_fail(-3, "r2l_isp_fwd: internal: a 16-bit output needs the row-streaming forward without an epilogue");
+    return r2l_fail(-3, "r2l_isp_fwd: internal: a 16-bit / channels-last output needs the row-streaming forward without an epilogue");
   if (!params || !workspace) return r2l_fail(-1, "r2l_isp_fwd: null pointer");
   if (additive && (H != 256 || W != 256))
     return r2l_fail(-1, "additive_layer is (1,3,256,256): needs 256x256 frames");
@@ -872,9 +895,14 @@ static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float*
       fa.nitems = (int)grid;
       static const launch_t atable[2][2] = {{r2l_launch_fwd_apply, r2l_launch_fwd_apply_u16},
                                             {r2l_launch_fwd_apply_epi, r2l_launch_fwd_apply_epi_u16}};
-      static const launch_t atable_io[2][2] = {{r2l_launch_fwd_apply_bf16, r2l_launch_fwd_apply_u16_bf16},
-                                               {r2l_launch_fwd_apply_f16, r2l_launch_fwd_apply_u16_f16}};
-      const launch_t apply = io != R2L_IO_F32 ? atable_io[io - 1][raw.u16 ? 1 : 0] : atable[epi ? 1 : 0][raw.u16 ? 1 : 0];
+      static const launch_t atable_io[R2L_IO_SLOTS][2] = {
+          {r2l_launch_fwd_apply_bf16, r2l_launch_fwd_apply_u16_bf16},
+          {r2l_launch_fwd_apply_f16, r2l_launch_fwd_apply_u16_f16},
+          {r2l_launch_fwd_apply_nhwc, r2l_launch_fwd_apply_u16_nhwc},
+          {r2l_launch_fwd_apply_bf16_nhwc, r2l_launch_fwd_apply_u16_bf16_nhwc},
+          {r2l_launch_fwd_apply_f16_nhwc, r2l_launch_fwd_apply_u16_f16_nhwc}};
+      const launch_t apply =
+          io != R2L_IO_F32 ? atable_io[r2l_io_slot(io)][raw.u16 ? 1 : 0] : atable[epi ? 1 : 0][raw.u16 ? 1 : 0];
       return apply(fa, (int)((grid + R2L_FA_NWV - 1) / R2L_FA_NWV), stream);
     }
     if (!out && stats) {  // the statistics pass: its own instantiation (no output code, fewer live scalars)
@@ -891,9 +919,10 @@ static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float*
     r2l_launch_fwd_stream_w8##sfx},                                                                                 \
    {r2l_launch_fwd_stream_w1_u16##sfx, r2l_launch_fwd_stream_w2_u16##sfx, r2l_launch_fwd_stream_w4_u16##sfx,        \
     r2l_launch_fwd_stream_w8_u16##sfx}}
-      static const launch_t table_io[2][2][4] = {R2L_FS_ROW_IO(_bf16), R2L_FS_ROW_IO(_f16)};
+      static const launch_t table_io[R2L_IO_SLOTS][2][4] = {R2L_FS_ROW_IO(_bf16), R2L_FS_ROW_IO(_f16), R2L_FS_ROW_IO(_nhwc),
+                                                            R2L_FS_ROW_IO(_bf16_nhwc), R2L_FS_ROW_IO(_f16_nhwc)};
 #undef R2L_FS_ROW_IO
-      return table_io[io - 1][raw.u16 ? 1 : 0][nw](fa, sgrid, stream);
+      return table_io[r2l_io_slot(io)][raw.u16 ? 1 : 0][nw](fa, sgrid, stream);
     }
     return table[epi ? 1 : 0][raw.u16 ? 1 : 0][nw](fa, sgrid, stream);
   }
@@ -1191,14 +1220,20 @@ static int r2l_bwd_launch(const R2LBwdCall& c, const R2LWorkspace& ws, const R2L
     typedef int (*launch_t)(const R2LBwd1Args&, int, void*);
     static const launch_t plane[2][2] = {{r2l_launch_bwd1_plane, r2l_launch_bwd1_plane_u16},
                                          {r2l_launch_bwd1_plane_epi, r2l_launch_bwd1_plane_epi_u16}};
-    static const launch_t plane_io[2][2] = {{r2l_launch_bwd1_plane_bf16, r2l_launch_bwd1_plane_u16_bf16},
-                                            {r2l_launch_bwd1_plane_f16, r2l_launch_bwd1_plane_u16_f16}};
+    static const launch_t plane_io[R2L_IO_SLOTS][2] = {{r2l_launch_bwd1_plane_bf16, r2l_launch_bwd1_plane_u16_bf16},
+                                                       {r2l_launch_bwd1_plane_f16, r2l_launch_bwd1_plane_u16_f16},
+                                                       {r2l_launch_bwd1_plane_nhwc, r2l_launch_bwd1_plane_u16_nhwc},
+                                                       {r2l_launch_bwd1_plane_bf16_nhwc, r2l_launch_bwd1_plane_u16_bf16_nhwc},
+                                                       {r2l_launch_bwd1_plane_f16_nhwc, r2l_launch_bwd1_plane_u16_f16_nhwc}};
+    typedef int (*launch_guv_t)(const R2LBwd1GuvArgs&, int, void*);
+    static const launch_guv_t guv_io[R2L_IO_SLOTS] = {r2l_launch_bwd1_plane_guv_bf16, r2l_launch_bwd1_plane_guv_f16,
+                                                      r2l_launch_bwd1_plane_guv_nhwc, r2l_launch_bwd1_plane_guv_bf16_nhwc,
+                                                      r2l_launch_bwd1_plane_guv_f16_nhwc};
     // (d/d raw: float32 frames, no epilogue -- r2l_raw_grad_preconditions)
     int e;
     if (c.io != R2L_IO_F32)
-      e = c.grad_raw ? (c.io == R2L_IO_BF16 ? r2l_launch_bwd1_plane_guv_bf16(R2LBwd1GuvArgs{a1, c.guv}, g1, stream)
-                                            : r2l_launch_bwd1_plane_guv_f16(R2LBwd1GuvArgs{a1, c.guv}, g1, stream))
-                     : plane_io[c.io - 1][u16](a1, g1, stream);
+      e = c.grad_raw ? guv_io[r2l_io_slot(c.io)](R2LBwd1GuvArgs{a1, c.guv}, g1, stream)
+                     : plane_io[r2l_io_slot(c.io)][u16](a1, g1, stream);
     else
       e = c.grad_raw ? r2l_launch_bwd1_plane_guv(R2LBwd1GuvArgs{a1, c.guv}, g1, stream)
                      : plane[c.ep.on ? 1 : 0][u16](a1, g1, stream);
@@ -1428,8 +1463,15 @@ static int r2l_bn_bwd_reduce_planes(const R2LRaw& raw, const float* additive, co
   a.totals = ws.moments;
   a.bn_bwd = bn_bwd;
   const int g = r2l_plane_grid(B, H, W, a.s.band_h, R2L_BNR_NWV, r2l_env_int("R2L_GRID_BNR", R2L_MAX_BLOCKS));
-  if (io == R2L_IO_BF16) return raw.u16 ? r2l_launch_bnr_planes_u16_bf16(a, g, stream) : r2l_launch_bnr_planes_bf16(a, g, stream);
-  if (io == R2L_IO_F16) return raw.u16 ? r2l_launch_bnr_planes_u16_f16(a, g, stream) : r2l_launch_bnr_planes_f16(a, g, stream);
+  if (io != R2L_IO_F32) {
+    typedef int (*launch_t)(const R2LBnrArgs&, int, void*);
+    static const launch_t bnr_io[R2L_IO_SLOTS][2] = {{r2l_launch_bnr_planes_bf16, r2l_launch_bnr_planes_u16_bf16},
+                                                     {r2l_launch_bnr_planes_f16, r2l_launch_bnr_planes_u16_f16},
+                                                     {r2l_launch_bnr_planes_nhwc, r2l_launch_bnr_planes_u16_nhwc},
+                                                     {r2l_launch_bnr_planes_bf16_nhwc, r2l_launch_bnr_planes_u16_bf16_nhwc},
+                                                     {r2l_launch_bnr_planes_f16_nhwc, r2l_launch_bnr_planes_u16_f16_nhwc}};
+    return bnr_io[r2l_io_slot(io)][raw.u16 ? 1 : 0](a, g, stream);
+  }
   return ep.on ? (raw.u16 ? r2l_launch_bnr_planes_epi_u16(a, g, stream) : r2l_launch_bnr_planes_epi(a, g, stream))
                : (raw.u16 ? r2l_launch_bnr_planes_u16(a, g, stream) : r2l_launch_bnr_planes(a, g, stream));
 #endif
@@ -1471,7 +1513,7 @@ static int r2l_isp_step_bwd_impl(const R2LStepBwd& q) {
   if (q.bn_mode == R2L_BN_TRAIN && !q.out && q.io == R2L_IO_F32)
     return r2l_fail(-1, "r2l_isp_step_bwd: train-mode BatchNorm needs the saved output");
   if (q.io != R2L_IO_F32 && q.grad_additive)
-    return r2l_fail(-3, "r2l_isp_step_bwd_io: a 16-bit cotangent is not served with an additive layer");
+    return r2l_fail(-3, "r2l_isp_step_bwd_io: a 16-bit / channels-last cotangent is not served with an additive layer");
   const R2LRaw rw = r2l_raw_any(q.raw, q.raw_u16, q.denom);
   // (before ANY launch: the recomputing BatchNorm sums below read the raw frames)
   if (int e = r2l_check_raw(rw, W, "r2l_isp_step_bwd")) return e;
@@ -1571,8 +1613,9 @@ int r2l_isp_step_bwd_select(const void* raw, int raw_u16, float denom, const flo
   return r2l_isp_step_bwd_impl(q);
 }
 
-// ---- 16-bit output / cotangent (include/r2l_isp.h: R2L_IO_*) ------------------------------------------------------------------
-// why a 16-bit call is not served, or null: the ONE predicate of r2l_isp_io_supported, r2l_isp_step_fwd_io and r2l_isp_step_bwd_io
+// ---- 16-bit and channels-last output / cotangent (include/r2l_isp.h: R2L_IO_*, R2L_LAYOUT_*) -----------------------------------
+// why a 16-bit or channels-last call is not served, or null: the ONE predicate of r2l_isp_io_supported, r2l_isp_layout_supported and
+// the r2l_isp_step_{fwd,bwd}_{io,layout} calls
 static const char* r2l_io_why(int raw_u16, bool has_additive, int B, int H, int W, int phase) {
   (void)raw_u16;  // (both frame types are served)
   if (!R2L_PLANE_PASSES) return "the serial emulation has no row-streaming forward and no plane passes";
@@ -1584,50 +1627,102 @@ static const char* r2l_io_why(int raw_u16, bool has_additive, int B, int H, int 
   if (!(phase & R2L_STEP_KEEP_LUMA)) return "needs R2L_STEP_KEEP_LUMA in `phase` of both calls";
   return nullptr;
 }
-static int r2l_io_check(const char* who, int io, const void* tensor, int raw_u16, bool has_additive, int B, int H, int W, int phase) {
-  if (io != R2L_IO_BF16 && io != R2L_IO_F16) return r2l_fail(-1, std::string(who) + ": io must be one of R2L_IO_*");
+// 0, or the error of a call whose `out` / `grad_out` is not planar float32.  layout = R2L_LAYOUT_NHWC is served where a 16-bit call
+// is, float32 included (r2l_isp_layout_supported)
+static int r2l_io_check(const char* who, int io, int layout, const void* tensor, int raw_u16, bool has_additive, int B, int H,
+                        int W, int phase) {
+  if (io != R2L_IO_F32 && io != R2L_IO_BF16 && io != R2L_IO_F16) return r2l_fail(-1, std::string(who) + ": io must be one of R2L_IO_*");
+  if (layout != R2L_LAYOUT_NCHW && layout != R2L_LAYOUT_NHWC)
+    return r2l_fail(-1, std::string(who) + ": layout must be one of R2L_LAYOUT_*");
+  if (io == R2L_IO_F32 && layout == R2L_LAYOUT_NCHW) return 0;
+  const bool nhwc = layout == R2L_LAYOUT_NHWC;
   if (const char* why = r2l_io_why(raw_u16, has_additive, B, H, W, phase))
-    return r2l_fail(-3, std::string(who) + ": a 16-bit output / cotangent is not served here: " + why);
-  if ((uintptr_t)tensor % 8) return r2l_fail(-1, std::string(who) + ": the 16-bit tensor must be 8-byte aligned");
+    return r2l_fail(-3, std::string(who) + (nhwc ? ": a channels-last output / cotangent is not served here: "
+                                                 : ": a 16-bit output / cotangent is not served here: ") + why);
+  if (nhwc && io == R2L_IO_F32) {
+    if ((uintptr_t)tensor % 16) return r2l_fail(-1, std::string(who) + ": the channels-last float32 tensor must be 16-byte aligned");
+  } else if ((uintptr_t)tensor % 8) {
+    return r2l_fail(-1, std::string(who) + ": the 16-bit tensor must be 8-byte aligned");
+  }
   return 0;
 }
-int r2l_isp_io_supported(int io, int raw_u16, int has_additive, int B, int H, int W, int phase) {
-  if (io == R2L_IO_F32) return 1;
-  if (io != R2L_IO_BF16 && io != R2L_IO_F16) return 0;
+int r2l_isp_layout_supported(int io, int layout, int raw_u16, int has_additive, int B, int H, int W, int phase) {
+  if (io != R2L_IO_F32 && io != R2L_IO_BF16 && io != R2L_IO_F16) return 0;
+  if (layout != R2L_LAYOUT_NCHW && layout != R2L_LAYOUT_NHWC) return 0;
+  if (io == R2L_IO_F32 && layout == R2L_LAYOUT_NCHW) return 1;
   return r2l_io_why(raw_u16, has_additive != 0, B, H, W, phase) ? 0 : 1;
+}
+int r2l_isp_io_supported(int io, int raw_u16, int has_additive, int B, int H, int W, int phase) {
+  return r2l_isp_layout_supported(io, R2L_LAYOUT_NCHW, raw_u16, has_additive, B, H, W, phase);
+}
+// both public forwards and both public backwards share one implementation; `who`: the entry point r2l_last_error() names
+static int r2l_step_fwd_layout_impl(const char* who, const void* raw, int raw_u16, float denom, const float* const* params_host,
+                            const float* additive, int bn_mode, float* running_mean, float* running_var,
+                            long long* num_batches_tracked, double eps, double momentum, void* out, int io, int layout,
+                            void* workspace, size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                            const double* gathered_stats, void* stream) {
+  if (int e = r2l_io_check(who, io, layout, out, raw_u16, additive != nullptr, B, H, W, phase)) return e;
+  return r2l_isp_step_fwd_impl(raw, raw_u16, denom, params_host, additive, bn_mode, running_mean, running_var,
+                               num_batches_tracked, eps, momentum, (float*)out, io | (layout == R2L_LAYOUT_NHWC ? R2L_IO_NHWC : 0),
+                               workspace, workspace_bytes, B, H, W, nranks, phase, gathered_stats, stream);
+}
+int r2l_isp_step_fwd_layout(const void* raw, int raw_u16, float denom, const float* const* params_host,
+                            const float* additive, int bn_mode, float* running_mean, float* running_var,
+                            long long* num_batches_tracked, double eps, double momentum, void* out, int io, int layout,
+                            void* workspace, size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                            const double* gathered_stats, void* stream) {
+  return r2l_step_fwd_layout_impl("r2l_isp_step_fwd_layout", raw, raw_u16, denom, params_host, additive, bn_mode, running_mean,
+                                  running_var, num_batches_tracked, eps, momentum, out, io, layout, workspace, workspace_bytes, B,
+                                  H, W, nranks, phase, gathered_stats, stream);
 }
 int r2l_isp_step_fwd_io(const void* raw, int raw_u16, float denom, const float* const* params_host,
                         const float* additive, int bn_mode, float* running_mean, float* running_var,
                         long long* num_batches_tracked, double eps, double momentum, void* out, int io, void* workspace,
                         size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
                         const double* gathered_stats, void* stream) {
-  if (io != R2L_IO_F32)
-    if (int e = r2l_io_check("r2l_isp_step_fwd_io", io, out, raw_u16, additive != nullptr, B, H, W, phase)) return e;
-  return r2l_isp_step_fwd_impl(raw, raw_u16, denom, params_host, additive, bn_mode, running_mean, running_var,
-                               num_batches_tracked, eps, momentum, (float*)out, io, workspace, workspace_bytes, B, H, W, nranks,
-                               phase, gathered_stats, stream);
+  return r2l_step_fwd_layout_impl("r2l_isp_step_fwd_io", raw, raw_u16, denom, params_host, additive, bn_mode, running_mean,
+                                  running_var, num_batches_tracked, eps, momentum, out, io, R2L_LAYOUT_NCHW, workspace,
+                                  workspace_bytes, B, H, W, nranks, phase, gathered_stats, stream);
+}
+static int r2l_step_bwd_layout_impl(const char* who, const void* raw, int raw_u16, float denom, const float* additive, const void* grad_out, int io,
+                            int layout, const void* out, float* grad_params, float* grad_additive, int bn_mode,
+                            void* workspace, size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                            const double* gathered_sums, void* stream, float* grad_raw, void* raw_grad_scratch,
+                            size_t raw_grad_scratch_bytes, unsigned grad_mask) {
+  if (io == R2L_IO_F32 && layout == R2L_LAYOUT_NCHW)
+    return r2l_isp_step_bwd_select(raw, raw_u16, denom, additive, (const float*)grad_out, (const float*)out, grad_params,
+                                   grad_additive, bn_mode, workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums,
+                                   stream, grad_raw, raw_grad_scratch, raw_grad_scratch_bytes, grad_mask);
+  if (int e = r2l_io_check(who, io, layout, grad_out, raw_u16, additive != nullptr, B, H, W, phase)) return e;
+  if (grad_mask & ~(unsigned)(R2L_GRAD_ALL_PARAMS | R2L_GRAD_RAW))
+    return r2l_fail(-1, std::string(who) + ": unknown bits in grad_mask");
+  if ((grad_raw != nullptr) != ((grad_mask & R2L_GRAD_RAW) != 0))
+    return r2l_fail(-1, std::string(who) + ": grad_raw goes with R2L_GRAD_RAW in grad_mask");
+  if (grad_mask && !grad_params) return r2l_fail(-1, std::string(who) + ": a gradient is asked for but grad_params is null");
+  const R2LStepBwd q{raw, raw_u16, denom, additive, (const float*)grad_out, (const float*)out, grad_params, grad_additive,
+                     bn_mode, workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw,
+                     (float*)raw_grad_scratch, grad_mask, io | (layout == R2L_LAYOUT_NHWC ? R2L_IO_NHWC : 0)};
+  if (grad_raw)
+    if (int e = r2l_raw_grad_preconditions(q, raw_grad_scratch_bytes)) return e;
+  return r2l_isp_step_bwd_impl(q);
+}
+int r2l_isp_step_bwd_layout(const void* raw, int raw_u16, float denom, const float* additive, const void* grad_out, int io,
+                            int layout, const void* out, float* grad_params, float* grad_additive, int bn_mode,
+                            void* workspace, size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
+                            const double* gathered_sums, void* stream, float* grad_raw, void* raw_grad_scratch,
+                            size_t raw_grad_scratch_bytes, unsigned grad_mask) {
+  return r2l_step_bwd_layout_impl("r2l_isp_step_bwd_layout", raw, raw_u16, denom, additive, grad_out, io, layout, out, grad_params,
+                                  grad_additive, bn_mode, workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream,
+                                  grad_raw, raw_grad_scratch, raw_grad_scratch_bytes, grad_mask);
 }
 int r2l_isp_step_bwd_io(const void* raw, int raw_u16, float denom, const float* additive, const void* grad_out, int io,
                         const void* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
                         size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
                         const double* gathered_sums, void* stream, float* grad_raw, void* raw_grad_scratch,
                         size_t raw_grad_scratch_bytes, unsigned grad_mask) {
-  if (io == R2L_IO_F32)
-    return r2l_isp_step_bwd_select(raw, raw_u16, denom, additive, (const float*)grad_out, (const float*)out, grad_params,
-                                   grad_additive, bn_mode, workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums,
-                                   stream, grad_raw, raw_grad_scratch, raw_grad_scratch_bytes, grad_mask);
-  if (int e = r2l_io_check("r2l_isp_step_bwd_io", io, grad_out, raw_u16, additive != nullptr, B, H, W, phase)) return e;
-  if (grad_mask & ~(unsigned)(R2L_GRAD_ALL_PARAMS | R2L_GRAD_RAW))
-    return r2l_fail(-1, "r2l_isp_step_bwd_io: unknown bits in grad_mask");
-  if ((grad_raw != nullptr) != ((grad_mask & R2L_GRAD_RAW) != 0))
-    return r2l_fail(-1, "r2l_isp_step_bwd_io: grad_raw goes with R2L_GRAD_RAW in grad_mask");
-  if (grad_mask && !grad_params) return r2l_fail(-1, "r2l_isp_step_bwd_io: a gradient is asked for but grad_params is null");
-  const R2LStepBwd q{raw, raw_u16, denom, additive, (const float*)grad_out, (const float*)out, grad_params, grad_additive,
-                     bn_mode, workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw,
-                     (float*)raw_grad_scratch, grad_mask, io};
-  if (grad_raw)
-    if (int e = r2l_raw_grad_preconditions(q, raw_grad_scratch_bytes)) return e;
-  return r2l_isp_step_bwd_impl(q);
+  return r2l_step_bwd_layout_impl("r2l_isp_step_bwd_io", raw, raw_u16, denom, additive, grad_out, io, R2L_LAYOUT_NCHW, out,
+                                  grad_params, grad_additive, bn_mode, workspace, workspace_bytes, B, H, W, nranks, phase,
+                                  gathered_sums, stream, grad_raw, raw_grad_scratch, raw_grad_scratch_bytes, grad_mask);
 }
 
 static int r2l_raw2rgb_fwd_impl(const R2LRaw& raw, const float* black_level, float* out, int B, int H, int W,

@@ -511,14 +511,21 @@ R2L_HD r2l_h4 r2l_load_h4_nt(const unsigned short* p) {
   return h;
 }
 #endif
+// ---- channels-last boundary tensors (R2L_LAYOUT_NHWC, include/r2l_isp.h) -------------------------------------------------------
+// The kernels' IO template parameter carries the layout as well: element type (R2L_IO_*) in the low two bits, R2L_IO_NHWC set
+// where the tensor is interleaved -- element 3 (y W + x) + k of an image instead of k H W + y W + x.  A lane's 4 pixels x 3
+// channels are then 12 consecutive elements: 48 bytes at 16-byte alignment in float32, 24 at 8 in 16 bits.  The planar values
+// 0, 1, 2 mean what they meant; only r2l_fs_colour (the store) and r2l_bp_fetch_g (the load) look at the bit.
+#define R2L_IO_NHWC 4
+#define R2L_IO_ELEM(IO) ((IO) & 3)
 // element i of a boundary tensor of type IO behind a float pointer (the argument blocks keep their float32 types)
 template <int IO>
 R2L_HD float* r2l_io_at(float* p, size_t i) {
-  return IO == R2L_IO_F32 ? p + i : (float*)((unsigned short*)p + i);
+  return R2L_IO_ELEM(IO) == R2L_IO_F32 ? p + i : (float*)((unsigned short*)p + i);
 }
 template <int IO>
 R2L_HD const float* r2l_io_at(const float* p, size_t i) {
-  return IO == R2L_IO_F32 ? p + i : (const float*)((const unsigned short*)p + i);
+  return R2L_IO_ELEM(IO) == R2L_IO_F32 ? p + i : (const float*)((const unsigned short*)p + i);
 }
 
 // ---- packed pairs ---------------------------------------------------------------------------------

@@ -59,16 +59,61 @@ template <>
 struct R2LBpStageT<R2L_IO_BF16> : R2LBpStageH<R2L_IO_BF16> {};
 template <>
 struct R2LBpStageT<R2L_IO_F16> : R2LBpStageH<R2L_IO_F16> {};
+// a channels-last cotangent (R2L_IO_NHWC) stays as loaded -- the lane's 12 consecutive elements, 12 registers in float32 and 6
+// packed in 16 bits -- and ch(k) picks elements k, 3 + k, 6 + k, 9 + k (and widens them) where the row is used: register renaming
+// under the full unrolling
+R2L_HD float r2l_f4_at(const r2l_f4& v, int j) { return j == 0 ? v.x : (j == 1 ? v.y : (j == 2 ? v.z : v.w)); }
+template <int IO>
+struct R2LBpStageL {
+  r2l_f4 m[3];
+  R2L_MEMBER float el(int i) const { return r2l_f4_at(m[i >> 2], i & 3); }
+  R2L_MEMBER r2l_f4 ch(int k) const {
+    r2l_f4 v;
+    v.x = el(k);
+    v.y = el(3 + k);
+    v.z = el(6 + k);
+    v.w = el(9 + k);
+    return v;
+  }
+};
+template <int IO>
+struct R2LBpStageLH {
+  r2l_h4 m[3];
+  R2L_MEMBER float el(int i) const {
+    const unsigned w = (i & 2) ? m[i >> 2].hi : m[i >> 2].lo;
+    return r2l_io_widen<R2L_IO_ELEM(IO)>((i & 1) ? w >> 16 : w & 0xffffu);
+  }
+  R2L_MEMBER r2l_f4 ch(int k) const {
+    r2l_f4 v;
+    v.x = el(k);
+    v.y = el(3 + k);
+    v.z = el(6 + k);
+    v.w = el(9 + k);
+    return v;
+  }
+};
+template <>
+struct R2LBpStageT<R2L_IO_F32 | R2L_IO_NHWC> : R2LBpStageL<R2L_IO_F32 | R2L_IO_NHWC> {};
+template <>
+struct R2LBpStageT<R2L_IO_BF16 | R2L_IO_NHWC> : R2LBpStageLH<R2L_IO_BF16 | R2L_IO_NHWC> {};
+template <>
+struct R2LBpStageT<R2L_IO_F16 | R2L_IO_NHWC> : R2LBpStageLH<R2L_IO_F16 | R2L_IO_NHWC> {};
 typedef R2LBpStageT<R2L_IO_F32> R2LBpStage;
 // the row a step consumes, as float32 (a float32 row: the row itself)
 R2L_HD const R2LBpStage& r2l_bp_widen(const R2LBpStage& s) { return s; }
-template <int IO>
-R2L_HD R2LBpStage r2l_bp_widen(const R2LBpStageH<IO>& s) {
+template <class S>
+R2L_HD R2LBpStage r2l_bp_planar(const S& s) {
   R2LBpStage w;
   R2L_PRAGMA_UNROLL
   for (int k = 0; k < 3; ++k) w.g[k] = s.ch(k);
   return w;
 }
+template <int IO>
+R2L_HD R2LBpStage r2l_bp_widen(const R2LBpStageH<IO>& s) { return r2l_bp_planar(s); }
+template <int IO>
+R2L_HD R2LBpStage r2l_bp_widen(const R2LBpStageL<IO>& s) { return r2l_bp_planar(s); }
+template <int IO>
+R2L_HD R2LBpStage r2l_bp_widen(const R2LBpStageLH<IO>& s) { return r2l_bp_planar(s); }
 // The LAST reader of a kept plane may take it around the caches (nontemporal loads), so that what it leaves in the 256 MiB memory-side
 // cache is what the next passes want (profiles/r05_nt_stores.txt, 64x512x512, alternating processes):
 //   HP in the sums pass (the step's last kernel): the NEXT step's apply pass 63.5 -> 60.1 us, blur pass 43.3 -> 41.5, statistics -0.9
@@ -78,7 +123,18 @@ template <bool EPI, int IO = R2L_IO_F32>
 R2L_HD void r2l_bp_fetch_g(const float* gimg, unsigned plane, int y, int H, int W, int x0, const R2LEpi& ep,
                            R2LBpStageT<IO>& s) {
   const int yc = y < 0 ? 0 : (y >= H ? H - 1 : y);
-  if constexpr (IO != R2L_IO_F32) {  // 8 bytes per lane and channel, read once: nontemporal as below
+  if constexpr ((IO & R2L_IO_NHWC) != 0) {  // the lane's 12 consecutive elements: 3 x 16 resp. 3 x 8 bytes, nontemporal as below
+    static_assert(!EPI, "a channels-last cotangent comes without the output epilogue");
+    const size_t e0 = 3 * ((size_t)yc * W + x0);
+    if constexpr (R2L_IO_ELEM(IO) == R2L_IO_F32) {
+      R2L_PRAGMA_UNROLL
+      for (int j = 0; j < 3; ++j) s.m[j] = r2l_load_f4_nt(gimg + e0 + 4 * j);
+    } else {
+      R2L_PRAGMA_UNROLL
+      for (int j = 0; j < 3; ++j) s.m[j] = r2l_load_h4_nt((const unsigned short*)gimg + e0 + 4 * j);
+    }
+    return;
+  } else if constexpr (IO != R2L_IO_F32) {  // 8 bytes per lane and channel, read once: nontemporal as below
     static_assert(!EPI, "a 16-bit cotangent comes in the ISP's own layout");
     const unsigned short* p = (const unsigned short*)gimg + (size_t)yc * W + x0;
     R2L_PRAGMA_UNROLL

@@ -210,21 +210,23 @@ R2L_HD void r2l_fs_stencil_plain(const float* r0, const float* r1, const float* 
   }
 }
 
-// the colour code of one output row (:203-217): Y'', U, V of the lane's 4 pixels -> RGB, clip, gamma, [statistics about the
-// lane's pivot], [BatchNorm], store (EPI: at the augmented position, R2LEpi)
-// STATS: 0 none; 1 the streaming kernel's form (under `a.stat_partial && store_ok`); 2 branch-free, weighted with smask
-// (1 for the pixels that count, 0 for the others), the pivot taken in the band's first row (`first`); 3 the sums of BatchNorm's
-// backward over grad_out (gk: this row's grad_out as pairs)
-// IO: the type `ob` holds (R2L_IO_*): a 16-bit output is narrowed here, at the store, and nowhere else
-template <bool EPI, int STATS, int IO = R2L_IO_F32>
-R2L_HD void r2l_fs_colour(const R2LFwdStreamArgs& a, R2LFoldedRef F, r2l_p2* acc, float* piv, const r2l_p2 ypp[2],
-                          const r2l_p2 u[2], const r2l_p2 v[2], int y, int y0, int x0, float* ob, unsigned plane,
-                          bool store_ok, const float mean[3], const float istd[3], float smask = 0.f,
-                          bool first = false, const r2l_p2 (*gk)[2] = nullptr) {
+// The channels-last form of r2l_fs_colour's store (IO with R2L_IO_NHWC): the image behind `ob` is interleaved, the lane's 4 pixels x 3
+// channels are elements 3 off0 .. 3 off0 + 11 -- 48 bytes at 16-byte alignment in float32, 24 at 8 in 16 bits.  The values are
+// computed channel by channel exactly as below (each is a function of its own channel and pixel; every channel's statistics meet
+// pair 0 before pair 1), kept -- 12 registers in float32, 6 packed in 16 bits -- and leave as three full-width stores.
+// MIRROR: the colour matrix, clip, gamma, pivot statistics and normalisation below are a second copy of r2l_fs_colour's (merged
+// into one loop nest they changed the planar code objects); the two must stay bit-identical -- change both or neither.
+template <int STATS, int IO>
+R2L_HD void r2l_fs_colour_nhwc(const R2LFwdStreamArgs& a, R2LFoldedRef F, r2l_p2* acc, float* piv, const r2l_p2 ypp[2],
+                               const r2l_p2 u[2], const r2l_p2 v[2], int y, int x0, float* ob, bool store_ok, const float mean[3],
+                               const float istd[3], float smask, bool first) {
+  static_assert(STATS == 0 || STATS == 2, "the channels-last store goes with the branch-free statistics or none");
+  constexpr int EL = R2L_IO_ELEM(IO);
   const unsigned off0 = (unsigned)y * (unsigned)a.W + (unsigned)x0;
+  r2l_p2 xs[3][2];
   R2L_PRAGMA_UNROLL
   for (int k = 0; k < 3; ++k) {
-    r2l_p2 x[2];
+    r2l_p2* x = xs[k];
     R2L_PRAGMA_UNROLL
     for (int p = 0; p < 2; ++p) {
       r2l_p2 rgb = r2l_pmul(r2l_splat2(F.M2[k * 3]), ypp[p]);
@@ -234,21 +236,6 @@ R2L_HD void r2l_fs_colour(const R2LFwdStreamArgs& a, R2LFoldedRef F, r2l_p2* acc
                                 r2l_log2(fminf(fmaxf(rgb[1], 1e-5f), 1.0f)));
       const r2l_p2 e = r2l_pmul(lg, r2l_splat2(F.inv_gamma));                    // :209
       x[p] = r2l_mk2(r2l_exp2(e[0]), r2l_exp2(e[1]));
-      if (STATS == 1 && a.stat_partial && store_ok) {
-        if (p == 0) piv[k] = (y == y0) ? x[0][0] : piv[k];
-        const r2l_p2 d = r2l_padd(x[p], r2l_splat2(-piv[k]));
-        acc[k] = r2l_padd(acc[k], d);
-        acc[3 + k] = r2l_pfma(d, d, acc[3 + k]);
-      }
-      if (STATS == 3) {
-        // BatchNorm's backward sums (:217 backward): sum g and sum g * xhat, xhat = the value the apply pass stored -- the same
-        // expression on the same numbers -- RECOMPUTED from the raw frame and Y' instead of read back (r2l_bnr_planes_block);
-        // smask: the wave-uniform 1 / 0 of the row (lanes beyond the frame are taken out once, after the band)
-        const r2l_p2 xh = r2l_pmul(r2l_padd(x[p], r2l_splat2(-mean[k])), r2l_splat2(istd[k]));
-        const r2l_p2 t = r2l_pmul(gk[k][p], r2l_splat2(smask));
-        acc[k] = r2l_padd(acc[k], t);
-        acc[3 + k] = r2l_pfma(t, xh, acc[3 + k]);
-      }
       if (STATS == 2) {
         if (p == 0) piv[k] = first ? x[0][0] : piv[k];
         const r2l_p2 d = r2l_padd(x[p], r2l_splat2(-piv[k]));
@@ -261,36 +248,112 @@ R2L_HD void r2l_fs_colour(const R2LFwdStreamArgs& a, R2LFoldedRef F, r2l_p2* acc
       R2L_PRAGMA_UNROLL
       for (int p = 0; p < 2; ++p)
         x[p] = r2l_pmul(r2l_padd(x[p], r2l_splat2(-mean[k])), r2l_splat2(istd[k]));  // :217
-      r2l_f4 s4;
-      s4.x = x[0][0];
-      s4.y = x[0][1];
-      s4.z = x[1][0];
-      s4.w = x[1][1];
-      if constexpr (IO != R2L_IO_F32) {
-        static_assert(!EPI, "the output epilogue stores float32");
-        r2l_store_h4_nt((unsigned short*)ob + (unsigned)k * plane + off0, r2l_io_narrow4<IO>(s4));  // (around the caches, as below)
-      } else if (!EPI) {
-        // the output goes AROUND the caches (nontemporal): 12 B/px that this pass never reads again would otherwise push the raw
-        // frames and Y' -- which the neighbouring bands and the backward re-read -- out of the memory-side cache: apply pass
-        // 72.8 -> 64.9 us at 64x512x512, bn_reduce (which reads the output later) +0.5 (profiles/r05_nt_stores.txt;
-        // measured).  The kept planes Y', dL/dY'', HP stay cached: their readers follow at once.
-        r2l_store_f4_nt(ob + (unsigned)k * plane + off0, s4);
-      } else {  // the augmented position of this lane's 4 pixels (R2LEpi)
-        float* o = ob + (unsigned)k * plane + (a.ep.s0 + a.ep.sr * y + a.ep.sc * x0);
-        if (a.ep.sc == 1) {
-          r2l_store_f4_nt(o, s4);
-        } else if (a.ep.sc == -1) {
-          r2l_f4 r4;
-          r4.x = s4.w;
-          r4.y = s4.z;
-          r4.z = s4.y;
-          r4.w = s4.x;
-          r2l_store_f4_nt(o - 3, r4);
-        } else {
-          o[0] = s4.x;
-          o[a.ep.sc] = s4.y;
-          o[2 * a.ep.sc] = s4.z;
-          o[3 * a.ep.sc] = s4.w;
+    }
+  }
+  if (ob && store_ok) {
+    // element 3 j + k of the lane's 12 = channel k of pixel j = xs[k][j >> 1][j & 1]; around the caches, as the planar form
+    r2l_f4 s[3];
+    s[0].x = xs[0][0][0], s[0].y = xs[1][0][0], s[0].z = xs[2][0][0], s[0].w = xs[0][0][1];  // R0 G0 B0 R1
+    s[1].x = xs[1][0][1], s[1].y = xs[2][0][1], s[1].z = xs[0][1][0], s[1].w = xs[1][1][0];  // G1 B1 R2 G2
+    s[2].x = xs[2][1][0], s[2].y = xs[0][1][1], s[2].z = xs[1][1][1], s[2].w = xs[2][1][1];  // B2 R3 G3 B3
+    R2L_PRAGMA_UNROLL
+    for (int j = 0; j < 3; ++j) {
+      if constexpr (EL == R2L_IO_F32)
+        r2l_store_f4_nt(ob + 3u * off0 + 4 * j, s[j]);
+      else
+        r2l_store_h4_nt((unsigned short*)ob + 3u * off0 + 4 * j, r2l_io_narrow4<EL>(s[j]));
+    }
+  }
+}
+
+// the colour code of one output row (:203-217): Y'', U, V of the lane's 4 pixels -> RGB, clip, gamma, [statistics about the
+// lane's pivot], [BatchNorm], store (EPI: at the augmented position, R2LEpi)
+// STATS: 0 none; 1 the streaming kernel's form (under `a.stat_partial && store_ok`); 2 branch-free, weighted with smask
+// (1 for the pixels that count, 0 for the others), the pivot taken in the band's first row (`first`); 3 the sums of BatchNorm's
+// backward over grad_out (gk: this row's grad_out as pairs)
+// IO: the type `ob` holds (R2L_IO_*): a 16-bit output is narrowed here, at the store, and nowhere else; with R2L_IO_NHWC the
+// store is r2l_fs_colour_nhwc's
+template <bool EPI, int STATS, int IO = R2L_IO_F32>
+R2L_HD void r2l_fs_colour(const R2LFwdStreamArgs& a, R2LFoldedRef F, r2l_p2* acc, float* piv, const r2l_p2 ypp[2],
+                          const r2l_p2 u[2], const r2l_p2 v[2], int y, int y0, int x0, float* ob, unsigned plane,
+                          bool store_ok, const float mean[3], const float istd[3], float smask = 0.f,
+                          bool first = false, const r2l_p2 (*gk)[2] = nullptr) {
+  // MIRROR: r2l_fs_colour_nhwc holds a second copy of the arithmetic below -- change both or neither
+  if constexpr ((IO & R2L_IO_NHWC) != 0) {
+    static_assert(!EPI, "the output epilogue stores planar float32");
+    r2l_fs_colour_nhwc<STATS, IO>(a, F, acc, piv, ypp, u, v, y, x0, ob, store_ok, mean, istd, smask, first);
+  } else {
+    const unsigned off0 = (unsigned)y * (unsigned)a.W + (unsigned)x0;
+    R2L_PRAGMA_UNROLL
+    for (int k = 0; k < 3; ++k) {
+      r2l_p2 x[2];
+      R2L_PRAGMA_UNROLL
+      for (int p = 0; p < 2; ++p) {
+        r2l_p2 rgb = r2l_pmul(r2l_splat2(F.M2[k * 3]), ypp[p]);
+        rgb = r2l_pfma(r2l_splat2(F.M2[k * 3 + 1]), u[p], rgb);
+        rgb = r2l_pfma(r2l_splat2(F.M2[k * 3 + 2]), v[p], rgb);
+        const r2l_p2 lg = r2l_mk2(r2l_log2(fminf(fmaxf(rgb[0], 1e-5f), 1.0f)),     // :206
+                                  r2l_log2(fminf(fmaxf(rgb[1], 1e-5f), 1.0f)));
+        const r2l_p2 e = r2l_pmul(lg, r2l_splat2(F.inv_gamma));                    // :209
+        x[p] = r2l_mk2(r2l_exp2(e[0]), r2l_exp2(e[1]));
+        if (STATS == 1 && a.stat_partial && store_ok) {
+          if (p == 0) piv[k] = (y == y0) ? x[0][0] : piv[k];
+          const r2l_p2 d = r2l_padd(x[p], r2l_splat2(-piv[k]));
+          acc[k] = r2l_padd(acc[k], d);
+          acc[3 + k] = r2l_pfma(d, d, acc[3 + k]);
+        }
+        if (STATS == 3) {
+          // BatchNorm's backward sums (:217 backward): sum g and sum g * xhat, xhat = the value the apply pass stored -- the same
+          // expression on the same numbers -- RECOMPUTED from the raw frame and Y' instead of read back (r2l_bnr_planes_block);
+          // smask: the wave-uniform 1 / 0 of the row (lanes beyond the frame are taken out once, after the band)
+          const r2l_p2 xh = r2l_pmul(r2l_padd(x[p], r2l_splat2(-mean[k])), r2l_splat2(istd[k]));
+          const r2l_p2 t = r2l_pmul(gk[k][p], r2l_splat2(smask));
+          acc[k] = r2l_padd(acc[k], t);
+          acc[3 + k] = r2l_pfma(t, xh, acc[3 + k]);
+        }
+        if (STATS == 2) {
+          if (p == 0) piv[k] = first ? x[0][0] : piv[k];
+          const r2l_p2 d = r2l_padd(x[p], r2l_splat2(-piv[k]));
+          const r2l_p2 t = r2l_pmul(d, r2l_splat2(smask));
+          acc[k] = r2l_padd(acc[k], t);
+          acc[3 + k] = r2l_pfma(t, d, acc[3 + k]);
+        }
+      }
+      if (ob && store_ok) {
+        R2L_PRAGMA_UNROLL
+        for (int p = 0; p < 2; ++p)
+          x[p] = r2l_pmul(r2l_padd(x[p], r2l_splat2(-mean[k])), r2l_splat2(istd[k]));  // :217
+        r2l_f4 s4;
+        s4.x = x[0][0];
+        s4.y = x[0][1];
+        s4.z = x[1][0];
+        s4.w = x[1][1];
+        if constexpr (IO != R2L_IO_F32) {
+          static_assert(!EPI, "the output epilogue stores float32");
+          r2l_store_h4_nt((unsigned short*)ob + (unsigned)k * plane + off0, r2l_io_narrow4<IO>(s4));  // (around the caches, as below)
+        } else if (!EPI) {
+          // the output goes AROUND the caches (nontemporal): 12 B/px that this pass never reads again would otherwise push the raw
+          // frames and Y' -- which the neighbouring bands and the backward re-read -- out of the memory-side cache: apply pass
+          // 72.8 -> 64.9 us at 64x512x512, bn_reduce (which reads the output later) +0.5 (profiles/r05_nt_stores.txt;
+          // measured).  The kept planes Y', dL/dY'', HP stay cached: their readers follow at once.
+          r2l_store_f4_nt(ob + (unsigned)k * plane + off0, s4);
+        } else {  // the augmented position of this lane's 4 pixels (R2LEpi)
+          float* o = ob + (unsigned)k * plane + (a.ep.s0 + a.ep.sr * y + a.ep.sc * x0);
+          if (a.ep.sc == 1) {
+            r2l_store_f4_nt(o, s4);
+          } else if (a.ep.sc == -1) {
+            r2l_f4 r4;
+            r4.x = s4.w;
+            r4.y = s4.z;
+            r4.z = s4.y;
+            r4.w = s4.x;
+            r2l_store_f4_nt(o - 3, r4);
+          } else {
+            o[0] = s4.x;
+            o[a.ep.sc] = s4.y;
+            o[2 * a.ep.sc] = s4.z;
+            o[3 * a.ep.sc] = s4.w;
+          }
         }
       }
     }

@@ -354,6 +354,38 @@ def io_supported(raw, module, dtype=None, keep=None):
                                          _STEP_KEEP_LUMA if keep else 0))
 
 
+# the memory layouts of that output / cotangent (include/r2l_isp.h: R2L_LAYOUT_*)
+LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
+LAYOUT_CODES = {None: LAYOUT_NCHW, torch.contiguous_format: LAYOUT_NCHW, torch.channels_last: LAYOUT_NHWC}
+
+
+def layout_supported(raw, module, memory_format=None, dtype=None, keep=None):
+    """do the fused kernels write this module's output directly in `memory_format` (default: module.output_memory_format) and
+    `dtype` (default: module.output_dtype) for these frames (r2l_isp_layout_supported, the predicate r2l_isp_step_fwd_layout /
+    _bwd_layout use)?  None / torch.contiguous_format: io_supported's answer.  torch.channels_last, in float32 or 16 bits: the
+    conditions of a 16-bit call (no additive layer, W % 4 == 0, W <= 2048, a step whose backward will run) -- elsewhere
+    ParametrizedProcessing runs the planar kernels and torch converts."""
+    memory_format = getattr(module, 'output_memory_format', None) if memory_format is None else memory_format
+    if memory_format not in LAYOUT_CODES:
+        raise _lib.R2LError(f'output_memory_format must be None, torch.contiguous_format or torch.channels_last, '
+                            f'got {memory_format!r}')
+    if LAYOUT_CODES[memory_format] == LAYOUT_NCHW:
+        return io_supported(raw, module, dtype, keep)
+    dtype = getattr(module, 'output_dtype', None) if dtype is None else dtype
+    if dtype not in IO_CODES:
+        raise _lib.R2LError(f'output_dtype must be None, torch.float32, torch.bfloat16 or torch.float16, got {dtype!r}')
+    if raw.ndim != 3 or not (raw.dtype == torch.float32 or raw.dtype in U16_DTYPES):
+        return False
+    if keep is None:
+        keep = torch.is_grad_enabled() and (raw.requires_grad or any(p.requires_grad for p in (
+            module.black_level, module.white_balance, module.colour_correction, module.gamma_correct, module.debayer.weight,
+            module.sharpening_filter.weight, module.gaussian_blur.weight)))
+    lib, _ = _lib.library_for(raw)
+    B, H, W = raw.shape
+    return bool(lib.r2l_isp_layout_supported(IO_CODES[dtype], LAYOUT_NHWC, int(raw.dtype in U16_DTYPES),
+                                             int(module.additive_layer is not None), B, H, W, _STEP_KEEP_LUMA if keep else 0))
+
+
 def _raw_grad_why(f32, W, has_additive, epi=False):
     """why r2l_isp_step_bwd_raw cannot produce d/d raw for such a call, or None if it can"""
     if epi:
@@ -409,11 +441,14 @@ class _IspFused(torch.autograd.Function):
     needs_input_grad to the library (r2l_isp_step_bwd_select), which runs reduced passes where only the gamma, blur or raw
     gradients are asked for; parameters that did not ask get None either way.  out_dtype (ParametrizedProcessing.output_dtype):
     torch.bfloat16 / torch.float16 -- `out` is allocated and written in that type and the cotangent is read in it
-    (r2l_isp_step_fwd_io / r2l_isp_step_bwd_io; the caller has asked io_supported); None / torch.float32: the calls above."""
+    (r2l_isp_step_fwd_io / r2l_isp_step_bwd_io; the caller has asked io_supported); None / torch.float32: the calls above.
+    out_layout (ParametrizedProcessing.output_memory_format): torch.channels_last -- `out` has channels-last strides and the
+    cotangent is read in them, in float32 or 16 bits (r2l_isp_step_fwd_layout / r2l_isp_step_bwd_layout; the caller has asked
+    layout_supported); None / torch.contiguous_format: the calls above."""
 
     @staticmethod
     def forward(ctx, raw, bl, wb, ccm, gamma, deb, sharp, blur, m1, m2, additive, bn_mode, bn_module, eps,
-                momentum, group, bits=16, grad_mode=True, epilogue=None, selective=False, out_dtype=None):
+                momentum, group, bits=16, grad_mode=True, epilogue=None, selective=False, out_dtype=None, out_layout=None):
         raw, denom = _raw_arg(raw, bits)
         params = (bl, wb, ccm, gamma, deb, sharp, blur, m1, m2)
         sizes = (4, 3, 9, 1, 81, 9, 25, 9, 9)
@@ -447,8 +482,13 @@ class _IspFused(torch.autograd.Function):
         if out_dtype not in IO_CODES:
             raise _lib.R2LError(f'output dtype must be None, torch.float32, torch.bfloat16 or torch.float16, got {out_dtype!r}')
         io = IO_CODES[out_dtype]
+        if out_layout not in LAYOUT_CODES:
+            raise _lib.R2LError(f'output memory format must be None, torch.contiguous_format or torch.channels_last, '
+                                f'got {out_layout!r}')
+        nhwc = LAYOUT_CODES[out_layout] == LAYOUT_NHWC
         out = torch.empty((B, 3, W, H) if (epi and (epilogue[2] & 1)) else (B, 3, H, W),
-                          dtype=out_dtype if io else torch.float32, device=dev)
+                          dtype=out_dtype if io else torch.float32, device=dev,
+                          memory_format=torch.channels_last if nhwc else torch.contiguous_format)
         rm = rv = nbt = None
         if bn_mode == BN_TRAIN:
             rm, rv, nbt = _bn_buffers(bn_module, dev)
@@ -463,6 +503,12 @@ class _IspFused(torch.autograd.Function):
         keep = _STEP_KEEP_LUMA if (grad_mode and any(ctx.needs_input_grad[:8])) else 0
 
         def call(phase, gathered):
+            if nhwc:
+                lib.check(lib.r2l_isp_step_fwd_layout(ptr(raw), int(denom is not None), denom or 1.0, table, ptr(additive),
+                                                      bn_mode, ptr(rm), ptr(rv), ptr(nbt), float(eps), mom, ptr(out), io,
+                                                      LAYOUT_NHWC, ptr(ws), nws, B, H, W, nranks, phase | keep | epi,
+                                                      ptr(gathered), stream), 'r2l_isp_step_fwd_layout')
+                return
             if io:
                 lib.check(lib.r2l_isp_step_fwd_io(ptr(raw), int(denom is not None), denom or 1.0, table, ptr(additive),
                                                   bn_mode, ptr(rm), ptr(rv), ptr(nbt), float(eps), mom, ptr(out), io, ptr(ws),
@@ -495,6 +541,7 @@ class _IspFused(torch.autograd.Function):
         ctx.ws = ws
         ctx.selective = bool(selective)
         ctx.io = io
+        ctx.nhwc = nhwc
         ctx.raw_why = _raw_grad_why(denom is None, W, additive is not None, bool(epi)) if ctx.needs_input_grad[0] else None
         return out
 
@@ -505,7 +552,13 @@ class _IspFused(torch.autograd.Function):
         if need_r and ctx.raw_why is not None:
             raise _lib.R2LError(ctx.raw_why + '; gradients w.r.t. such raw frames are defined on the staged path '
                                 '(ParametrizedProcessing routes them there)')
-        if ctx.io:
+        if ctx.nhwc:        # a cotangent of any strides: made channels-last once where it is not (a no-op where it is)
+            if gout.dtype != out.dtype:
+                raise TypeError(f'grad_out must be {out.dtype} like the output, got {gout.dtype}')
+            gout = gout.contiguous(memory_format=torch.channels_last)
+            if gout.data_ptr() % (8 if ctx.io else 16):     # (a channels-last view at an odd offset of its storage)
+                gout = gout.clone(memory_format=torch.channels_last)
+        elif ctx.io:
             if gout.dtype != out.dtype:
                 raise TypeError(f'grad_out must be {out.dtype} like the output, got {gout.dtype}')
             gout = gout if gout.is_contiguous() else gout.contiguous()
@@ -530,6 +583,13 @@ class _IspFused(torch.autograd.Function):
         mask = grad_mask(ctx.needs_input_grad) if ctx.selective else 0
 
         def call(phase, gathered):
+            if ctx.nhwc:    # (as a 16-bit call: the full route for any mask)
+                m = mask or ((GRAD_RAW if need_r else 0) | (127 if (need_p or need_r) else 0))
+                lib.check(lib.r2l_isp_step_bwd_layout(ptr(raw), int(denom is not None), denom or 1.0, ptr(additive), ptr(gout),
+                                                      ctx.io, LAYOUT_NHWC, ptr(out), ptr(gp), ptr(gadd), ctx.bn_mode, ptr(ws),
+                                                      nws, B, H, W, ctx.nranks, phase | ctx.keep, ptr(gathered), stream,
+                                                      ptr(graw), ptr(scratch), nscr, m), 'r2l_isp_step_bwd_layout')
+                return
             if ctx.io:      # (the library runs the full route for any mask; grad_raw goes with GRAD_RAW)
                 m = mask or ((GRAD_RAW if need_r else 0) | (127 if (need_p or need_r) else 0))
                 lib.check(lib.r2l_isp_step_bwd_io(ptr(raw), int(denom is not None), denom or 1.0, ptr(additive), ptr(gout),
@@ -565,20 +625,22 @@ class _IspFused(torch.autograd.Function):
             for i, ((_, off, n), shape) in enumerate(zip(PARAM_LAYOUT, ctx.shapes)):
                 if ctx.needs_input_grad[1 + i]:
                     grads[i] = gp[off:off + n].view(shape)
-        return (graw, *grads, None, None, gadd, None, None, None, None, None, None, None, None, None, None)
+        return (graw, *grads, None, None, gadd, None, None, None, None, None, None, None, None, None, None, None)
 
 
-def isp_fused(raw, module, bn_mode=BN_NONE, group=None, epilogue=None, out_dtype=None):
+def isp_fused(raw, module, bn_mode=BN_NONE, group=None, epilogue=None, out_dtype=None, out_layout=None):
     """fused forward of a ParametrizedProcessing-shaped module (parameters by the reference's names).  epilogue =
     (hflip, vflip, k): the output leaves the kernels as rot90^k(vflip(hflip(out))).  out_dtype = torch.bfloat16 / torch.float16:
-    the kernels write the output in that type (where io_supported says so; no epilogue then)."""
+    the kernels write the output in that type (where io_supported says so; no epilogue then).  out_layout =
+    torch.channels_last: they write it with channels-last strides (where layout_supported says so; no epilogue either)."""
     bn = module.batch_norm
     return _IspFused.apply(raw, module.black_level, module.white_balance, module.colour_correction,
                            module.gamma_correct, module.debayer.weight, module.sharpening_filter.weight,
                            module.gaussian_blur.weight, module.M_RGB_2_YUV, module.M_YUV_2_RGB,
                            module.additive_layer, bn_mode, bn, bn.eps if bn is not None else 1e-5,
                            bn.momentum if bn is not None else None, group, getattr(module, 'raw_bits', 16),
-                           torch.is_grad_enabled(), epilogue, bool(getattr(module, 'selective_backward', False)), out_dtype)
+                           torch.is_grad_enabled(), epilogue, bool(getattr(module, 'selective_backward', False)), out_dtype,
+                           out_layout)
 
 
 # --------------------------------------------------------------------------------------------------

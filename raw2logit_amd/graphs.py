@@ -15,6 +15,7 @@ and backward as two graphs around static-buffer copies, is SLOWER than eager on 
     g = StepGraph(processor, raw, None, loss=lambda rgb: criterion(head(rgb), target), loss_modules=(head,))
 
 A processor with `output_dtype` set (a bfloat16 / float16 output) is captured like any other: `cotangent` is then a tensor of that type.
+So is one with `output_memory_format = torch.channels_last`: hand it a channels-last `cotangent` and the backward reads it in place.
 
 The processor must not have run on another stream before (its AccumulateGrad nodes are created by the warm-up here, on
 the capture's side stream).

@@ -231,13 +231,21 @@ class ParametrizedProcessing(nn.Module):
     output and read the 16-bit cotangent themselves -- 6 instead of 12 bytes per pixel each, no cast passes; everywhere else
     the float32 path runs and torch casts.  Both give bit-identical values; the arithmetic, the parameters, ``.stages`` and
     BatchNorm's statistics stay float32 (``.half()`` on the module still raises).  Anything but None or those three dtypes
-    raises R2LError.  Opt-in until measured in real workloads."""
+    raises R2LError.  Opt-in until measured in real workloads.
+    ``output_memory_format`` (opt-in, default None = the planar layout) -- ``torch.channels_last``: the module returns
+    ``default_result.contiguous(memory_format=torch.channels_last)``, shape (B,3,H,W) with channels-last strides, for a task
+    model converted with ``model.to(memory_format=torch.channels_last)``; it combines with ``output_dtype``.  Where the fused
+    kernels serve such a call (functional.layout_supported: the conditions of a 16-bit call, float32 output included) they
+    store the interleaved output and read the interleaved cotangent themselves (one of other strides is made channels-last
+    once); everywhere else the planar path runs and torch converts -- the same values and gradients.  Anything but None,
+    ``torch.contiguous_format`` or ``torch.channels_last`` raises R2LError.  Opt-in."""
 
     raw_bits = 16
     supports_output_epilogue = True
     fused_raw_grad = False
     selective_backward = False
     output_dtype = None
+    output_memory_format = None
 
     def __init__(self, camera_parameters=None, track_stages=False, batch_norm_output=True):
         super().__init__()
@@ -312,12 +320,20 @@ class ParametrizedProcessing(nn.Module):
             raise F_._lib.R2LError(f'output_dtype must be None, torch.float32, torch.bfloat16 or torch.float16, got {odt!r}')
         io16 = odt if (F_.IO_CODES[odt] and epilogue is None and not self.track_stages and raw.dtype != torch.float64
                        and F_.io_supported(raw, self, odt)) else None
+        # `output_memory_format` (opt-in) likewise: the kernels store channels-last where they serve the call, in float32 or 16 bits
+        omf = self.output_memory_format
+        if omf not in F_.LAYOUT_CODES:
+            raise F_._lib.R2LError(f'output_memory_format must be None, torch.contiguous_format or torch.channels_last, '
+                                   f'got {omf!r}')
+        nhwc = F_.LAYOUT_CODES[omf] == F_.LAYOUT_NHWC
+        lay = omf if (nhwc and epilogue is None and not self.track_stages and raw.dtype != torch.float64
+                      and F_.layout_supported(raw, self, omf, odt)) else None
         # `fused_raw_grad = True` (opt-in): frames that require grad take the fused kernels too where they can produce
         # d/d raw (float32 frames, W % 4 == 0, W <= 2048, no additive layer); the epilogue then runs after them
         needs_raw_grad = raw.requires_grad and torch.is_grad_enabled()
         fused_raw = needs_raw_grad and not self.track_stages and self.fused_raw_grad and F_.raw_grad_supported(raw, self)
         if fused_raw:
-            rgb = self._fused_forward(raw, None, io16)
+            rgb = self._fused_forward(raw, None, io16, lay)
             d['stages'] = _LazyStages(self, raw)
         elif self.track_stages or needs_raw_grad:
             from ..staged import staged_forward
@@ -329,7 +345,7 @@ class ParametrizedProcessing(nn.Module):
             odd = bool(epilogue is not None and (epilogue[2] & 1))
             fuse = epilogue is not None and F_.epilogue_supported(raw, self) and \
                 (not odd or (getattr(self, 'fuse_rot90', False) and raw.shape[-1] == raw.shape[-2]))
-            rgb = self._fused_forward(raw, epilogue if fuse else None, io16)
+            rgb = self._fused_forward(raw, epilogue if fuse else None, io16, lay)
             d['stages'] = _LazyStages(self, raw)
             if fuse:
                 epilogue = None
@@ -343,12 +359,14 @@ class ParametrizedProcessing(nn.Module):
 
         if odt is not None and rgb.dtype != odt:
             rgb = rgb.to(odt)       # (autograd widens the cotangent; the stages stay float32)
+        if nhwc and not rgb.is_contiguous(memory_format=torch.channels_last):
+            rgb = rgb.contiguous(memory_format=torch.channels_last)     # (autograd converts the cotangent back)
 
         self.buffer['processed_rgb'] = rgb
 
         return rgb
 
-    def _fused_forward(self, raw, epilogue=None, out_dtype=None):
+    def _fused_forward(self, raw, epilogue=None, out_dtype=None, out_layout=None):
         bn = self.batch_norm
         if bn is None:
             mode = F_.BN_NONE
@@ -356,4 +374,4 @@ class ParametrizedProcessing(nn.Module):
             mode = F_.BN_TRAIN      # batch statistics; running statistics are updated on the device
         else:
             mode = F_.BN_EVAL
-        return F_.isp_fused(raw, self, mode, self.process_group, epilogue, out_dtype)
+        return F_.isp_fused(raw, self, mode, self.process_group, epilogue, out_dtype, out_layout)
