@@ -1180,6 +1180,9 @@ static int r2l_bwd_raw_pass(const R2LBwdCall& c, const R2LWorkspace& ws, const R
 // (this call's fold kernel, or the step's forward)
 static int r2l_bwd_launch(const R2LBwdCall& c, const R2LWorkspace& ws, const R2LBwdPlan& p) {
   if (c.ep.on && c.additive) return r2l_fail(-3, "r2l_isp_bwd: no output epilogue with an additive layer");
+  // (the plane passes count their work items -- B x strips x bands -- in an int, like the forward's: the same 2^30 limit, before any launch)
+  for (const int band : {p.b1_band, p.hb_band, p.hp_band, p.b2_band, p.raw_band})
+    if (band > 0 && r2l_plane_items(c.B, c.H, c.W, band) > (1L << 30)) return r2l_fail(-1, "r2l_isp_step_bwd: batch too large");
   const int u16 = c.raw.u16 ? 1 : 0, g1 = p.b1_grid;
   void* const stream = c.stream;
   const R2LBwd1Args a1 = r2l_bwd1_args(c, ws, p);
