@@ -171,57 +171,64 @@ R2L_KERNEL_V(r2l_launch_fwd_add_exact, R2LFwdArgs, R2L_LDS3(GFwd), R2L_OCC_FWD, 
 #endif
 // (8 wavefronts side by side -- frames 1024 < W <= 2048 -- need 99 KB of LDS: one workgroup per CU, 2 wavefronts per SIMD)
 #define R2L_FS_OCC_NW(NW) ((NW) == 8 ? 2 : R2L_FS_OCC)
-#define R2L_FS_KERNEL(name, NW, U16)                                                                    \
-  R2L_KERNEL_NT_LDS(name, R2LFwdStreamArgs, (NW) * 64, R2L_FS_LDS_FLOATS(NW), R2L_FS_OCC_NW(NW), r2l_fwd_stream_block<NW, U16>)
-R2L_FS_KERNEL(r2l_launch_fwd_stream_w1, 1, false)
-R2L_FS_KERNEL(r2l_launch_fwd_stream_w2, 2, false)
-R2L_FS_KERNEL(r2l_launch_fwd_stream_w4, 4, false)
-R2L_FS_KERNEL(r2l_launch_fwd_stream_w8, 8, false)
-R2L_FS_KERNEL(r2l_launch_fwd_stream_w1_u16, 1, true)
-R2L_FS_KERNEL(r2l_launch_fwd_stream_w2_u16, 2, true)
-R2L_FS_KERNEL(r2l_launch_fwd_stream_w4_u16, 4, true)
-R2L_FS_KERNEL(r2l_launch_fwd_stream_w8_u16, 8, true)
+// One spelling per family.  R2L_FS_KERNELS(pre, sfx, EPI, SONLY, IO) emits the eight kernels r2l_launch_fwd_stream<pre>_w{1,2,4,8}[_u16]<sfx>,
+// R2L_FS_ROW(pre, sfx) their row of r2l_fwd_stream_table: [16-bit container frames][wavefronts per row: 1, 2, 4, 8]
+#define R2L_FS_KERNEL(pre, NW, u16, sfx, ...)                                                                              \
+  R2L_KERNEL_NT_LDS(r2l_launch_fwd_stream##pre##_w##NW##u16##sfx, R2LFwdStreamArgs, (NW) * 64, R2L_FS_LDS_FLOATS(NW),     \
+                    R2L_FS_OCC_NW(NW), r2l_fwd_stream_block<NW, __VA_ARGS__>)
+#define R2L_FS_KERNELS(pre, sfx, ...)                  \
+  R2L_FS_KERNEL(pre, 1, , sfx, false, __VA_ARGS__)     \
+  R2L_FS_KERNEL(pre, 2, , sfx, false, __VA_ARGS__)     \
+  R2L_FS_KERNEL(pre, 4, , sfx, false, __VA_ARGS__)     \
+  R2L_FS_KERNEL(pre, 8, , sfx, false, __VA_ARGS__)     \
+  R2L_FS_KERNEL(pre, 1, _u16, sfx, true, __VA_ARGS__)  \
+  R2L_FS_KERNEL(pre, 2, _u16, sfx, true, __VA_ARGS__)  \
+  R2L_FS_KERNEL(pre, 4, _u16, sfx, true, __VA_ARGS__)  \
+  R2L_FS_KERNEL(pre, 8, _u16, sfx, true, __VA_ARGS__)
+#define R2L_FS_ROW(pre, sfx)                                                                                            \
+  {{r2l_launch_fwd_stream##pre##_w1##sfx, r2l_launch_fwd_stream##pre##_w2##sfx, r2l_launch_fwd_stream##pre##_w4##sfx,    \
+    r2l_launch_fwd_stream##pre##_w8##sfx},                                                                              \
+   {r2l_launch_fwd_stream##pre##_w1_u16##sfx, r2l_launch_fwd_stream##pre##_w2_u16##sfx,                                 \
+    r2l_launch_fwd_stream##pre##_w4_u16##sfx, r2l_launch_fwd_stream##pre##_w8_u16##sfx}}
+R2L_FS_KERNELS(, , false, false, R2L_IO_F32)
 // ... the statistics pass of train-mode BatchNorm (no output; keeps Y' when asked): its own instantiation
-#define R2L_FS_KERNEL_STATS(name, NW, U16)                                                              \
-  R2L_KERNEL_NT_LDS(name, R2LFwdStreamArgs, (NW) * 64, R2L_FS_LDS_FLOATS(NW), R2L_FS_OCC_NW(NW), r2l_fwd_stream_block<NW, U16, false, true>)
-R2L_FS_KERNEL_STATS(r2l_launch_fwd_stream_stats_w1, 1, false)
-R2L_FS_KERNEL_STATS(r2l_launch_fwd_stream_stats_w2, 2, false)
-R2L_FS_KERNEL_STATS(r2l_launch_fwd_stream_stats_w4, 4, false)
-R2L_FS_KERNEL_STATS(r2l_launch_fwd_stream_stats_w8, 8, false)
-R2L_FS_KERNEL_STATS(r2l_launch_fwd_stream_stats_w1_u16, 1, true)
-R2L_FS_KERNEL_STATS(r2l_launch_fwd_stream_stats_w2_u16, 2, true)
-R2L_FS_KERNEL_STATS(r2l_launch_fwd_stream_stats_w4_u16, 4, true)
-R2L_FS_KERNEL_STATS(r2l_launch_fwd_stream_stats_w8_u16, 8, true)
+R2L_FS_KERNELS(_stats, , false, true, R2L_IO_F32)
 // ... with the output epilogue (flip / flip / rot90 of the output planes as part of the stores, R2LEpi)
-#define R2L_FS_KERNEL_EPI(name, NW, U16)                                                                \
-  R2L_KERNEL_NT_LDS(name, R2LFwdStreamArgs, (NW) * 64, R2L_FS_LDS_FLOATS(NW), R2L_FS_OCC_NW(NW), r2l_fwd_stream_block<NW, U16, true>)
-R2L_FS_KERNEL_EPI(r2l_launch_fwd_stream_epi_w1, 1, false)
-R2L_FS_KERNEL_EPI(r2l_launch_fwd_stream_epi_w2, 2, false)
-R2L_FS_KERNEL_EPI(r2l_launch_fwd_stream_epi_w4, 4, false)
-R2L_FS_KERNEL_EPI(r2l_launch_fwd_stream_epi_w8, 8, false)
-R2L_FS_KERNEL_EPI(r2l_launch_fwd_stream_epi_w1_u16, 1, true)
-R2L_FS_KERNEL_EPI(r2l_launch_fwd_stream_epi_w2_u16, 2, true)
-R2L_FS_KERNEL_EPI(r2l_launch_fwd_stream_epi_w4_u16, 4, true)
-R2L_FS_KERNEL_EPI(r2l_launch_fwd_stream_epi_w8_u16, 8, true)
+R2L_FS_KERNELS(_epi, , true, false, R2L_IO_F32)
 // ... writing the output as bfloat16 / float16 (r2l_isp_step_fwd_io: R2L_IO_*; no epilogue)
-#define R2L_FS_KERNEL_IO(name, NW, U16, IO)                                                              \
-  R2L_KERNEL_NT_LDS(name, R2LFwdStreamArgs, (NW) * 64, R2L_FS_LDS_FLOATS(NW), R2L_FS_OCC_NW(NW),          \
-                    r2l_fwd_stream_block<NW, U16, false, false, IO>)
-#define R2L_FS_KERNELS_IO(sfx, IO)                                  \
-  R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w1##sfx, 1, false, IO)     \
-  R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w2##sfx, 2, false, IO)     \
-  R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w4##sfx, 4, false, IO)     \
-  R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w8##sfx, 8, false, IO)     \
-  R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w1_u16##sfx, 1, true, IO)  \
-  R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w2_u16##sfx, 2, true, IO)  \
-  R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w4_u16##sfx, 4, true, IO)  \
-  R2L_FS_KERNEL_IO(r2l_launch_fwd_stream_w8_u16##sfx, 8, true, IO)
-R2L_FS_KERNELS_IO(_bf16, R2L_IO_BF16)
-R2L_FS_KERNELS_IO(_f16, R2L_IO_F16)
+R2L_FS_KERNELS(, _bf16, false, false, R2L_IO_BF16)
+R2L_FS_KERNELS(, _f16, false, false, R2L_IO_F16)
 // ... writing it channels-last (r2l_isp_step_fwd_layout: R2L_LAYOUT_NHWC; float32 and 16 bits, no epilogue)
-R2L_FS_KERNELS_IO(_nhwc, R2L_IO_F32 | R2L_IO_NHWC)
-R2L_FS_KERNELS_IO(_bf16_nhwc, R2L_IO_BF16 | R2L_IO_NHWC)
-R2L_FS_KERNELS_IO(_f16_nhwc, R2L_IO_F16 | R2L_IO_NHWC)
+R2L_FS_KERNELS(, _nhwc, false, false, R2L_IO_F32 | R2L_IO_NHWC)
+R2L_FS_KERNELS(, _bf16_nhwc, false, false, R2L_IO_BF16 | R2L_IO_NHWC)
+R2L_FS_KERNELS(, _f16_nhwc, false, false, R2L_IO_F16 | R2L_IO_NHWC)
+// The implementations' `io` = element type (R2L_IO_*) | R2L_IO_NHWC for a channels-last tensor (r2l_common.h).  Every value but
+// R2L_IO_F32 takes the routes a 16-bit call takes; its rows in their launch tables (r2l_io_check has seen the value):
+#define R2L_IO_SLOTS 5
+static int r2l_io_slot(int io) { return (io & R2L_IO_NHWC) ? 2 + R2L_IO_ELEM(io) : io - 1; }
+typedef int (*r2l_fwd_stream_launch_t)(const R2LFwdStreamArgs&, int, void*);
+enum { R2L_FS_PLAIN, R2L_FS_STATS, R2L_FS_EPI, R2L_FS_IO /* + r2l_io_slot */ };
+static const r2l_fwd_stream_launch_t r2l_fwd_stream_table[R2L_FS_IO + R2L_IO_SLOTS][2][4] = {
+    R2L_FS_ROW(, ),      R2L_FS_ROW(_stats, ), R2L_FS_ROW(_epi, ),      R2L_FS_ROW(, _bf16),
+    R2L_FS_ROW(, _f16),  R2L_FS_ROW(, _nhwc),  R2L_FS_ROW(, _bf16_nhwc), R2L_FS_ROW(, _f16_nhwc)};
+// A family of [_u16] pairs -- plain, with the output epilogue (<pre> = _epi), one per io slot (<sfx>): the kernels base<pre>[_u16]<sfx>
+// and their row of a launch table, [16-bit container frames]
+#define R2L_PAIR_KERNELS(KERNEL, base, pre, sfx, ...) \
+  KERNEL(base##pre##sfx, false, __VA_ARGS__)          \
+  KERNEL(base##pre##_u16##sfx, true, __VA_ARGS__)
+#define R2L_PAIR_ROW(base, pre, sfx) {base##pre##sfx, base##pre##_u16##sfx}
+#define R2L_PAIR_FAMILY(KERNEL, base)                                             \
+  R2L_PAIR_KERNELS(KERNEL, base, , , false, R2L_IO_F32)                           \
+  R2L_PAIR_KERNELS(KERNEL, base, _epi, , true, R2L_IO_F32)                        \
+  R2L_PAIR_KERNELS(KERNEL, base, , _bf16, false, R2L_IO_BF16)                     \
+  R2L_PAIR_KERNELS(KERNEL, base, , _f16, false, R2L_IO_F16)                       \
+  R2L_PAIR_KERNELS(KERNEL, base, , _nhwc, false, R2L_IO_F32 | R2L_IO_NHWC)        \
+  R2L_PAIR_KERNELS(KERNEL, base, , _bf16_nhwc, false, R2L_IO_BF16 | R2L_IO_NHWC)  \
+  R2L_PAIR_KERNELS(KERNEL, base, , _f16_nhwc, false, R2L_IO_F16 | R2L_IO_NHWC)
+#define R2L_PAIR_TABLE(base)                                                                                             \
+  {R2L_PAIR_ROW(base, , ),      R2L_PAIR_ROW(base, _epi, ),       R2L_PAIR_ROW(base, , _bf16),     R2L_PAIR_ROW(base, , _f16), \
+   R2L_PAIR_ROW(base, , _nhwc), R2L_PAIR_ROW(base, , _bf16_nhwc), R2L_PAIR_ROW(base, , _f16_nhwc)}
+enum { R2L_PAIR_PLAIN, R2L_PAIR_EPI, R2L_PAIR_IO /* + r2l_io_slot */ };
 // the apply pass of train-mode BatchNorm on the Y' plane the statistics pass kept: independent wavefronts, no LDS
 #ifndef R2L_FA_OCC
 #define R2L_FA_OCC 3
@@ -229,25 +236,10 @@ R2L_FS_KERNELS_IO(_f16_nhwc, R2L_IO_F16 | R2L_IO_NHWC)
 #ifndef R2L_FA_NWV
 #define R2L_FA_NWV 4  // wavefronts (= work items) per workgroup of the apply and luma passes
 #endif
-#define R2L_FA_KERNEL(name, U16, EPI) \
-  R2L_KERNEL_NT_LDS(name, R2LFwdStreamArgs, 64 * R2L_FA_NWV, 4, R2L_FA_OCC, r2l_fwd_apply_block<U16, EPI, false, R2L_FA_NWV>)
-R2L_FA_KERNEL(r2l_launch_fwd_apply, false, false)
-R2L_FA_KERNEL(r2l_launch_fwd_apply_u16, true, false)
-R2L_FA_KERNEL(r2l_launch_fwd_apply_epi, false, true)
-R2L_FA_KERNEL(r2l_launch_fwd_apply_epi_u16, true, true)
-#define R2L_FA_KERNEL_IO(name, U16, IO)                                             \
-  R2L_KERNEL_NT_LDS(name, R2LFwdStreamArgs, 64 * R2L_FA_NWV, 4, R2L_FA_OCC,         \
-                    r2l_fwd_apply_block<U16, false, false, R2L_FA_NWV, IO>)
-R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_bf16, false, R2L_IO_BF16)
-R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_u16_bf16, true, R2L_IO_BF16)
-R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_f16, false, R2L_IO_F16)
-R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_u16_f16, true, R2L_IO_F16)
-R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_nhwc, false, R2L_IO_F32 | R2L_IO_NHWC)
-R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_u16_nhwc, true, R2L_IO_F32 | R2L_IO_NHWC)
-R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_bf16_nhwc, false, R2L_IO_BF16 | R2L_IO_NHWC)
-R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_u16_bf16_nhwc, true, R2L_IO_BF16 | R2L_IO_NHWC)
-R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_f16_nhwc, false, R2L_IO_F16 | R2L_IO_NHWC)
-R2L_FA_KERNEL_IO(r2l_launch_fwd_apply_u16_f16_nhwc, true, R2L_IO_F16 | R2L_IO_NHWC)
+#define R2L_FA_KERNEL(name, U16, EPI, IO) \
+  R2L_KERNEL_NT_LDS(name, R2LFwdStreamArgs, 64 * R2L_FA_NWV, 4, R2L_FA_OCC, r2l_fwd_apply_block<U16, EPI, false, R2L_FA_NWV, IO>)
+R2L_PAIR_FAMILY(R2L_FA_KERNEL, r2l_launch_fwd_apply)
+static const r2l_fwd_stream_launch_t r2l_fwd_apply_table[R2L_PAIR_IO + R2L_IO_SLOTS][2] = R2L_PAIR_TABLE(r2l_launch_fwd_apply);
 // ... the same walk without output: the BatchNorm statistics from the kept plane (2 wavefronts per workgroup, each with
 // its own work items; <= R2L_MAX_BLOCKS workgroups = partials of the reduction tree)
 #define R2L_FA_STATS_NWV 4
@@ -367,26 +359,12 @@ R2L_KERNEL_NT_LDS(r2l_launch_bwd_raw_plane, R2LRawGradArgs, 64 * R2L_BR_NWV, 4, 
 #define R2L_BNR_OCC 3
 #endif
 #define R2L_BNR_NWV 4
-#define R2L_BNR_KERNEL(name, U16, EPI)                                                                          \
+#define R2L_BNR_KERNEL(name, U16, EPI, IO)                                                                      \
   R2L_KERNEL_NT_LDS(name, R2LBnrArgs, 64 * R2L_BNR_NWV, R2L_FA_LDS_FLOATS(R2L_BNR_NWV, true), R2L_BNR_OCC,      \
-                    r2l_bnr_planes_block<U16, EPI, R2L_BNR_NWV>)
-R2L_BNR_KERNEL(r2l_launch_bnr_planes, false, false)
-R2L_BNR_KERNEL(r2l_launch_bnr_planes_u16, true, false)
-R2L_BNR_KERNEL(r2l_launch_bnr_planes_epi, false, true)
-R2L_BNR_KERNEL(r2l_launch_bnr_planes_epi_u16, true, true)
-#define R2L_BNR_KERNEL_IO(name, U16, IO)                                                                        \
-  R2L_KERNEL_NT_LDS(name, R2LBnrArgs, 64 * R2L_BNR_NWV, R2L_FA_LDS_FLOATS(R2L_BNR_NWV, true), R2L_BNR_OCC,      \
-                    r2l_bnr_planes_block<U16, false, R2L_BNR_NWV, IO>)
-R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_bf16, false, R2L_IO_BF16)
-R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_u16_bf16, true, R2L_IO_BF16)
-R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_f16, false, R2L_IO_F16)
-R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_u16_f16, true, R2L_IO_F16)
-R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_nhwc, false, R2L_IO_F32 | R2L_IO_NHWC)
-R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_u16_nhwc, true, R2L_IO_F32 | R2L_IO_NHWC)
-R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_bf16_nhwc, false, R2L_IO_BF16 | R2L_IO_NHWC)
-R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_u16_bf16_nhwc, true, R2L_IO_BF16 | R2L_IO_NHWC)
-R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_f16_nhwc, false, R2L_IO_F16 | R2L_IO_NHWC)
-R2L_BNR_KERNEL_IO(r2l_launch_bnr_planes_u16_f16_nhwc, true, R2L_IO_F16 | R2L_IO_NHWC)
+                    r2l_bnr_planes_block<U16, EPI, R2L_BNR_NWV, IO>)
+R2L_PAIR_FAMILY(R2L_BNR_KERNEL, r2l_launch_bnr_planes)
+typedef int (*r2l_bnr_launch_t)(const R2LBnrArgs&, int, void*);
+static const r2l_bnr_launch_t r2l_bnr_table[R2L_PAIR_IO + R2L_IO_SLOTS][2] = R2L_PAIR_TABLE(r2l_launch_bnr_planes);
 #endif
 R2L_KERNEL_V(r2l_launch_bwd2, R2LBwd2Args, R2L_LDS3(GBwd2), R2L_OCC_BWD2, r2l_bwd2_block<GBwd2, false>)
 R2L_KERNEL_V(r2l_launch_fwd_u16, R2LFwdArgs, R2L_LDS3(GFwd), R2L_OCC_FWD, r2l_fwd_block<GFwd, false, false, true>)
@@ -755,211 +733,247 @@ static int r2l_check_raw(const R2LRaw& raw, int W, const char* who) {
   return 0;
 }
 
-// internal flag of r2l_isp_fwd_impl (r2l_isp_step_fwd sets it): the workspace's Y' plane is this batch's, written by the
-// statistics pass with R2L_F_KEEP_LUMA -- the apply pass reads it instead of computing it again
-#define R2L_F_LUMA_VALID 1024
-// ... and of the statistics pass: luma pass (raw -> Y' into the workspace) + statistics from that plane, instead of the
-// streaming forward without output (r2l_isp_step_fwd sets it in train mode)
-#define R2L_F_SPLIT_STATS 2048
-#define R2L_F_INTERNAL (R2L_F_LUMA_VALID | R2L_F_SPLIT_STATS)
-// The implementations' `io` = element type (R2L_IO_*) | R2L_IO_NHWC for a channels-last tensor (r2l_common.h).  Every value but
-// R2L_IO_F32 takes the routes a 16-bit call takes; its row in their launch tables (r2l_io_check has seen the value):
-#define R2L_IO_SLOTS 5
-static int r2l_io_slot(int io) { return (io & R2L_IO_NHWC) ? 2 + R2L_IO_ELEM(io) : io - 1; }
+// ---- the forward: one plan, one launcher ----------------------------------------------------------------------------------
 // where the row-streaming forward (r2l_param_stream.h) runs -- and with R2L_F_KEEP_LUMA leaves Y' for kernel B1
 static bool r2l_fwd_streams(bool additive, int W) {
   return R2L_PLANE_PASSES && !additive && (W & 3) == 0 && W <= 2048 && !r2l_env_int("R2L_FWD_TILED", 0);
 }
-static int r2l_isp_fwd_impl(const R2LRaw& raw, const float* params, const float* additive,
-                            const float* bn_mean_istd, float* out, double* stats, void* workspace,
-                            size_t workspace_bytes, int B, int H, int W, int flags, void* stream,
-                            const R2LBnFinalizeArgs* fin = nullptr, const R2LEpi* ep = nullptr, int io = R2L_IO_F32) {
-  // io: what `out` really holds (R2L_IO_* | R2L_IO_NHWC; r2l_isp_step_fwd_layout has checked that the streaming kernels serve the call)
-  if (int e = r2l_check_dims(B, H, W)) return e;
-  if (int e = r2l_check_raw(raw, W, "r2l_isp_fwd")) return e;
-  if (io != R2L_IO_F32 && (!r2l_fwd_streams(additive, W) || (ep && ep->on)))
-    return r2l_fail(-3, "r2l_isp_fwd: internal: a 16-bit / channels-last output needs the row-streaming forward without an epilogue");
-  if (!params || !workspace) return r2l_fail(-1, "r2l_isp_fwd: null pointer");
-  if (additive && (H != 256 || W != 256))
-    return r2l_fail(-1, "additive_layer is (1,3,256,256): needs 256x256 frames");
-  if (r2l_env_int("R2L_FORCE_SPLIT", 0)) flags |= R2L_F_INTERNAL;  // (diagnostic builds: tests/timeline_fwd.py)
-  const bool stats_only = (flags & R2L_F_STATS_ONLY) != 0;
-  if (stats_only) out = nullptr;
-  if (!out && !stats) return r2l_fail(-1, "r2l_isp_fwd: nothing to compute (no out, no stats)");
-  const R2LWorkspace ws = r2l_carve(workspace, B, H, W);
-  if (workspace_bytes < ws.total) return r2l_fail(-2, "r2l_isp_fwd: workspace too small");
-  if (!(flags & R2L_F_FOLDED_VALID)) {
-    R2LFoldArgs fa{params, ws.folded, ws.counters};
-    if (int e = r2l_launch_fold(fa, 1, stream)) return e;
-  }
+// which pass of a step a forward is: a whole forward (every public r2l_isp_fwd*; the step's without train-mode BatchNorm), the
+// statistics pass of train mode, or its apply pass -- the workspace's Y' plane is then this batch's, left by the statistics pass
+enum { R2L_FWD_WHOLE, R2L_FWD_STATS_PASS, R2L_FWD_APPLY_PASS };
+// what a forward works on
+struct R2LFwdCall {
+  R2LRaw raw;
+  const float *params, *additive, *bn;
+  float* out;     // elements of type io; null: the statistics alone
+  double* stats;  // or null
+  const R2LBnFinalizeArgs* fin;  // or null; one rank: the last workgroup also does the BatchNorm bookkeeping
+  R2LEpi ep;
+  int io;    // what `out` really holds (R2L_IO_* | R2L_IO_NHWC; r2l_io_check has seen that the streaming kernels serve the call)
+  int pass;  // R2L_FWD_*
+  int B, H, W;
+  void* stream;
+};
+enum { R2L_FWD_STREAM, R2L_FWD_STREAM_STATS, R2L_FWD_SPLIT_STATS, R2L_FWD_APPLY, R2L_FWD_TILES };
+enum { R2L_FWD_TILE_EXACT, R2L_FWD_TILE_RAGGED, R2L_FWD_TILE_ADD };
+enum { R2L_YP_NONE, R2L_YP_WRITE, R2L_YP_READ };
+// the work items of one launch: bands of band_h rows (0: a tile kernel), nitems of them in all, on `grid` workgroups
+struct R2LPass {
+  int band_h, nband, nitems, grid;
+};
+// What a forward launches, decided from the shape of the call alone (r2l_fwd_plan): r2l_fwd_launch walks it
+struct R2LFwdPlan {
+  int route;       // R2L_FWD_STREAM: the row-streaming kernel; _STREAM_STATS: its statistics-only instantiation; _SPLIT_STATS: luma
+                   // pass + statistics from the plane; _APPLY: the apply pass on the kept Y'; _TILES: the tile kernels
+  int tile;        // R2L_FWD_TILE_*
+  int nw;          // wavefronts side by side per row: 1 << nw (the column of r2l_fwd_stream_table)
+  int yp;          // R2L_YP_*: what the route's (last) launch does with the workspace's Y' plane
+  bool epi;        // the output goes through the epilogue
+  bool too_large;  // a pass counts more work items than an int holds
+  R2LPass luma, main;  // the luma pass of R2L_FWD_SPLIT_STATS; the route's one or last launch
+};
+// a plane pass (r2l_param_stream.h, r2l_param_plane_bwd.h): independent wavefronts, one per (image, band, 256-column strip); band
+// height: r2l_band_rows for `slots` resident wavefronts; nwv items in flight per workgroup, at most `cap` workgroups (r2l_plane_grid)
+static R2LPass r2l_plane_pass(int B, int H, int W, long slots, const char* band_env, int nwv, long cap, bool& too_large) {
+  R2LPass p;
+  p.band_h = r2l_band_rows(B, H, W, slots, band_env);
+  p.nband = (H + p.band_h - 1) / p.band_h;
+  const long items = r2l_plane_items(B, H, W, p.band_h);
+  too_large = too_large || items > (1L << 30);
+  p.nitems = (int)items;
+  p.grid = r2l_plane_grid(B, H, W, p.band_h, nwv, cap);
+  return p;
+}
+// The only reader of the forward's overrides of diagnostic builds (R2L_FORCE_SPLIT, R2L_FWD_*, R2L_GRID_FWD, the band heights;
+// R2L_FWD_TILED: r2l_fwd_streams).  has_out: after R2L_F_STATS_ONLY
+static R2LFwdPlan r2l_fwd_plan(int pass, bool has_out, bool has_stats, bool additive, bool keep_luma, bool epi_on, int B, int H,
+                               int W) {
+  R2LFwdPlan p = {};
+  p.epi = epi_on && has_out;
 #ifndef R2L_SERIAL
   if (r2l_fwd_streams(additive, W)) {
+    // (diagnostic builds, tests/timeline_fwd.py: every call as both passes of a step)
+    const bool force = r2l_env_int("R2L_FORCE_SPLIT", 0) != 0;
+    const bool stats_pass = force || pass == R2L_FWD_STATS_PASS, apply_pass = force || pass == R2L_FWD_APPLY_PASS;
     // row-streaming forward: work item = (image, band of rows); short bands are cheap here (the 8 halo rows of a
     // band only compute their luma), so aim at ~2048 items (three wavefronts per SIMD: the kernel's row step is a
     // chain of scalar-load waits, which only other wavefronts can fill), bands of >= 16 rows
-    R2LFwdStreamArgs fa;
-    fa.raw = raw;
-    fa.F = ws.folded;
-    fa.bn = bn_mean_istd;
-    fa.out = out;
-    // (a statistics pass of the streaming kernel keeps Y' too: for kernel B1 and for the apply pass)
-    fa.yp_out = (flags & (R2L_F_KEEP_LUMA | R2L_F_SPLIT_STATS)) ? ws.yp : nullptr;
-    fa.yp_in = nullptr;
-#ifdef R2L_EXP_STAMPS
-    fa.tl = r2l_env_int("R2L_TL_STREAM", 0) ? (unsigned long long*)ws.debug : nullptr;  // (tests/timeline_fwd.py)
-#endif
-    fa.stat_partial = stats ? ws.part_small : nullptr;
-    fa.B = B;
-    fa.H = H;
-    fa.W = W;
+    p.nw = W <= 256 ? 0 : (W <= 512 ? 1 : (W <= 1024 ? 2 : 3));
     // one round of resident workgroups: 256 CUs x 12 wavefronts (three per SIMD) / wavefronts per workgroup
-    const int nwv = W <= 256 ? 1 : (W <= 512 ? 2 : (W <= 1024 ? 4 : 8));
-    const long resident = 256L * (12 / nwv);
-    long nband = r2l_env_int("R2L_FS_BAND", 0) ? (H + r2l_env_int("R2L_FS_BAND", 32) - 1) / r2l_env_int("R2L_FS_BAND", 32)
-                                               : resident / B;
+    const long resident = 256L * (12 >> p.nw);
+    const int fs_band = r2l_env_int("R2L_FS_BAND", 0);
+    long nband = fs_band ? (H + fs_band - 1) / fs_band : resident / B;
     if (nband > H / R2L_FS_MINBAND) nband = H / R2L_FS_MINBAND;
     if (nband < 1) nband = 1;
-    fa.band_h = (int)((H + nband - 1) / nband);
-    fa.band_h += fa.band_h & 1;
-    fa.nband = (H + fa.band_h - 1) / fa.band_h;
-    const long nitems = (long)B * fa.nband;
-    if (nitems > (1L << 30)) return r2l_fail(-1, "r2l_isp_fwd: batch too large");
-    fa.nitems = (int)nitems;
+    R2LPass fs;
+    fs.band_h = (int)((H + nband - 1) / nband);
+    fs.band_h += fs.band_h & 1;
+    fs.nband = (H + fs.band_h - 1) / fs.band_h;
+    const long nitems = (long)B * fs.nband;
+    p.too_large = nitems > (1L << 30);  // (counted on every route of a frame that streams)
+    fs.nitems = (int)nitems;
     long cap = r2l_env_int("R2L_GRID_FWD", (int)(resident < R2L_MAX_BLOCKS ? resident : R2L_MAX_BLOCKS));
     if (cap > R2L_MAX_BLOCKS) cap = R2L_MAX_BLOCKS;
-    const int sgrid = (int)(nitems < cap ? nitems : cap);
-    fa.tree = R2LTree{ws.part_small, nullptr, ws.gpartial, stats ? ws.counters : nullptr, 12, 0};
-    fa.stats_out = stats;
-    if (fin)
-      fa.fin = *fin;
-    else
-      fa.fin.bn = nullptr;
-    const int nw = W <= 256 ? 0 : (W <= 512 ? 1 : (W <= 1024 ? 2 : 3));
-    typedef int (*launch_t)(const R2LFwdStreamArgs&, int, void*);
-    static const launch_t table[2][2][4] = {
-        {{r2l_launch_fwd_stream_w1, r2l_launch_fwd_stream_w2, r2l_launch_fwd_stream_w4, r2l_launch_fwd_stream_w8},
-         {r2l_launch_fwd_stream_w1_u16, r2l_launch_fwd_stream_w2_u16, r2l_launch_fwd_stream_w4_u16,
-          r2l_launch_fwd_stream_w8_u16}},
-        {{r2l_launch_fwd_stream_epi_w1, r2l_launch_fwd_stream_epi_w2, r2l_launch_fwd_stream_epi_w4,
-          r2l_launch_fwd_stream_epi_w8},
-         {r2l_launch_fwd_stream_epi_w1_u16, r2l_launch_fwd_stream_epi_w2_u16, r2l_launch_fwd_stream_epi_w4_u16,
-          r2l_launch_fwd_stream_epi_w8_u16}}};
-    const bool epi = ep && ep->on && out;
-    fa.ep = epi ? *ep : R2LEpi{0, 0, 0, 0};
-    // The passes on the kept luma plane (r2l_param_stream.h: r2l_fwd_luma_block, r2l_fwd_apply_block): independent
-    // wavefronts, one per (image, band, 256-column strip); band heights: r2l_band_rows
-    const long nstrip = (W + 255) / 256;
-    auto band_rows = [&](long slots, const char* env) { return r2l_band_rows(B, H, W, slots, env); };
+    fs.grid = (int)(nitems < cap ? nitems : cap);
+    // The passes on the kept luma plane (r2l_fwd_luma_block, r2l_fwd_apply_block): r2l_plane_pass
     const bool kept_ok = !r2l_env_int("R2L_FWD_APPLY_RECOMPUTE", 0);
     // statistics pass = luma pass + statistics from the plane, where that is faster than the streaming forward without
     // output: frames one strip wide (64x256x256: 12 + 26 us against 46; 128x256x256: 17 + 36 against 61).  On 512-wide
     // frames the two kernels issue as many vector instructions as the one (7.1 M + 15.9 M against 23.9 M at 64x512x512)
     // and take as long (28.5 + 55 us against 79.7): profiles/r03_split_stats.txt
     const bool split = r2l_env_int("R2L_FWD_STATS_SPLIT", 0) || (W <= 256 && !r2l_env_int("R2L_FWD_STATS_STREAM", 0));
-    if (!out && stats && (flags & R2L_F_SPLIT_STATS) && kept_ok && split) {
-      R2LFwdStreamArgs la = fa;
-      la.stat_partial = nullptr;
-#ifdef R2L_EXP_STAMPS
-      la.tl = (unsigned long long*)ws.debug;
-      fa.tl = (unsigned long long*)ws.debug + 8192;
-#endif
-      la.band_h = band_rows(256L * 4 * R2L_FL_OCC, "R2L_FL_BAND");
-      la.nband = (H + la.band_h - 1) / la.band_h;
-      const long lgrid = (long)B * la.nband * nstrip;
-      if (lgrid > (1L << 30)) return r2l_fail(-1, "r2l_isp_fwd: batch too large");
-      la.nitems = (int)lgrid;
-      const int lg = (int)((lgrid + R2L_FA_NWV - 1) / R2L_FA_NWV);
-      if (int e = raw.u16 ? r2l_launch_fwd_luma_u16(la, lg, stream) : r2l_launch_fwd_luma(la, lg, stream)) return e;
-      fa.yp_in = ws.yp;
-      fa.yp_out = nullptr;
-      fa.band_h = band_rows(256L * 4 * R2L_FA_STATS_OCC, "R2L_FST_BAND");
-      fa.nband = (H + fa.band_h - 1) / fa.band_h;
-      const long items = (long)B * fa.nband * nstrip;
-      if (items > (1L << 30)) return r2l_fail(-1, "r2l_isp_fwd: batch too large");
-      fa.nitems = (int)items;
-      const int g = r2l_plane_grid(B, H, W, fa.band_h, R2L_FA_STATS_NWV, r2l_env_int("R2L_GRID_FWD", R2L_MAX_BLOCKS));
-      return raw.u16 ? r2l_launch_fwd_stats_u16(fa, g, stream) : r2l_launch_fwd_stats(fa, g, stream);
+    if (!has_out && has_stats && stats_pass && kept_ok && split) {
+      p.route = R2L_FWD_SPLIT_STATS;
+      p.yp = R2L_YP_READ;
+      p.luma = r2l_plane_pass(B, H, W, 256L * 4 * R2L_FL_OCC, "R2L_FL_BAND", R2L_FA_NWV, 0, p.too_large);
+      // (<= R2L_MAX_BLOCKS workgroups = partials of the reduction tree)
+      p.main = r2l_plane_pass(B, H, W, 256L * 4 * R2L_FA_STATS_OCC, "R2L_FST_BAND", R2L_FA_STATS_NWV,
+                              r2l_env_int("R2L_GRID_FWD", R2L_MAX_BLOCKS), p.too_large);
+    } else if (has_out && !has_stats && apply_pass && kept_ok) {
+      p.route = R2L_FWD_APPLY;
+      p.yp = R2L_YP_READ;
+      p.main = r2l_plane_pass(B, H, W, 256L * 4 * R2L_FA_OCC, "R2L_FA_BAND", R2L_FA_NWV, 0, p.too_large);
+    } else {
+      // the statistics alone: the kernel's own instantiation (no output code, fewer live scalars)
+      p.route = (!has_out && has_stats) ? R2L_FWD_STREAM_STATS : R2L_FWD_STREAM;
+      // (a statistics pass of the streaming kernel keeps Y' too: for kernel B1 and for the apply pass)
+      p.yp = (keep_luma || stats_pass) ? R2L_YP_WRITE : R2L_YP_NONE;
+      p.main = fs;
     }
-    if (out && !stats && (flags & R2L_F_LUMA_VALID) && kept_ok) {
-      // apply pass on the kept Y'
-#ifdef R2L_EXP_STAMPS
-      fa.tl = (unsigned long long*)ws.debug + 16384;
-#endif
-      fa.yp_in = ws.yp;
-      fa.yp_out = nullptr;
-      fa.stat_partial = nullptr;
-      fa.band_h = band_rows(256L * 4 * R2L_FA_OCC, "R2L_FA_BAND");
-      fa.nband = (H + fa.band_h - 1) / fa.band_h;
-      const long grid = (long)B * fa.nband * nstrip;
-      if (grid > (1L << 30)) return r2l_fail(-1, "r2l_isp_fwd: batch too large");
-      fa.nitems = (int)grid;
-      static const launch_t atable[2][2] = {{r2l_launch_fwd_apply, r2l_launch_fwd_apply_u16},
-                                            {r2l_launch_fwd_apply_epi, r2l_launch_fwd_apply_epi_u16}};
-      static const launch_t atable_io[R2L_IO_SLOTS][2] = {
-          {r2l_launch_fwd_apply_bf16, r2l_launch_fwd_apply_u16_bf16},
-          {r2l_launch_fwd_apply_f16, r2l_launch_fwd_apply_u16_f16},
-          {r2l_launch_fwd_apply_nhwc, r2l_launch_fwd_apply_u16_nhwc},
-          {r2l_launch_fwd_apply_bf16_nhwc, r2l_launch_fwd_apply_u16_bf16_nhwc},
-          {r2l_launch_fwd_apply_f16_nhwc, r2l_launch_fwd_apply_u16_f16_nhwc}};
-      const launch_t apply =
-          io != R2L_IO_F32 ? atable_io[r2l_io_slot(io)][raw.u16 ? 1 : 0] : atable[epi ? 1 : 0][raw.u16 ? 1 : 0];
-      return apply(fa, (int)((grid + R2L_FA_NWV - 1) / R2L_FA_NWV), stream);
-    }
-    if (!out && stats) {  // the statistics pass: its own instantiation (no output code, fewer live scalars)
-      static const launch_t stable[2][4] = {
-          {r2l_launch_fwd_stream_stats_w1, r2l_launch_fwd_stream_stats_w2, r2l_launch_fwd_stream_stats_w4,
-           r2l_launch_fwd_stream_stats_w8},
-          {r2l_launch_fwd_stream_stats_w1_u16, r2l_launch_fwd_stream_stats_w2_u16, r2l_launch_fwd_stream_stats_w4_u16,
-           r2l_launch_fwd_stream_stats_w8_u16}};
-      return stable[raw.u16 ? 1 : 0][nw](fa, sgrid, stream);
-    }
-    if (io != R2L_IO_F32) {
-#define R2L_FS_ROW_IO(sfx)                                                                                          \
-  {{r2l_launch_fwd_stream_w1##sfx, r2l_launch_fwd_stream_w2##sfx, r2l_launch_fwd_stream_w4##sfx,                    \
-    r2l_launch_fwd_stream_w8##sfx},                                                                                 \
-   {r2l_launch_fwd_stream_w1_u16##sfx, r2l_launch_fwd_stream_w2_u16##sfx, r2l_launch_fwd_stream_w4_u16##sfx,        \
-    r2l_launch_fwd_stream_w8_u16##sfx}}
-      static const launch_t table_io[R2L_IO_SLOTS][2][4] = {R2L_FS_ROW_IO(_bf16), R2L_FS_ROW_IO(_f16), R2L_FS_ROW_IO(_nhwc),
-                                                            R2L_FS_ROW_IO(_bf16_nhwc), R2L_FS_ROW_IO(_f16_nhwc)};
-#undef R2L_FS_ROW_IO
-      return table_io[r2l_io_slot(io)][raw.u16 ? 1 : 0][nw](fa, sgrid, stream);
-    }
-    return table[epi ? 1 : 0][raw.u16 ? 1 : 0][nw](fa, sgrid, stream);
+    return p;
   }
 #endif
-  if (ep && ep->on && out && additive) return r2l_fail(-3, "r2l_isp_fwd: no output epilogue with an additive layer");
+  p.route = R2L_FWD_TILES;
+  // (an additive layer means 256 x 256 frames: they tile exactly)
+  const bool exact = (H % GFwd::TH == 0) && (W % GFwd::TW == 0);
+  p.tile = additive ? R2L_FWD_TILE_ADD : (exact ? R2L_FWD_TILE_EXACT : R2L_FWD_TILE_RAGGED);
   const int ntiles = B * ((H + GFwd::TH - 1) / GFwd::TH) * ((W + GFwd::TW - 1) / GFwd::TW);
-  const int grid = r2l_tile_grid(ntiles, r2l_env_int("R2L_GRID_FWD", 512));
-  R2LFwdArgs a;
+  p.main.grid = r2l_tile_grid(ntiles, r2l_env_int("R2L_GRID_FWD", 512));
+  return p;
+}
+#ifndef R2L_SERIAL
+// the argument block of the streaming kernel and of every plane pass (luma, statistics from the plane, apply; the backward's
+// BatchNorm sums) over `pass`: no output, no Y' plane, no epilogue; sums: its partials go through the workspace's reduction tree
+// (the arrival counters are valid: this call or an earlier one on this workspace ran the fold kernel)
+static R2LFwdStreamArgs r2l_fwd_stream_args(const R2LRaw& raw, const R2LWorkspace& ws, const float* bn, int B, int H, int W,
+                                            const R2LPass& pass, bool sums) {
+  R2LFwdStreamArgs a;
   a.raw = raw;
-  a.additive = additive;
   a.F = ws.folded;
-  a.bn = bn_mean_istd;
-  a.out = out;
-  a.stat_partial = stats ? ws.part_small : nullptr;
+  a.bn = bn;
+  a.out = nullptr;
+  a.yp_out = nullptr;
+  a.yp_in = nullptr;
+#ifdef R2L_EXP_STAMPS
+  a.tl = nullptr;
+#endif
+  a.stat_partial = sums ? ws.part_small : nullptr;
   a.B = B;
   a.H = H;
   a.W = W;
+  a.band_h = pass.band_h;
+  a.nband = pass.nband;
+  a.nitems = pass.nitems;
+  a.tree = R2LTree{ws.part_small, nullptr, ws.gpartial, sums ? ws.counters : nullptr, 12, 0};
+  a.stats_out = nullptr;
+  a.fin.bn = nullptr;
+  a.ep = R2LEpi{0, 0, 0, 0};
+  return a;
+}
+#endif
+// The launches of plan `p` = r2l_fwd_plan(this call), in order.  The workspace's folded weights and arrival counters are valid
+static int r2l_fwd_launch(const R2LFwdCall& c, const R2LWorkspace& ws, const R2LFwdPlan& p) {
+  const int u16 = c.raw.u16 ? 1 : 0;
+  const R2LEpi ep = p.epi ? c.ep : R2LEpi{0, 0, 0, 0};
+#ifndef R2L_SERIAL
+  if (p.route != R2L_FWD_TILES) {
+    R2LFwdStreamArgs fa = r2l_fwd_stream_args(c.raw, ws, c.bn, c.B, c.H, c.W, p.main, c.stats != nullptr);
+    fa.out = c.out;
+    fa.yp_out = p.yp == R2L_YP_WRITE ? ws.yp : nullptr;
+    fa.yp_in = p.yp == R2L_YP_READ ? ws.yp : nullptr;
+    fa.stats_out = c.stats;
+    if (c.fin) fa.fin = *c.fin;
+    fa.ep = ep;
+#ifdef R2L_EXP_STAMPS  // (tests/timeline_fwd.py: the streaming kernel on request, each plane pass in its own third)
+    if (p.route == R2L_FWD_APPLY) fa.tl = (unsigned long long*)ws.debug + 16384;
+    else if (p.route == R2L_FWD_SPLIT_STATS) fa.tl = (unsigned long long*)ws.debug + 8192;
+    else if (r2l_env_int("R2L_TL_STREAM", 0)) fa.tl = (unsigned long long*)ws.debug;
+#endif
+    switch (p.route) {
+      case R2L_FWD_SPLIT_STATS: {
+        R2LFwdStreamArgs la = fa;  // raw -> Y'
+        la.yp_out = ws.yp;
+        la.yp_in = nullptr;
+        la.stat_partial = nullptr;
+        la.band_h = p.luma.band_h;
+        la.nband = p.luma.nband;
+        la.nitems = p.luma.nitems;
+#ifdef R2L_EXP_STAMPS
+        la.tl = (unsigned long long*)ws.debug;
+#endif
+        if (int e = u16 ? r2l_launch_fwd_luma_u16(la, p.luma.grid, c.stream) : r2l_launch_fwd_luma(la, p.luma.grid, c.stream)) return e;
+        return u16 ? r2l_launch_fwd_stats_u16(fa, p.main.grid, c.stream) : r2l_launch_fwd_stats(fa, p.main.grid, c.stream);
+      }
+      case R2L_FWD_APPLY:
+        return r2l_fwd_apply_table[c.io != R2L_IO_F32 ? R2L_PAIR_IO + r2l_io_slot(c.io) : (p.epi ? R2L_PAIR_EPI : R2L_PAIR_PLAIN)][u16](
+            fa, p.main.grid, c.stream);
+      case R2L_FWD_STREAM_STATS:
+        return r2l_fwd_stream_table[R2L_FS_STATS][u16][p.nw](fa, p.main.grid, c.stream);
+      default:
+        return r2l_fwd_stream_table[c.io != R2L_IO_F32 ? R2L_FS_IO + r2l_io_slot(c.io) : (p.epi ? R2L_FS_EPI : R2L_FS_PLAIN)][u16][p.nw](
+            fa, p.main.grid, c.stream);
+    }
+  }
+#endif
+  // the tile kernels
+  if (p.epi && c.additive) return r2l_fail(-3, "r2l_isp_fwd: no output epilogue with an additive layer");
+  R2LFwdArgs a;
+  a.raw = c.raw;
+  a.additive = c.additive;
+  a.F = ws.folded;
+  a.bn = c.bn;
+  a.out = c.out;
+  a.stat_partial = c.stats ? ws.part_small : nullptr;
+  a.B = c.B;
+  a.H = c.H;
+  a.W = c.W;
   a.debug = ws.debug;
-  // the statistics are reduced by the last workgroups of the same launch (the workspace's arrival counters
-  // are valid: this call or an earlier one on this workspace ran the fold kernel)
-  a.tree = R2LTree{ws.part_small, nullptr, ws.gpartial, stats ? ws.counters : nullptr, 12, 0};
-  a.stats_out = stats;
-  if (fin)
-    a.fin = *fin;
+  // the statistics are reduced by the last workgroups of the same launch
+  a.tree = R2LTree{ws.part_small, nullptr, ws.gpartial, c.stats ? ws.counters : nullptr, 12, 0};
+  a.stats_out = c.stats;
+  if (c.fin)
+    a.fin = *c.fin;
   else
     a.fin.bn = nullptr;
-  a.ep = (ep && ep->on && out) ? *ep : R2LEpi{0, 0, 0, 0};
-  const bool exact = (H % GFwd::TH == 0) && (W % GFwd::TW == 0);
-  int e;
-  if (raw.u16)   // (an additive layer means 256 x 256 frames: they tile exactly)
-    e = additive ? r2l_launch_fwd_add_exact_u16(a, grid, stream)
-                 : (exact ? r2l_launch_fwd_u16(a, grid, stream) : r2l_launch_fwd_ragged_u16(a, grid, stream));
-  else
-    e = additive ? r2l_launch_fwd_add_exact(a, grid, stream)
-                 : (exact ? r2l_launch_fwd(a, grid, stream) : r2l_launch_fwd_ragged(a, grid, stream));
-  if (e) return e;
-  return 0;
+  a.ep = ep;
+  typedef int (*launch_t)(const R2LFwdArgs&, int, void*);
+  static const launch_t tile[3][2] = {{r2l_launch_fwd, r2l_launch_fwd_u16},
+                                      {r2l_launch_fwd_ragged, r2l_launch_fwd_ragged_u16},
+                                      {r2l_launch_fwd_add_exact, r2l_launch_fwd_add_exact_u16}};
+  return tile[p.tile][u16](a, p.main.grid, c.stream);
+}
+// validate, carve, fold if needed, plan, launch.  flags: the public R2L_F_* bits (others are ignored)
+static int r2l_isp_fwd_impl(R2LFwdCall c, int flags, void* workspace, size_t workspace_bytes) {
+  const int B = c.B, H = c.H, W = c.W;
+  if (int e = r2l_check_dims(B, H, W)) return e;
+  if (int e = r2l_check_raw(c.raw, W, "r2l_isp_fwd")) return e;
+  if (c.io != R2L_IO_F32 && (!r2l_fwd_streams(c.additive, W) || c.ep.on))
+    return r2l_fail(-3, "r2l_isp_fwd: internal: a 16-bit / channels-last output needs the row-streaming forward without an epilogue");
+  if (!c.params || !workspace) return r2l_fail(-1, "r2l_isp_fwd: null pointer");
+  if (c.additive && (H != 256 || W != 256))
+    return r2l_fail(-1, "additive_layer is (1,3,256,256): needs 256x256 frames");
+  if (flags & R2L_F_STATS_ONLY) c.out = nullptr;
+  if (!c.out && !c.stats) return r2l_fail(-1, "r2l_isp_fwd: nothing to compute (no out, no stats)");
+  const R2LWorkspace ws = r2l_carve(workspace, B, H, W);
+  if (workspace_bytes < ws.total) return r2l_fail(-2, "r2l_isp_fwd: workspace too small");
+  if (!(flags & R2L_F_FOLDED_VALID)) {
+    R2LFoldArgs fa{c.params, ws.folded, ws.counters};
+    if (int e = r2l_launch_fold(fa, 1, c.stream)) return e;
+  }
+  const R2LFwdPlan p = r2l_fwd_plan(c.pass, c.out != nullptr, c.stats != nullptr, c.additive != nullptr,
+                                    (flags & R2L_F_KEEP_LUMA) != 0, c.ep.on != 0, B, H, W);
+  if (p.too_large) return r2l_fail(-1, "r2l_isp_fwd: batch too large");
+  return r2l_fwd_launch(c, ws, p);
 }
 
 int r2l_bn_finalize(const double* stats, int nranks, float* bn_mean_istd, double* moments, float* running_mean,
@@ -1006,8 +1020,6 @@ int r2l_bn_bwd_reduce(const float* grad_out, const float* out, const double* tot
 
 // ---- the backward: one plan, one launcher ---------------------------------------------------------------------------------
 #define R2L_STEP_EPI_MASK (R2L_STEP_EPI_HFLIP | R2L_STEP_EPI_VFLIP | (3 << R2L_STEP_EPI_ROT_SHIFT))
-// R2L_BWD_PLANES of diagnostic builds: the plane passes (and the recomputing BatchNorm sums) below their pixel thresholds too
-static bool r2l_bwd_planes_forced() { return r2l_env_int("R2L_BWD_PLANES", 0) != 0; }
 // kernel B1 as a tile kernel (which instantiation), as the plane passes, or as a reduced plane pass (R2LBwdPlan::select)
 enum { R2L_B1_TILE_SAVED, R2L_B1_TILE_ADD, R2L_B1_TILE_EXACT, R2L_B1_TILE_RAGGED, R2L_B1_PLANES };
 // What a backward launches, decided from the shape of the call alone (r2l_bwd_plan): r2l_bwd_launch walks it, and
@@ -1024,11 +1036,13 @@ struct R2LBwdPlan {
   int hp_grid, hp_band;  // the HP pass alone
   int b2_grid, b2_band, b2_nmain;  // kernel B2: the tile kernel, or the sums pass (b2_nmain workgroups + R2L_B2S_HELPERS)
   int raw_grid, raw_band;          // the d/d raw gather pass
+  bool bnr;                        // train-mode BatchNorm's backward sums are recomputed from raw + Y' (r2l_bnr_planes_block)
+  int bnr_grid, bnr_band;          // ... instead of read back from the saved output (r2l_bn_bwd_reduce)
 };
 // grad_mask: the R2L_GRAD_* bits a caller of r2l_isp_step_bwd_select asks for, 0 = every parameter gradient; want_raw: d/d raw too.
 // The only reader of the backward's overrides of diagnostic builds (R2L_BWD_*, R2L_GRID_BWD*, the band heights).
-// io16: grad_out is bfloat16 / float16 (r2l_isp_step_bwd_io) -- read by the plane passes only, which such a call therefore
-// takes at every size, on the full route whatever the mask
+// io16: grad_out is bfloat16 / float16 or channels-last (r2l_isp_step_bwd_io, _layout) -- read by the plane passes only, which such
+// a call therefore takes at every size, on the full route whatever the mask
 static R2LBwdPlan r2l_bwd_plan(unsigned grad_mask, bool want_raw, int raw_u16, bool has_additive, bool epi_on,
                                bool keep_luma, int B, int H, int W, bool io16 = false) {
   R2LBwdPlan p = {};
@@ -1046,7 +1060,9 @@ static R2LBwdPlan r2l_bwd_plan(unsigned grad_mask, bool want_raw, int raw_u16, b
   // 110+, 64x256x256 (4.2 Mpx) 77.7 against 80.5 since the tails were shortened (profiles/r04_small.txt; round 3: 99 against 85,
   // and the threshold was 6 Mi px)
   // (d/d raw: the plane passes at every size -- the gather pass reads the planes they leave)
-  const bool planes = want_raw || r2l_bwd_planes_forced() || (size_t)B * H * W >= ((size_t)4 << 20);
+  // (R2L_BWD_PLANES of diagnostic builds: the plane passes, and the recomputing BatchNorm sums, below their pixel thresholds too)
+  const bool forced = r2l_env_int("R2L_BWD_PLANES", 0) != 0;
+  const bool planes = want_raw || forced || (size_t)B * H * W >= ((size_t)4 << 20);
   const bool b1_planes = p.saved && planes && (want_raw || !r2l_env_int("R2L_BWD1_TILED", 0));
   p.b2_planes = b1_planes && (want_raw || !r2l_env_int("R2L_BWD2_TILED", 0));
   // The reduced passes: the sums of the black level, white balance, colour matrix, debayer and sharpen gradients need the whole
@@ -1089,6 +1105,17 @@ static R2LBwdPlan r2l_bwd_plan(unsigned grad_mask, bool want_raw, int raw_u16, b
   if (want_raw_mask && p.b2_planes) {  // d/d raw from HP and the chroma gradient planes: one item per wavefront
     p.raw_band = band_rows(256L * 4 * R2L_BR_OCC, "R2L_BR_BAND");
     p.raw_grid = r2l_plane_grid(B, H, W, p.raw_band, R2L_BR_NWV, 0);
+  }
+  // BatchNorm's backward sums of a step whose forward kept Y' (R2L_F_KEEP_LUMA on the row-streaming path): recomputed from the raw
+  // frame and Y' on batches of >= 6 Mi px -- the forward's output is then not read at all by the backward
+  // (from 6 Mi px: at 64x256x256 = 4 Mi px the whole step, output included, lives in the memory-side cache and reading the output back
+  //  is cheaper than recomputing it -- bn_reduce 22.4-23.8 us against 27.1; at 128x256x256 37.2 against 37.5, the step 2 % faster)
+  // A 16-bit / channels-last cotangent is read by this pass only, at every size (without an epilogue)
+  p.bnr = keep_luma && r2l_fwd_streams(has_additive, W) && (io16 ? !epi_on : (forced || (size_t)B * H * W >= ((size_t)6 << 20)));
+  if (p.bnr) {
+    // (band height as kernel B1's: 36 rows at 64x512x512 -- 61.4 us against 63.2 at 24 rows, 71-73 at 12 / 18 / 30, 68.4 at 48)
+    p.bnr_band = band_rows(256L * 4 * 2, "R2L_BNR_BAND");
+    p.bnr_grid = r2l_plane_grid(B, H, W, p.bnr_band, R2L_BNR_NWV, r2l_env_int("R2L_GRID_BNR", R2L_MAX_BLOCKS));
   }
 #endif
   if (p.b1 != R2L_B1_PLANES) {
@@ -1174,6 +1201,21 @@ static int r2l_bwd_raw_pass(const R2LBwdCall& c, const R2LWorkspace& ws, const R
   if (r2l_plane_items(c.B, c.H, c.W, p.raw_band) > (1L << 30)) return r2l_fail(-1, "r2l_isp_step_bwd_raw: batch too large");
   const R2LRawGradArgs a{ws.folded, ws.hp, c.guv, c.grad_raw, c.B, c.H, c.W, p.raw_band};
   return r2l_launch_bwd_raw_plane(a, p.raw_grid, c.stream);
+}
+// phase A of a step's backward where p.bnr: the BatchNorm sums from raw + Y' + grad_out into the workspace (means: and their means)
+static int r2l_bwd_bnr_pass(const R2LBwdCall& c, const R2LWorkspace& ws, const R2LBwdPlan& p, float* means) {
+  if (r2l_plane_items(c.B, c.H, c.W, p.bnr_band) > (1L << 30)) return r2l_fail(-1, "r2l_isp_step_bwd: batch too large");
+  const R2LPass pass{p.bnr_band, (c.H + p.bnr_band - 1) / p.bnr_band, (int)r2l_plane_items(c.B, c.H, c.W, p.bnr_band), p.bnr_grid};
+  R2LBnrArgs a;
+  a.s = r2l_fwd_stream_args(c.raw, ws, ws.bn, c.B, c.H, c.W, pass, true);
+  a.s.yp_in = ws.yp;
+  a.s.ep = c.ep.on ? c.ep : R2LEpi{0, 0, 0, 0};
+  a.gout = c.gout;
+  a.sums = ws.bsums;
+  a.totals = ws.moments;
+  a.bn_bwd = means;
+  return r2l_bnr_table[c.io != R2L_IO_F32 ? R2L_PAIR_IO + r2l_io_slot(c.io) : (c.ep.on ? R2L_PAIR_EPI : R2L_PAIR_PLAIN)][c.raw.u16 ? 1 : 0](
+      a, p.bnr_grid, c.stream);
 }
 #endif
 // The launches of plan `p` = r2l_bwd_plan(this call), in order.  The workspace's folded weights and arrival counters are valid
@@ -1394,10 +1436,9 @@ static int r2l_isp_step_fwd_impl(const void* raw, int raw_u16, float denom, cons
   if (bn_mode == R2L_BN_TRAIN && phase != R2L_STEP_B) {
     // statistics pass; one rank: the last workgroup also does the BatchNorm bookkeeping
     R2LBnFinalizeArgs f{ws.stats, 1, ws.bn, ws.moments, running_mean, running_var, eps, momentum, num_batches_tracked};
-    if (int e = r2l_isp_fwd_impl(rw, ws.packed, additive, nullptr, nullptr, ws.stats, workspace, workspace_bytes, B, H,
-                                 W, R2L_F_STATS_ONLY | R2L_F_FOLDED_VALID | R2L_F_SPLIT_STATS | keep, stream,
-                                 phase == R2L_STEP_ALL ? &f : nullptr))
-      return e;
+    const R2LFwdCall c{rw, ws.packed, additive, nullptr, nullptr, ws.stats, phase == R2L_STEP_ALL ? &f : nullptr,
+                       R2LEpi{0, 0, 0, 0}, R2L_IO_F32, R2L_FWD_STATS_PASS, B, H, W, stream};
+    if (int e = r2l_isp_fwd_impl(c, R2L_F_STATS_ONLY | R2L_F_FOLDED_VALID | keep, workspace, workspace_bytes)) return e;
     if (phase == R2L_STEP_A) return 0;
   }
   if (phase == R2L_STEP_B) {
@@ -1407,9 +1448,9 @@ static int r2l_isp_step_fwd_impl(const void* raw, int raw_u16, float denom, cons
   }
   // (train mode: the statistics pass of this call -- or of phase A of this step -- has left Y' in the workspace wherever the
   // row-streaming forward runs, and the apply pass reads it)
-  return r2l_isp_fwd_impl(rw, ws.packed, additive, bn_mode == R2L_BN_NONE ? nullptr : ws.bn, out, nullptr, workspace,
-                          workspace_bytes, B, H, W,
-                          R2L_F_FOLDED_VALID | keep | (bn_mode == R2L_BN_TRAIN ? R2L_F_LUMA_VALID : 0), stream, nullptr, &ep, io);
+  const R2LFwdCall c{rw, ws.packed, additive, bn_mode == R2L_BN_NONE ? nullptr : ws.bn, out, nullptr, nullptr, ep, io,
+                     bn_mode == R2L_BN_TRAIN ? R2L_FWD_APPLY_PASS : R2L_FWD_WHOLE, B, H, W, stream};
+  return r2l_isp_fwd_impl(c, R2L_F_FOLDED_VALID | keep, workspace, workspace_bytes);
 }
 int r2l_isp_step_fwd(const void* raw, int raw_u16, float denom, const float* const* params_host,
                      const float* additive, int bn_mode, float* running_mean, float* running_var,
@@ -1420,66 +1461,6 @@ int r2l_isp_step_fwd(const void* raw, int raw_u16, float denom, const float* con
                                num_batches_tracked, eps, momentum, out, R2L_IO_F32, workspace, workspace_bytes, B, H, W, nranks,
                                phase, gathered_stats, stream);
 }
-// BatchNorm's backward sums of a step whose forward kept Y' (R2L_F_KEEP_LUMA on the row-streaming path): recomputed from the raw
-// frame and Y' (r2l_bnr_planes_block) on batches of >= 6 Mi px where the plane passes run -- the forward's output is then
-// not read at all by the backward.  Returns 1 when it did not run (the caller falls back to r2l_bn_bwd_reduce).
-// io: the type behind grad_out (R2L_IO_*); a 16-bit cotangent is read by this pass only, at every size.
-static int r2l_bn_bwd_reduce_planes(const R2LRaw& raw, const float* additive, const float* grad_out, const R2LWorkspace& ws,
-                                    const R2LEpi& ep, float* bn_bwd, int B, int H, int W, int keep, void* stream,
-                                    int io = R2L_IO_F32) {
-#ifdef R2L_SERIAL
-  (void)raw; (void)additive; (void)grad_out; (void)ws; (void)ep; (void)bn_bwd; (void)B; (void)H; (void)W; (void)keep; (void)stream;
-  (void)io;
-  return 1;
-#else
-  // (from 6 Mi px: at 64x256x256 = 4 Mi px the whole step, output included, lives in the memory-side cache and reading the output back
-  //  is cheaper than recomputing it -- bn_reduce 22.4-23.8 us against 27.1; at 128x256x256 37.2 against 37.5, the step 2 % faster)
-  const bool planes = io != R2L_IO_F32 || r2l_bwd_planes_forced() || (size_t)B * H * W >= ((size_t)6 << 20);
-  if (!keep || !r2l_fwd_streams(additive, W) || !planes) return 1;
-  if (io != R2L_IO_F32 && ep.on) return 1;
-  R2LBnrArgs a;
-  a.s.raw = raw;
-  a.s.F = ws.folded;
-  a.s.bn = ws.bn;
-  a.s.out = nullptr;
-  a.s.yp_out = nullptr;
-  a.s.yp_in = ws.yp;
-#ifdef R2L_EXP_STAMPS
-  a.s.tl = nullptr;
-#endif
-  a.s.stat_partial = ws.part_small;
-  a.s.B = B;
-  a.s.H = H;
-  a.s.W = W;
-  // (band height as kernel B1's: 36 rows at 64x512x512 -- 61.4 us against 63.2 at 24 rows, 71-73 at 12 / 18 / 30, 68.4 at 48)
-  a.s.band_h = r2l_band_rows(B, H, W, 256L * 4 * 2, "R2L_BNR_BAND");
-  a.s.nband = (H + a.s.band_h - 1) / a.s.band_h;
-  const long items = r2l_plane_items(B, H, W, a.s.band_h);
-  if (items > (1L << 30)) return r2l_fail(-1, "r2l_isp_step_bwd: batch too large");
-  a.s.nitems = (int)items;
-  a.s.tree = R2LTree{ws.part_small, nullptr, ws.gpartial, ws.counters, 12, 0};
-  a.s.stats_out = nullptr;
-  a.s.fin.bn = nullptr;
-  a.s.ep = ep.on ? ep : R2LEpi{0, 0, 0, 0};
-  a.gout = grad_out;
-  a.sums = ws.bsums;
-  a.totals = ws.moments;
-  a.bn_bwd = bn_bwd;
-  const int g = r2l_plane_grid(B, H, W, a.s.band_h, R2L_BNR_NWV, r2l_env_int("R2L_GRID_BNR", R2L_MAX_BLOCKS));
-  if (io != R2L_IO_F32) {
-    typedef int (*launch_t)(const R2LBnrArgs&, int, void*);
-    static const launch_t bnr_io[R2L_IO_SLOTS][2] = {{r2l_launch_bnr_planes_bf16, r2l_launch_bnr_planes_u16_bf16},
-                                                     {r2l_launch_bnr_planes_f16, r2l_launch_bnr_planes_u16_f16},
-                                                     {r2l_launch_bnr_planes_nhwc, r2l_launch_bnr_planes_u16_nhwc},
-                                                     {r2l_launch_bnr_planes_bf16_nhwc, r2l_launch_bnr_planes_u16_bf16_nhwc},
-                                                     {r2l_launch_bnr_planes_f16_nhwc, r2l_launch_bnr_planes_u16_f16_nhwc}};
-    return bnr_io[r2l_io_slot(io)][raw.u16 ? 1 : 0](a, g, stream);
-  }
-  return ep.on ? (raw.u16 ? r2l_launch_bnr_planes_epi_u16(a, g, stream) : r2l_launch_bnr_planes_epi(a, g, stream))
-               : (raw.u16 ? r2l_launch_bnr_planes_u16(a, g, stream) : r2l_launch_bnr_planes(a, g, stream));
-#endif
-}
-
 // r2l_isp_step_bwd, r2l_isp_step_bwd_raw and r2l_isp_step_bwd_select: one implementation, what they ask of it
 struct R2LStepBwd {
   const void* raw;
@@ -1524,13 +1505,23 @@ static int r2l_isp_step_bwd_impl(const R2LStepBwd& q) {
   if (q.workspace_bytes < ws.total) return r2l_fail(-2, "r2l_isp_step_bwd: workspace too small (r2l_isp_workspace_bytes)");
   const float* bn = q.bn_mode == R2L_BN_NONE ? nullptr : ws.bn;
   const float* bn_bwd = q.bn_mode == R2L_BN_TRAIN ? ws.bn_bwd : nullptr;
+  // the step's forward has folded the parameters (and kept Y', with R2L_STEP_KEEP_LUMA)
+  const R2LBwdCall c{rw, ws.packed, q.additive, bn, bn_bwd, q.grad_out, q.grad_params, q.grad_raw, q.guv, ep, q.grad_mask,
+                     B, H, W, q.stream, q.io};
+  const R2LBwdPlan p = r2l_bwd_plan(q.grad_mask, q.grad_raw != nullptr, q.raw_u16, q.additive != nullptr, ep.on != 0,
+                                    keep != 0, B, H, W, q.io != R2L_IO_F32);
   if (q.bn_mode == R2L_BN_TRAIN && phase != R2L_STEP_B) {
     float* means = phase == R2L_STEP_ALL ? ws.bn_bwd : nullptr;
-    int e = r2l_bn_bwd_reduce_planes(rw, q.additive, q.grad_out, ws, ep, means, B, H, W, keep, q.stream, q.io);
-    if (e == 1 && q.io != R2L_IO_F32)
+    if (!p.bnr && q.io != R2L_IO_F32)
       return r2l_fail(-3, "r2l_isp_step_bwd_io: internal: the BatchNorm sums of a 16-bit cotangent need the plane pass");
-    if (e == 1) e = r2l_bn_bwd_reduce(q.grad_out, q.out, ws.moments, ws.bsums, means, q.workspace, q.workspace_bytes, B, H, W,
-                                      R2L_F_FOLDED_VALID, q.stream);
+    int e;
+#ifndef R2L_SERIAL
+    if (p.bnr)
+      e = r2l_bwd_bnr_pass(c, ws, p, means);
+    else
+#endif
+      e = r2l_bn_bwd_reduce(q.grad_out, q.out, ws.moments, ws.bsums, means, q.workspace, q.workspace_bytes, B, H, W,
+                            R2L_F_FOLDED_VALID, q.stream);
     if (e) return e;
     if (phase == R2L_STEP_A) return 0;
   }
@@ -1538,13 +1529,9 @@ static int r2l_isp_step_bwd_impl(const R2LStepBwd& q) {
     R2LBnBwdMeansArgs m{q.gathered_sums, q.nranks, ws.moments + 6, ws.bn_bwd};
     if (int e = r2l_launch_bn_bwd_means(m, 1, q.stream)) return e;
   }
-  if (q.grad_params) {  // the step's forward has folded the parameters (and kept Y', with R2L_STEP_KEEP_LUMA)
+  if (q.grad_params) {
     if (q.additive && (H != 256 || W != 256))
       return r2l_fail(-1, "additive_layer is (1,3,256,256): needs 256x256 frames");
-    const R2LBwdCall c{rw, ws.packed, q.additive, bn, bn_bwd, q.grad_out, q.grad_params, q.grad_raw, q.guv, ep, q.grad_mask,
-                       B, H, W, q.stream, q.io};
-    const R2LBwdPlan p = r2l_bwd_plan(q.grad_mask, q.grad_raw != nullptr, q.raw_u16, q.additive != nullptr, ep.on != 0,
-                                      keep != 0, B, H, W, q.io != R2L_IO_F32);
     if (int e = r2l_bwd_launch(c, ws, p)) return e;
   }
   if (q.grad_additive) return r2l_additive_bwd(q.grad_out, q.out, bn, bn_bwd, q.grad_additive, B, H, W, q.stream);
@@ -2233,8 +2220,9 @@ static int r2l_static_fwd_impl(const R2LRaw& raw, float* out, int B, int H, int 
 int r2l_isp_fwd(const float* raw, const float* params, const float* additive,
                 const float* bn_mean_istd, float* out, double* stats, void* workspace,
                 size_t workspace_bytes, int B, int H, int W, int flags, void* stream) {
-  return r2l_isp_fwd_impl(r2l_raw_f32(raw), params, additive, bn_mean_istd, out, stats, workspace, workspace_bytes,
-                          B, H, W, flags & ~R2L_F_INTERNAL, stream);
+  return r2l_isp_fwd_impl(R2LFwdCall{r2l_raw_f32(raw), params, additive, bn_mean_istd, out, stats, nullptr, R2LEpi{0, 0, 0, 0},
+                                     R2L_IO_F32, R2L_FWD_WHOLE, B, H, W, stream},
+                          flags, workspace, workspace_bytes);
 }
 // statistics pass + BatchNorm bookkeeping in one launch (one rank: no exchange between the two)
 static int r2l_isp_fwd_stats_bn_impl(const R2LRaw& raw, const float* params, const float* additive, double* stats,
@@ -2245,8 +2233,9 @@ static int r2l_isp_fwd_stats_bn_impl(const R2LRaw& raw, const float* params, con
   if ((running_mean == nullptr) != (running_var == nullptr))
     return r2l_fail(-1, "r2l_isp_fwd_stats_bn: running_mean and running_var go together");
   R2LBnFinalizeArgs f{stats, 1, bn_mean_istd, moments, running_mean, running_var, eps, momentum, num_batches_tracked};
-  return r2l_isp_fwd_impl(raw, params, additive, nullptr, nullptr, stats, workspace, workspace_bytes, B, H, W,
-                          R2L_F_STATS_ONLY, stream, &f);
+  return r2l_isp_fwd_impl(R2LFwdCall{raw, params, additive, nullptr, nullptr, stats, &f, R2LEpi{0, 0, 0, 0}, R2L_IO_F32,
+                                     R2L_FWD_WHOLE, B, H, W, stream},
+                          R2L_F_STATS_ONLY, workspace, workspace_bytes);
 }
 int r2l_isp_fwd_stats_bn(const float* raw, const float* params, const float* additive, double* stats,
                          float* bn_mean_istd, double* moments, float* running_mean, float* running_var,
@@ -2267,8 +2256,9 @@ int r2l_isp_fwd_stats_bn_u16(const unsigned short* raw, float denom, const float
 int r2l_isp_fwd_u16(const unsigned short* raw, float denom, const float* params, const float* additive,
                     const float* bn_mean_istd, float* out, double* stats, void* workspace,
                     size_t workspace_bytes, int B, int H, int W, int flags, void* stream) {
-  return r2l_isp_fwd_impl(r2l_raw_u16(raw, denom), params, additive, bn_mean_istd, out, stats, workspace,
-                          workspace_bytes, B, H, W, flags & ~R2L_F_INTERNAL, stream);
+  return r2l_isp_fwd_impl(R2LFwdCall{r2l_raw_u16(raw, denom), params, additive, bn_mean_istd, out, stats, nullptr,
+                                     R2LEpi{0, 0, 0, 0}, R2L_IO_F32, R2L_FWD_WHOLE, B, H, W, stream},
+                          flags, workspace, workspace_bytes);
 }
 int r2l_isp_bwd(const float* raw, const float* params, const float* additive,
                 const float* bn_mean_istd, const float* bn_bwd, const float* grad_out,

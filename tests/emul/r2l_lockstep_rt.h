@@ -263,12 +263,18 @@ inline void fiber_main() {
 }
 extern "C" inline void r2l_ls_fiber_trampoline() { fiber_main(); }
 
+// A driver may watch the launches: the observer sees every launch's shape and argument block before its workgroups run, and its
+// return value says whether they run at all (false: a dry run, for drivers that record what a call WOULD launch)
+typedef bool (*Observer)(const char* name, int grid, int nt, size_t lds_floats, const void* kernarg);
+static Observer g_observer = nullptr;
+
 // Run `grid` workgroups of `nt` lanes one after the other: body(bid, lds) is the kernel's workgroup program, run by every lane
 // with threadIdx.x set.  lds_floats: the kernel's LDS size (a fresh, poisoned heap block per launch).
 template <class BODY>
 inline void launch(const char* name, int grid, int nt, size_t lds_floats, const void* kernarg, BODY&& body) {
   static std::mutex one_launch;
   std::lock_guard<std::mutex> hold(one_launch);
+  if (g_observer && !g_observer(name, grid, nt, lds_floats, kernarg)) return;
   Group g;
   g.name = name;
   g.nt = nt;
