@@ -542,6 +542,13 @@ static int r2l_env_int(const char* name, int dflt) {
 #else
 static inline int r2l_env_int(const char*, int dflt) { return dflt; }
 #endif
+// the flat grid-stride kernels (staged path, raw2rgb, the weak augmentation's permutation): min(computed grid, R2L_GRID_FLAT)
+// in diagnostic builds, so that their second and later passes run at small shapes; the computed grid in the product build
+static int r2l_flat_grid(size_t g) {
+  const size_t cap = (size_t)r2l_env_int("R2L_GRID_FLAT", 0x7fffffff);
+  if (g > cap) g = cap;
+  return g < 1 ? 1 : (int)g;
+}
 // persistent tile-walking kernels: at most `cap` workgroups (256 CUs x resident workgroups per CU),
 // a multiple of 8 when possible so that the XCD-grouped walk applies
 static int r2l_tile_grid(int ntiles, int cap) {
@@ -1725,7 +1732,7 @@ static int r2l_raw2rgb_fwd_impl(const R2LRaw& raw, const float* black_level, flo
   const size_t nitems = (size_t)B * (H / 2) * ((W + 3) / 4);
   size_t grid = (nitems + R2L_NT - 1) / R2L_NT;
   if (grid > 4096) grid = 4096;
-  return r2l_launch_raw2rgb_fwd(a, (int)grid, stream);
+  return r2l_launch_raw2rgb_fwd(a, r2l_flat_grid(grid), stream);
 }
 
 size_t r2l_raw2rgb_bwd_workspace_bytes(int B, int H, int W) {
@@ -1748,6 +1755,7 @@ int r2l_raw2rgb_bwd(const float* grad_out, float* grad_raw, double* grad_black_l
   const size_t nitems = (size_t)B * (H / 2) * ((W + 3) / 4);
   size_t grid = (nitems + R2L_NT - 1) / R2L_NT;
   if (grid > R2L_MAX_BLOCKS) grid = R2L_MAX_BLOCKS;
+  grid = (size_t)r2l_flat_grid(grid);
   if (int e = r2l_launch_raw2rgb_bwd(a, (int)grid, stream)) return e;
   if (grad_black_level) {
     R2LReduceRowsArgs r{(const float*)workspace, grad_black_level, (int)grid, 1.0, nullptr};
@@ -2376,11 +2384,14 @@ int r2l_static_fwd_io(const void* raw, int frames, float denom, void* out, int o
 // ---- staged (track_stages=True) entry points -------------------------------------------------------
 size_t r2l_stage_workspace_bytes(void) { return sizeof(float) * 81 * R2L_MAX_BLOCKS + 256; }
 
-static int r2l_stage_grid(int B, int H, int W, int per_thread) {
+static int r2l_stage_shares(int B, int H, int W, int per_thread) {  // the grid the shape asks for
   const size_t n = (size_t)B * H * W / per_thread;
   size_t g = (n + R2L_NT - 1) / R2L_NT;
   if (g > R2L_MAX_BLOCKS) g = R2L_MAX_BLOCKS;
   return g < 1 ? 1 : (int)g;
+}
+static int r2l_stage_grid(int B, int H, int W, int per_thread) {
+  return r2l_flat_grid((size_t)r2l_stage_shares(B, H, W, per_thread));
 }
 static int r2l_stage_finish(const float* partial, int nslots, int grid, float* out, void* stream) {
   R2LReduceRowsArgs r{partial, nullptr, grid, 1.0, out};
@@ -2447,10 +2458,10 @@ int r2l_stage_point(int op, const float* x, const float* g, const float* w, cons
   const bool reduces = (op == 3 || op == 7);
   if (reduces && (!sums6 || !workspace || workspace_bytes < r2l_stage_workspace_bytes()))
     return r2l_fail(-2, "r2l_stage_point: reduction needs sums + workspace");
-  const int grid = r2l_stage_grid(B, H, W * 3, 4);
-  R2LPointArgs a{x, g, w, aux, aux2, y, reduces ? (float*)workspace : nullptr, B, H, W, op};
+  const int shares = r2l_stage_shares(B, H, W * 3, 4), grid = r2l_stage_grid(B, H, W * 3, 4);
+  R2LPointArgs a{x, g, w, aux, aux2, y, reduces ? (float*)workspace : nullptr, B, H, W, op, shares};
   if (int e = r2l_launch_point(a, grid, stream)) return e;
-  return reduces ? r2l_stage_finish((const float*)workspace, 6, grid, sums6, stream) : 0;
+  return reduces ? r2l_stage_finish((const float*)workspace, 6, shares, sums6, stream) : 0;
 }
 
 // ---- augmentation after the ISP (utils/augmentation.py) -------------------------------------------------
@@ -2479,12 +2490,12 @@ int r2l_augment(const float* x, float* y, int N, int H, int W, int hflip, int vf
     t.ntc = (W + R2L_AUG_TS - 1) / R2L_AUG_TS;
     size_t nt = (size_t)N * t.ntr * t.ntc;
     if (nt > (size_t)1 << 30) return r2l_fail(-1, "r2l_augment: batch too large");
-    return r2l_launch_aug_tiled(t, (int)(nt < 4096 ? nt : 4096), stream);
+    return r2l_launch_aug_tiled(t, r2l_flat_grid(nt < 4096 ? nt : 4096), stream);
   }
   R2LAugArgs a{x, y, N, H, W, hflip != 0, vflip != 0, k & 3, inverse != 0};
   size_t g = ((size_t)N * H * W + R2L_NT - 1) / R2L_NT;
   if (g > 8192) g = 8192;
-  return r2l_launch_aug(a, (int)g, stream);
+  return r2l_launch_aug(a, r2l_flat_grid(g), stream);
 }
 int r2l_add_noise(const float* x, const float* noise, float std, float* y, size_t n, void* stream) {
   if (!x || !noise || !y || n == 0) return r2l_fail(-1, "r2l_add_noise: null pointer / empty");

@@ -264,16 +264,21 @@ struct R2LPointArgs {
   const float* aux;   // gamma bwd: forward output; bn bwd: forward output (xhat)
   const float* aux2;  // bn bwd: mean_g[3], mean_gxhat[3] or null (eval mode)
   float* y;
-  float* partial;
+  float* partial;  // [6][nv]
   int B, H, W, op;
+  int nv;  // shares of the work = rows of `partial`: the grid the shape alone asks for (the launch's grid unless a diagnostic build caps it)
 };
+// The elements are dealt to nv shares by the shape alone, and workgroup bid takes shares bid, bid + nblk, ...: the order in which
+// the sums of ops 3 and 7 are added -- and with the batch statistics everything behind train-mode BatchNorm -- does not depend on
+// how many workgroups run.  (Launched with nv workgroups, the product's case, every workgroup takes exactly one share.)
 R2L_BLOCKFN void r2l_point_block(const R2LPointArgs& a, int bid, int nblk, float* lds) {
   const size_t hw = (size_t)a.H * a.W, n4 = (size_t)a.B * 3 * hw / 4;  // hw is a multiple of 4
   R2L_TREG_DECL(R2LAccN<6>, regs);
+  for (int share = bid; share < a.nv; share += nblk) {
   R2L_PHASE_BEGIN
   R2L_PRAGMA_UNROLL
   for (int i = 0; i < 6; ++i) R2L_TREG(regs).acc[i] = 0.f;
-  for (size_t i4 = (size_t)bid * R2L_NT + tid; i4 < n4; i4 += (size_t)nblk * R2L_NT) {
+  for (size_t i4 = (size_t)share * R2L_NT + tid; i4 < n4; i4 += (size_t)a.nv * R2L_NT) {
     const size_t e = i4 * 4;
     const int c = (int)((e / hw) % 3);
     float xv[4] = {0, 0, 0, 0}, gv[4] = {0, 0, 0, 0}, av[4] = {0, 0, 0, 0}, o[4] = {0, 0, 0, 0};
@@ -322,7 +327,8 @@ R2L_BLOCKFN void r2l_point_block(const R2LPointArgs& a, int bid, int nblk, float
   }
   R2L_PHASE_END
   if (a.partial) {
-    R2L_BLOCK_REDUCE(6, regs, lds, a.partial, bid, nblk)
+    R2L_BLOCK_REDUCE(6, regs, lds, a.partial, share, a.nv)
+  }
   }
 }
 

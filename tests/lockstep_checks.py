@@ -2,7 +2,8 @@
 the parity checks of the GPU suite on host memory, served by tests/_build/libr2l_lockstep.so -- every kernel in its device form,
 one fiber per lane on a single host thread (one lane runs at a time: address and UB checks, no inter-lane races), built with -fsanitize=address,undefined (tests/emul/r2l_lockstep_rt.h).
 
-    python tests/lockstep_checks.py <library> [group ...]        groups: planes shapes stream passes static canary [fuzz]
+    python tests/lockstep_checks.py <library> [group ...]        groups: planes shapes stream passes static canary flat [fuzz]
+                                                                 (flat also runs wherever canary does)
 
 Prints one line per check; exit code 0 only if every check passed (AddressSanitizer aborts the process at the first bad access;
 UBSan reports are fatal through UBSAN_OPTIONS=halt_on_error=1)."""
@@ -25,6 +26,8 @@ PLANE_KERNELS = ('r2l_launch_bwd1_plane', 'r2l_launch_bwd2_sums')
 def main():
     lib_path = sys.argv[1]
     groups = set(sys.argv[2:]) or {'planes', 'shapes', 'stream', 'passes', 'static', 'canary'}
+    if 'canary' in groups:
+        groups.add('flat')
     emul_hook.enable(lib_path)
     lib = emul_hook.active()
     assert not lib.is_device
@@ -119,6 +122,20 @@ def main():
                     run(f'guard zones + poison, plane passes {H}x{W} u16={u16}',
                         lambda: ga.run_both('cpu', tc._step_bytes(2, H, W), tc._param_step('cpu', 2, H, W, True, u16, seed=50 + n,
                                                                                            kind='scene'), f'{H}x{W}'))
+    if 'flat' in groups:
+        # the flat grid-stride kernels under R2L_GRID_FLAT (the launch takes min(its own grid, the cap) workgroups): every lane of
+        # the stage-by-stage kernels, raw2rgb and the permutation walks several work items, the tiled permutation reuses its LDS tile
+        from oracle.golden_cases import PARAM_CASES
+        ragged = next(c for c in PARAM_CASES if c['name'] == 'drone_ragged_tile')
+        for cap in ((3,) if quick else pc.STAGED_MULTIPASS_CAPS):
+            with env(R2L_GRID_FLAT=cap):
+                run(f'stage-by-stage kernels, golden drone_ragged_tile, {cap} workgroups',
+                    lambda: pc.check_staged_case(ragged, golden, 'cpu'), ('r2l_launch_conv33_bwd', 'r2l_launch_pconv_bwd', 'r2l_launch_point'))
+        run('raw2rgb 3x70x134, forward and VJP, 1 workgroup' + ('' if quick else ' and 3'),
+            lambda: pc.check_raw2rgb_passes('cpu', 3, 70, 134, caps=(1,) if quick else (1, 3)), ('r2l_launch_raw2rgb_bwd',))
+        run('permutation kernels, 15 moves, forward and VJP, 1 workgroup' + ('' if quick else ' and 4'),
+            lambda: pc.check_permutation_shapes('cpu', planes=[(68, 132), (63, 65)] if quick else None, caps=(1,) if quick else (1, 4)),
+            ('r2l_launch_aug',))
     if 'fuzz' in groups:
         # random frame shapes and band heights for a time budget (not part of the default run: R2L_LOCKSTEP_FUZZ_S seconds, SEED):
         # the plane passes / streaming forward at shapes nobody listed, every access under ASan, every result against the oracle

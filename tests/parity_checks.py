@@ -1214,11 +1214,15 @@ def check_staged_case(case, golden, device):
     def flip(a, b, c):
         return max(np.abs(np.asarray(b) - np.asarray(a)).max(), np.abs(np.asarray(c) - np.asarray(a)).max())
     tol = out_tolerance(cache, case['bn'])
+    oerr, otol = np.abs(_sample(y.detach().cpu().numpy(), full) - g[pre + 'out']), 2 * _sample(tol, full)
+    ow = np.unravel_index((oerr / otol).argmax(), oerr.shape)
+    report(f'staged/{case["name"]}/out vs reference (golden, float32)', oerr[ow], otol[ow])
     assert np.all(np.abs(_sample(y.detach().cpu().numpy(), full) - g[pre + 'out']) <= 2 * _sample(tol, full))
     for k, st in m.stages.items():
         ref = g[pre + 'stage/' + k]
         got = _sample(st.detach().cpu().numpy(), full)
         lim = 2e-4 if k in ('gamma_correct', 'noise') else 2e-5
+        report(f'staged/{case["name"]}/stage {k} vs reference (golden)', np.abs(got - ref).max(), lim)
         assert np.abs(got - ref).max() <= lim, (k, np.abs(got - ref).max())
         if not case['track']:
             assert not st.retains_grad      # (:220-222: retain_grad only when track_stages)
@@ -1238,5 +1242,495 @@ def check_staged_case(case, golden, device):
         if k == 'additive_layer':
             got = _sample(got, full)
         e = np.abs(got - ref).max()
+        report(f'staged/{case["name"]}/grad {k} vs reference (golden, float32)', e,
+               2 * grad_rtol * (np.abs(ref).max() + 1e-6) + 2 * flip(o_nom[k], o_lo[k], o_hi[k]))
         assert e <= 2 * grad_rtol * (np.abs(ref).max() + 1e-6) + 2 * flip(o_nom[k], o_lo[k], o_hi[k]), \
             ('param grad', k, e)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# The flat grid-stride kernels past one grid pass: the stage-by-stage kernels (r2l_stage_*), raw2rgb, the weak
+# augmentation's permutation, and the static plane passes at frames that bracket their interior fast path.
+#
+# Each of these launches caps its grid (2048 / 4096 / 8192 workgroups of 512 lanes), so a lane takes a second work item only
+# on batches of more than a million pixels.  Two ways in: the shipped library on a batch that large, built as a PERIODIC batch
+# (a block of frames repeated R times: every block of every result must equal block 0 bit for bit, block 0 is held to the
+# float64 oracle of the block, the reductions to R x the oracle's); and R2L_GRID_FLAT on the diagnostic builds -- the launch
+# takes min(its own grid, R2L_GRID_FLAT) workgroups -- which runs the same loops at small shapes, on the host emulations too.
+# Every case runs inside the NaN-poisoned guarded arena (guarded_arena.py): an element a broken loop never wrote is NaN
+# afterwards, a store outside a buffer lands in a guard zone.
+# ------------------------------------------------------------------------------------------------------------------------
+FLAT_LANES = 512                 # R2L_NT
+STAGE_GRID_CAP = 2048            # R2L_MAX_BLOCKS: r2l_stage_grid, the raw2rgb backward
+RAW2RGB_FWD_GRID_CAP = 4096
+AUG_ELEMENTWISE_GRID_CAP = 8192
+
+
+def flat_cap(device, cap):
+    """context: R2L_GRID_FLAT = cap, served by the diagnostic builds; cap None: the launch's own grid (whatever library is loaded)"""
+    import contextlib
+    return env_overrides(device, {'R2L_GRID_FLAT': cap}) if cap else contextlib.nullcontext()
+
+
+class poisoned_arena:
+    """context: the device allocations of the wrappers (outputs, gradients, workspaces) and what the check places come out of one
+    NaN-poisoned arena with guard zones between the payloads (large_index_checks.guarded); on the way out every guard byte must
+    still hold the poison."""
+
+    def __init__(self, device, nbytes, what):
+        import large_index_checks as lc
+        self.lc, self.what = lc, what
+        self.cm = lc.guarded(device, int(nbytes))
+
+    def __enter__(self):
+        self.arena = self.cm.__enter__()
+        return self.arena
+
+    def __exit__(self, et, ev, tb):
+        try:
+            if et is None:
+                assert len(self.arena.blocks) >= 2, (self.what, 'the call allocated nothing from the arena')
+                self.lc.check_guard_zones(self.arena, self.what)
+        finally:
+            self.cm.__exit__(et, ev, tb)
+        return False
+
+
+def _bitwise_differing(a, b):
+    """how many elements of two host tensors of one shape differ in their bits (NaN == NaN)"""
+    ia = a.contiguous().view(torch.int32) if a.dtype == torch.float32 else a
+    ib = b.contiguous().view(torch.int32) if b.dtype == torch.float32 else b
+    return int((ia != ib).sum())
+
+
+# ---- B: the stage-by-stage kernels under a capped grid ----------------------------------------------------------------
+STAGED_MULTIPASS_CAPS = (1, 3, 8)
+_TRACKED = {}
+
+
+def staged_tracked_runs(device, bn, caps=STAGED_MULTIPASS_CAPS, B=2, H=70, W=134):
+    """A tracked run (track_stages=True, frames that require grad) of BxHxW frames under BatchNorm in mode `bn` ('train' / 'eval')
+    on the launch's own grid and under R2L_GRID_FLAT = cap, each inside the poisoned arena.  -> [(cap, name, differing elements,
+    max |difference|, scale of the own-grid result)] for the output, every stage, every stage gradient, d/d raw ('exact' names)
+    and the parameter gradients and running statistics ('grad ...', 'running_...').  Computed once per (device, bn)."""
+    key = (str(device), bn, tuple(caps), B, H, W)
+    if key in _TRACKED:
+        return _TRACKED[key]
+    raw_np = midtone_frames(B, H, W, seed=7)
+    cot_np = np.random.default_rng(8).standard_normal((B, 3, H, W)).astype(np.float32)
+    P = orc.IspParams(orc.DRONE_CAMERA_PARAMS, dtype=np.float32)
+    P.perturb(9, 0.01)
+    tcase = dict(camera='drone', track=True, additive=False, training=(bn == 'train'), bn=True)
+
+    def run(cap):
+        what = f'staged multipass tracked {B}x{H}x{W} bn={bn}, {cap or "own"} workgroups'
+        with poisoned_arena(device, 256 << 20, what) as arena, flat_cap(device, cap):
+            m = make_module(tcase, P, device)
+            raw, cot = arena.place(raw_np, 'raw').requires_grad_(True), arena.place(cot_np, 'cot')
+            y = m(raw)
+            y.backward(cot)
+            res = {'out': y.detach(), 'd/d raw': raw.grad}
+            for k, st in m.stages.items():
+                res['stage ' + k] = st.detach()
+                res['stage gradient ' + k] = st.grad
+            res.update({'grad ' + n: p.grad for n, p in m.named_parameters()})
+            res['running_mean'], res['running_var'] = m.batch_norm.running_mean, m.batch_norm.running_var
+            assert int(m.batch_norm.num_batches_tracked) == (1 if bn == 'train' else 0)
+            res = {k: v.detach().cpu().clone() for k, v in res.items()}
+        for k, v in res.items():
+            assert not bool(v.isnan().any()), (what, k, 'contains NaN: the poison reached a result')
+        return res
+    r0 = run(None)
+    assert len(r0) == 2 + 2 * 6 + 7 + 2, sorted(r0)
+    rows = []
+    for cap in caps:
+        r1 = run(cap)
+        rows += [(cap, k, _bitwise_differing(r1[k], r0[k]), float((r1[k] - r0[k]).abs().max()), float(r0[k].abs().max()))
+                 for k in r0]
+    _TRACKED[key] = rows
+    return rows
+
+
+def _reduced(name):
+    return name.startswith('grad ') or name.startswith('running_')
+
+
+def check_staged_multipass(golden, device, caps=STAGED_MULTIPASS_CAPS):
+    """r2l_stage_grid under R2L_GRID_FLAT: with 1, 3 or 8 workgroups every lane of r2l_conv33 / mix3 / pconv (K = 3, 5) /
+    point (ops 0-3 and 5-7: these cases have no additive layer, op 4, and no T.Normalize, op 8) walks several pixels and adds
+    them into its 81 / 25 / 9 / 6 reduction slots -- the regime the shipped library enters above 2^20 pixels.
+    (i) The golden case drone_ragged_tile (1x70x134) at check_staged_case's unchanged limits.
+    (ii) A tracked run of 2x70x134 frames under train-mode and under eval-mode BatchNorm against the same run on the launch's own
+    grid: the output, every stage, every stage gradient and d/d raw bit for bit, the reductions (parameter gradients, running
+    statistics) within check_grid_independence's 2e-4 of their scale.  Under train-mode BatchNorm the output and everything
+    behind it are functions of the batch statistics, sums over the batch: they are bit-identical because r2l_point_block deals
+    its elements to shares defined by the shape alone, whatever the number of workgroups that take them."""
+    from oracle.golden_cases import PARAM_CASES
+    case = next(c for c in PARAM_CASES if c['name'] == 'drone_ragged_tile')
+    for cap in caps:
+        with poisoned_arena(device, 256 << 20, f'staged multipass golden, {cap} workgroups'), flat_cap(device, cap):
+            check_staged_case(case, golden, device)
+    bad = []
+    for bn in ('train', 'eval'):
+        for cap, k, nd, d, sc in staged_tracked_runs(device, bn, caps):
+            pre = f'staged multipass/bn={bn}/{cap} workgroups/{k} vs the launch\'s own grid'
+            if _reduced(k):
+                report(pre, d, 2e-4 * (sc + 1e-6))
+                if not d <= 2e-4 * (sc + 1e-6):
+                    bad.append((bn, cap, k, d, sc))
+            else:
+                report(pre + ' (differing elements)', nd, 0.0)
+                if nd:
+                    bad.append((bn, cap, k, nd, d))
+    assert not bad, ('(BatchNorm mode, workgroups, tensor, differing elements or error, max |difference| or scale)', bad)
+
+
+# ---- C: the stage-by-stage kernels of the shipped library on 1.5 Mpx --------------------------------------------------
+def _staged_oracle_bn(bn):
+    """the oracle's BatchNorm argument for bn in 'none' / 'train' / 'eval' (fuzz_more.fuzz_staged's running statistics)"""
+    if bn == 'eval':
+        return dict(training=False, running_mean=np.array([0.3, 0.35, 0.4]), running_var=np.array([0.02, 0.03, 0.025]))
+    return dict(training=True, running_mean=np.zeros(3), running_var=np.ones(3)) if bn == 'train' else None
+
+
+def _staged_module(P, bn, device):
+    m = ppt.ParametrizedProcessing(orc.DRONE_CAMERA_PARAMS, track_stages=True, batch_norm_output=(bn != 'none'))
+    with torch.no_grad():
+        for k, v in P.by_name().items():
+            if k != 'additive_layer':
+                NAME2ATTR[k](m).copy_(torch.from_numpy(np.asarray(v)))
+        if bn == 'eval':
+            obn = _staged_oracle_bn(bn)
+            m.batch_norm.running_mean.copy_(torch.from_numpy(obn['running_mean']))
+            m.batch_norm.running_var.copy_(torch.from_numpy(obn['running_var']))
+    return m.to(device).train(bn == 'train')
+
+
+def staged_block_oracle(bn, Bb, H, W):
+    """the float64 oracle of the repeated block (tracked stages, stage gradients, d/d raw, parameter gradients and their
+    clip-flip spread) and the block's inputs; P is the float32 parameter set the module gets"""
+    n = ('none', 'train', 'eval').index(bn)
+    raw_b = midtone_frames(Bb, H, W, seed=60 + n)
+    cot_b = np.random.default_rng(80 + n).standard_normal((Bb, 3, H, W)).astype(np.float32)
+    P = orc.IspParams(orc.DRONE_CAMERA_PARAMS, dtype=np.float32)
+    P.perturb(70 + n, 0.01)
+    obn = _staged_oracle_bn(bn)
+    P64 = P.astype(np.float64)
+    out, stages, cache = orc.parametrized_forward(raw_b, P64, track_stages=True, bn=obn)
+    lo_hi = (float(cache['rgb'].min()), float(cache['rgb'].max()))
+    assert lo_hi[0] > 0.05 and lo_hi[1] < 0.95, lo_hi          # no pixel near a clip threshold (check_frame_shapes)
+    g, graw, sg = orc.parametrized_backward(P64, cache, cot_b, stage_grads=True)
+    glo, _, _ = orc.parametrized_backward(P64, cache, cot_b, clip_shift=1e-6)
+    ghi, _, _ = orc.parametrized_backward(P64, cache, cot_b, clip_shift=-1e-6)
+    flip = {k: max(np.abs(np.asarray(glo[k]) - np.asarray(g[k])).max(), np.abs(np.asarray(ghi[k]) - np.asarray(g[k])).max())
+            for k in g}
+    return dict(raw=raw_b, cot=cot_b, P=P, obn=obn, out=out, stages=stages, cache=cache, grads=g, grad_raw=graw,
+                stage_grads=sg, flip=flip)
+
+
+def check_staged_beyond_one_pass(device, bn, R=8, Bb=2, H=256, W=384):
+    """The shipped library's stage-by-stage kernels past their grid cap: a block of Bb frames of midtone_frames repeated R times
+    (R * Bb * H * W = 1 572 864 px: 3072 workgroups' worth for the stencil / matrix kernels, 2304 for the point kernels, both
+    capped at 2048 with a ragged second pass), a cotangent periodic in the same way, track_stages=True, frames that require
+    grad.  Every block of the output, of every stage, of every stage gradient and of d/d raw equals block 0 bit for bit; block 0
+    within fuzz_more.fuzz_staged's limits of the float64 oracle of the block (under train-mode BatchNorm the periodic batch has
+    the block's statistics); the parameter gradients within check_frame_shapes' limit of R x the block's oracle gradient."""
+    import large_index_checks as lc
+    px = R * Bb * H * W
+    assert px > STAGE_GRID_CAP * FLAT_LANES and 3 * px // 4 > STAGE_GRID_CAP * FLAT_LANES
+    assert px % (STAGE_GRID_CAP * FLAT_LANES) and (3 * px // 4) % (STAGE_GRID_CAP * FLAT_LANES)       # a ragged second pass
+    what = f'staged beyond one pass {R}x{Bb}x{H}x{W} bn={bn}'
+    o = staged_block_oracle(bn, Bb, H, W)
+    m = _staged_module(o['P'], bn, device)
+    nb = 12 * px                                   # bytes of one (B,3,H,W) float32 tensor
+    with poisoned_arena(device, lc.arena_bytes(*([nb] * 60 + [1 << 20] * 40)) + (512 << 20), what) as arena:
+        raw = arena.place(torch.from_numpy(o['raw']).to(device).repeat(R, 1, 1), 'raw').requires_grad_(True)
+        cot = arena.place(torch.from_numpy(o['cot']).to(device).repeat(R, 1, 1, 1), 'cot')
+        y = m(raw)
+        y.backward(cot)
+        ten = {'out': y.detach(), 'd/d raw': raw.grad}
+        for k, st in m.stages.items():
+            ten['stage ' + k], ten['stage gradient ' + k] = st.detach(), st.grad
+        assert len(ten) == 2 + 2 * 6, sorted(ten)
+        lo, hi = arena.buf.data_ptr(), arena.buf.data_ptr() + arena.nbytes
+        assert lo <= y.data_ptr() < hi and lo <= raw.grad.data_ptr() < hi, 'the results are not arena payloads'
+        for k, t in ten.items():
+            lc.assert_no_nan(t, f'{what}/{k}')
+            lc.assert_periodic(t, R, f'{what}/{k}')
+        block0 = {k: t[:Bb].cpu().numpy().astype(np.float64) for k, t in ten.items()}
+        grads = {k: NAME2ATTR[k](m).grad.detach().cpu().numpy().astype(np.float64) for k in o['grads']}
+        stats = None
+        if bn == 'train':
+            stats = (m.batch_norm.running_mean.cpu().numpy().astype(np.float64),
+                     m.batch_norm.running_var.cpu().numpy().astype(np.float64), int(m.batch_norm.num_batches_tracked))
+    # block 0 against the float64 oracle of the block, fuzz_staged's limits
+    istd = float(np.max(o['cache']['istd'])) if bn != 'none' else 1.0
+    failed = []
+
+    def hold(name, err, lim):
+        report(f'{what}/{name}', err, lim)
+        if not err <= lim:
+            failed.append((name, float(err), float(lim)))
+    hold('out block 0 vs float64 oracle', np.abs(block0['out'] - o['out']).max(), 2e-5 * istd)
+    for k in o['stages']:
+        hold(f'stage {k} block 0 vs float64 oracle', np.abs(block0['stage ' + k] - o['stages'][k]).max(), 2e-5)
+        sg = o['stage_grads'][k]
+        hold(f'stage gradient {k} block 0 vs float64 oracle', np.abs(block0['stage gradient ' + k] - sg).max(),
+             1e-4 * (np.abs(sg).max() + 1e-6))
+    hold('d/d raw block 0 vs float64 oracle', np.abs(block0['d/d raw'] - o['grad_raw']).max(),
+         1e-4 * (np.abs(o['grad_raw']).max() + 1e-6))
+    # the reductions: R x the block's oracle gradient, check_frame_shapes' limit (cot.size: the whole batch's)
+    cot_size = 3 * px
+    g32 = None
+    for k, og in o['grads'].items():
+        want = R * np.asarray(og, dtype=np.float64)
+        e = np.abs(grads[k].reshape(want.shape) - want).max()
+        lim = 3e-5 * (np.abs(want).max() + 1e-6) + 2 * R * o['flip'][k] + 7e-8 * np.sqrt(cot_size)
+        if bn == 'train':          # BatchNorm's backward cancels: float32 round-off of a sum of cot.size terms of size ~1
+            lim += 1e-7 * cot_size
+        if not e <= lim:
+            # the conditioning of the case, measured: the float32 oracle's own distance from the float64 one on the block --
+            # only where the float32 oracle misses the plain limit itself
+            if g32 is None:
+                P32 = o['P'].astype(np.float32)
+                _, _, c32 = orc.parametrized_forward(o['raw'], P32, track_stages=True, bn=_staged_oracle_bn(bn))
+                g32, _, _ = orc.parametrized_backward(P32, c32, o['cot'])
+            d32 = R * np.abs(np.asarray(g32[k], dtype=np.float64).reshape(want.shape) - want / R).max()
+            report(f'{what}/grad {k}: float32 oracle vs float64 oracle (x {R}), against the plain limit', d32, lim)
+            if d32 > lim:
+                lim += 2 * d32
+        hold(f'grad {k} vs {R} x float64 oracle of the block', e, lim)
+    if stats is not None:
+        x = o['cache']['pre_bn'].astype(np.float64)
+        mean, var = x.mean(axis=(0, 2, 3)), x.var(axis=(0, 2, 3))
+        for name, got, want in (('running_mean', stats[0], 0.1 * mean), ('running_var', stats[1], 0.9 + 0.1 * var * px / (px - 1))):
+            e, lim = np.abs(got - want), 1e-6 + 1e-5 * np.abs(want)       # (check_param_case: rtol 1e-5, atol 1e-6)
+            i = int((e / lim).argmax())
+            hold(f'{name} vs the oracle (unbiased factor of {px} px)', e[i], lim[i])
+        assert stats[2] == 1
+    assert not failed, (what, '(name, error, limit)', failed)
+
+
+# ---- D: raw2rgb past its grid caps ------------------------------------------------------------------------------------
+def raw2rgb_black_level_bound(B, H, W, cap, abs_sum, total):
+    """A-PRIORI bound of |grad_black_level - its float64 value| for one Bayer site, built like aux_checks.l2_sum_bound.  The
+    terms are the cotangent's own float32 values (g / 2 for the shared green of the 3-channel packed form: exact), so the only
+    roundings are the float32 additions on the longest path through r2l_raw2rgb_bwd_block,
+        2 T   acc -= g, twice (two quads) per trip of the lane's grid-stride loop, T = ceil(items / (grid * 512))
+        32    R2L_BLOCK_REDUCE: 32 sequential additions of a 16-lane group ...
+        16    ... and 16 of the lane that adds the group sums,
+    gamma_k = k u / (1 - k u) with u = 2^-24 times sum |term|; then the float64 additions of the workgroups' partials
+    (r2l_reduce_rows_block: at most grid + 48 of them, u64 = 2^-53) and the rounding of the float64 total to the float32 the
+    autograd function returns.  -> (bound, trips, grid)"""
+    items = B * (H // 2) * ((W + 3) // 4)
+    grid = min(-(-items // FLAT_LANES), STAGE_GRID_CAP, cap or STAGE_GRID_CAP)
+    trips = -(-items // (grid * FLAT_LANES))
+    k, u = 2 * trips + 32 + 16, 2.0 ** -24
+    k64, u64 = grid + 48, 2.0 ** -53
+    return (k * u / (1.0 - k * u) + k64 * u64 / (1.0 - k64 * u64)) * abs_sum + u * abs(total), trips, grid
+
+
+def check_raw2rgb_passes(device, Bb, H, W, R=1, caps=(None,), reduce_sizes=(False, True)):
+    """raw2rgb forward and VJP on a block of Bb frames repeated R times, under R2L_GRID_FLAT = cap (None: the launch's own grid):
+    float32 frames and 12-bit containers (raw2rgb_bits), reduce_size x out_channels, with and without a black level that requires
+    grad.  The output and d/d raw are periodic bit for bit and block 0 equals orc.raw2rgb / orc.raw2rgb_vjp bit for bit;
+    grad_black_level against R x the float64 sum over the block's cotangent within raw2rgb_black_level_bound."""
+    import large_index_checks as lc
+    rng = np.random.default_rng(H * W + Bb)
+    u = rng.integers(0, 4096, (Bb, H, W)).astype(np.uint16)
+    raw_np = u.astype(np.float32) / np.float32(4095)
+    bl_np = np.array([0.0625, 0.0626, 0.0625, 0.0626], dtype=np.float32)
+    B = Bb * R
+    sites = ((0, 0), (0, 1), (1, 0), (1, 1))
+    for rs in reduce_sizes:
+        for oc in (3, 4):
+            oshape = (Bb, oc, H // 2, W // 2) if rs else (Bb, oc, H, W)
+            cot_np = rng.standard_normal(oshape).astype(np.float32)
+            gr_ref, gbl_ref = orc.raw2rgb_vjp(cot_np, H, W, rs, oc)
+            assert gr_ref.dtype == np.float32
+            abs_sum = np.array([np.abs(gr_ref[:, a::2, b::2]).sum(dtype=np.float64) for a, b in sites])
+            refs = {False: orc.raw2rgb(raw_np, None, rs, oc), True: orc.raw2rgb(raw_np, bl_np, rs, oc)}
+            n_out = 4 * B * int(np.prod(oshape[1:]))
+            for use_bl in (False, True):
+                for frames in ('f32', 'u16'):
+                    if frames == 'u16' and W % 4:
+                        # the library's documented refusal (functional._raw_arg); 16-bit frames run at the W % 4 == 0 shape
+                        try:
+                            F_.raw2rgb_bits(torch.from_numpy(u.view(np.int16)).to(device), None, rs, oc, 12)
+                        except ValueError as e:
+                            assert '16-bit frames need W % 4 == 0' in str(e), str(e)
+                            continue
+                        raise AssertionError('16-bit frames of W % 4 != 0 must be refused')
+                    for cap in caps:
+                        what = f'raw2rgb {R}x{Bb}x{H}x{W} reduce_size={int(rs)} C={oc} bl={int(use_bl)} {frames}, ' \
+                               f'{cap or "own"} workgroups'
+                        need = lc.arena_bytes(4 * B * H * W, n_out, n_out, 4 * B * H * W, 1 << 16, 1 << 16, 1 << 16, 1 << 16)
+                        with poisoned_arena(device, need, what) as arena, flat_cap(device, cap):
+                            if frames == 'u16':
+                                raw = arena.place(torch.from_numpy(u.view(np.int16)).to(device).repeat(R, 1, 1), 'raw')
+                            else:
+                                raw = arena.place(torch.from_numpy(raw_np).to(device).repeat(R, 1, 1), 'raw').requires_grad_(True)
+                            cot = arena.place(torch.from_numpy(cot_np).to(device).repeat(R, 1, 1, 1), 'cot')
+                            bl = torch.from_numpy(bl_np).to(device).requires_grad_(True) if use_bl else None
+                            out = F_.raw2rgb_bits(raw, bl, rs, oc, 12 if frames == 'u16' else 16)
+                            if out.requires_grad:
+                                out.backward(cot)
+                            results = [('out', out.detach(), refs[use_bl])]
+                            if frames == 'f32':
+                                results.append(('d/d raw', raw.grad, gr_ref))
+                            for name, t, ref in results:
+                                lc.assert_no_nan(t, f'{what}/{name}')
+                                if R > 1:
+                                    lc.assert_periodic(t, R, f'{what}/{name}')
+                                nd = _bitwise_differing(t[:Bb].cpu(), torch.from_numpy(np.ascontiguousarray(ref, dtype=np.float32)))
+                                report(f'{what}/{name} block 0 vs the oracle (differing elements)', nd, 0.0)
+                                assert nd == 0, (what, name, nd)
+                            if use_bl:
+                                got = bl.grad.detach().cpu().numpy().astype(np.float64)
+                                for s in range(4):
+                                    want = R * gbl_ref[s]
+                                    bound, trips, grid = raw2rgb_black_level_bound(B, H, W, cap, R * abs_sum[s], want)
+                                    report(f'{what}/grad_black_level[{s}] vs {R} x float64 sum ({trips} trips of {grid} workgroups; '
+                                           f'rounding-count bound)', abs(got[s] - want), bound)
+                                    assert abs(got[s] - want) <= bound, (what, s, got[s], want, bound, trips, grid)
+                            del raw, cot, out, results
+
+
+def check_raw2rgb_multipass(device):
+    """the small form: 3x70x134 (a last item of one quad: W % 4 == 2; 16-bit frames are refused there) and 3x70x136 (16-bit
+    frames too) with 1 and 3 workgroups"""
+    check_raw2rgb_passes(device, 3, 70, 134, R=1, caps=(1, 3))
+    check_raw2rgb_passes(device, 3, 70, 136, R=1, caps=(1, 3))
+
+
+def check_raw2rgb_beyond_one_pass(device, reduce_size):
+    """the shipped library: a block of 4 frames of 512x512 repeated 18 times, 18.9 Mpx = 4608 workgroups' worth of items --
+    past the forward's 4096 and the backward's 2048, with a ragged last pass"""
+    Bb, H, W, R = 4, 512, 512, 18
+    items = R * Bb * (H // 2) * (W // 4)
+    assert items > RAW2RGB_FWD_GRID_CAP * FLAT_LANES and items % (RAW2RGB_FWD_GRID_CAP * FLAT_LANES) and \
+        items % (STAGE_GRID_CAP * FLAT_LANES)
+    check_raw2rgb_passes(device, Bb, H, W, R=R, reduce_sizes=(reduce_size,))
+
+
+# ---- E: the weak augmentation's permutation ----------------------------------------------------------------------------
+PERMUTATION_PLANES_TILED = [(68, 132), (132, 68), (64, 64), (60, 196), (4, 260), (128, 4), (72, 72), (64, 192), (196, 60)]
+PERMUTATION_PLANES_ELEMENTWISE = [(66, 130), (63, 65), (5, 4), (130, 6)]
+PERMUTATION_MOVES = [(h, v, k) for h in (False, True) for v in (False, True) for k in range(4) if h or v or k]
+
+
+def torch_flip_rot(x, hflip, vflip, k):
+    """what the reference composes (utils/augmentation.py:70-74)"""
+    if hflip:
+        x = x.flip(-1)
+    if vflip:
+        x = x.flip(-2)
+    return x.rot90(k, dims=(-1, -2))
+
+
+def check_permutation_shapes(device, planes=None, caps=(None, 1, 4)):
+    """aug.flip_rot forward and VJP (a cotangent of the output's shape) for all 15 non-identity (hflip, vflip, k) against
+    torch's flip / rot90 and autograd through them, bit for bit, on N = 3 planes: for the 16-byte tiled kernel
+    (r2l_aug_tiled_block, 64x64 LDS transpose for odd k) ragged tiles next to full ones, non-square multi-tile planes, one
+    partial tile, planes 4 wide / 4 high; for the element-wise kernel (r2l_aug_block) H or W no multiple of 4.  Again under
+    R2L_GRID_FLAT = 1 and 4: one workgroup then walks full and ragged tiles in turn, reusing its LDS tile."""
+    from raw2logit_amd import augmentation as aug
+    import large_index_checks as lc
+    assert len(PERMUTATION_MOVES) == 15
+    N = 3
+    for (H, W) in (planes or PERMUTATION_PLANES_TILED + PERMUTATION_PLANES_ELEMENTWISE):
+        tiled = H % 4 == 0 and W % 4 == 0
+        rng = np.random.default_rng(1000 * H + W)
+        x_np = rng.standard_normal((N, H, W)).astype(np.float32)
+        cot_np = {False: rng.standard_normal((N, H, W)).astype(np.float32), True: rng.standard_normal((N, W, H)).astype(np.float32)}
+        refs = {}
+        for mv in PERMUTATION_MOVES:
+            xr = torch.from_numpy(x_np).requires_grad_(True)
+            yr = torch_flip_rot(xr, *mv)
+            yr.backward(torch.from_numpy(cot_np[bool(mv[2] & 1)]))
+            refs[mv] = (yr.detach().contiguous(), xr.grad)
+        what = f'permutation/{"tiled" if tiled else "element-wise"} kernel {N}x{H}x{W}'
+        calls = 2 * len(caps) * len(PERMUTATION_MOVES)
+        worst = 0
+        with poisoned_arena(device, lc.arena_bytes(*([4 * N * H * W] * (calls + 3))), what) as arena:
+            x = arena.place(x_np, 'x')
+            cot = {odd: arena.place(c, 'cot') for odd, c in cot_np.items()}
+            for cap in caps:
+                with flat_cap(device, cap):
+                    for mv in PERMUTATION_MOVES:
+                        xg = x.detach().requires_grad_(True)
+                        y = aug.flip_rot(xg, *mv)
+                        y.backward(cot[bool(mv[2] & 1)])
+                        yr, gr = refs[mv]
+                        assert tuple(y.shape) == tuple(yr.shape), (what, mv, tuple(y.shape))
+                        nf, nb = _bitwise_differing(y.detach().cpu(), yr), _bitwise_differing(xg.grad.cpu(), gr)
+                        worst = max(worst, nf, nb)
+                        assert nf == 0 and nb == 0, (what, 'workgroups', cap or 'own', '(hflip, vflip, k)', mv,
+                                                     'differing elements forward / VJP', nf, nb)
+        report(f'{what}: 15 moves x forward, VJP x grids {[c or "own" for c in caps]} vs torch flip / rot90 (differing elements)',
+               worst, 0.0)
+
+
+def check_permutation_beyond_one_pass(device, shape=(6, 3, 510, 510), moves=((True, True, 3), (False, True, 2))):
+    """the element-wise kernel of the shipped library past its 8192-workgroup cap (4 194 304 elements): forward and VJP against
+    torch's flip / rot90 and autograd through them on the device, bit for bit"""
+    from raw2logit_amd import augmentation as aug
+    import large_index_checks as lc
+    n = int(np.prod(shape))
+    assert n > AUG_ELEMENTWISE_GRID_CAP * FLAT_LANES and (shape[-1] % 4 or shape[-2] % 4)
+    rng = np.random.default_rng(510)
+    x_np = rng.standard_normal(shape).astype(np.float32)
+    cot_np = rng.standard_normal(shape).astype(np.float32)          # (square planes: the output's shape)
+    what = f'permutation/element-wise kernel {shape} past one pass'
+    with poisoned_arena(device, lc.arena_bytes(*([4 * n] * (2 + 2 * len(moves)))), what) as arena:
+        x, cot = arena.place(x_np, 'x'), arena.place(cot_np, 'cot')
+        for mv in moves:
+            xg = x.detach().requires_grad_(True)
+            y = aug.flip_rot(xg, *mv)
+            y.backward(cot)
+            xr = x.detach().clone().requires_grad_(True)
+            yr = torch_flip_rot(xr, *mv)
+            yr.backward(cot)
+            nf = int((lc.bits(y.detach()) != lc.bits(yr.detach().contiguous())).sum())
+            nb = int((lc.bits(xg.grad) != lc.bits(xr.grad.contiguous())).sum())
+            report(f'{what} {mv}: forward vs torch (differing elements)', nf, 0.0)
+            report(f'{what} {mv}: VJP vs autograd through torch (differing elements)', nb, 0.0)
+            assert nf == 0 and nb == 0, (what, mv, nf, nb)
+
+
+# ---- F: the static plane passes and Menon2007 around the interior fast path --------------------------------------------------
+# r2l_plane_filter_block takes its two-pixel interior form where y >= r && y + r < H && x >= rx && x + 1 + rx < W (r = 1, 2, 4):
+# frames where that region is empty (4x4, 4x8: r = 2 and 4), one row high (6 rows: r = 2; 10 rows: r = 4), one pixel pair wide,
+# and the strip boundaries of FRAME_SHAPES_PLANES
+STATIC_PLANE_SHAPES = [(4, 4), (4, 8), (6, 80), (36, 256), (66, 132), (10, 260), (8, 516), (14, 1028)]
+STATIC_PLANE_CHAINS = [(('menon2007', 'none', 'none'), {}),
+                       (('menon2007', 'unsharp_masking', 'median_denoising'), {}),
+                       (('malvar2004', 'unsharp_masking', 'median_denoising'), {}),
+                       (('bilinear', 'sharpening_filter', 'median_denoising'), {'median_kernel_size': 5}),
+                       (('malvar2004', 'none', 'gaussian_denoising'), {}),
+                       (('bilinear', 'unsharp_masking', 'fft_denoising'), {})]
+assert all(s in FRAME_SHAPES_PLANES for s in STATIC_PLANE_SHAPES)
+
+
+def check_static_plane_shapes(device, shapes=None, chains=None, B=2):
+    """F_.static_pipeline against orc.static_batch at the project's 1e-5 on float32 frames, the 12-bit containers bit-identical to
+    them (as check_static_combinations), at the frame shapes that bracket the plane passes' fast-path bounds.  Malvar2004 frames
+    are raised to at least 6x8 (fuzz_more.fuzz_static).  No chain of the list is refused at these shapes (every W % 4 == 0)."""
+    cam = orc.DRONE_CAMERA_PARAMS
+    for (H0, W0) in (shapes or STATIC_PLANE_SHAPES):
+        for (deb, sh, dn), opts in (chains or STATIC_PLANE_CHAINS):
+            H, W = (max(H0, 6), max(W0, 8)) if deb == 'malvar2004' else (H0, W0)
+            u = np.random.default_rng(1000 * H + W).integers(0, 4096, (B, H, W)).astype(np.uint16)
+            raw_np = u.astype(np.float32) / np.float32(4095)
+            ref = orc.static_batch(raw_np, cam, deb, sh, dn, **opts)
+            what = f'static plane shapes/{deb}|{sh}|{dn}{"|" + str(opts) if opts else ""} {B}x{H}x{W}'
+            with poisoned_arena(device, (32 << 20) + 2 * 128 * B * H * W, what) as arena:
+                out = F_.static_pipeline(arena.place(raw_np, 'raw'), cam, deb, sh, dn, **opts)
+                out16 = F_.static_pipeline(arena.place(u.view(np.int16), 'u16'), cam, deb, sh, dn, bits=12, **opts)
+                out, out16 = out.cpu(), out16.cpu()
+            err = np.abs(out.numpy() - ref)
+            report(what, err.max(), 1e-5)
+            assert err.max() <= 1e-5, (what, err.max(), np.unravel_index(err.argmax(), err.shape))     # (NaN fails this too)
+            nd = _bitwise_differing(out16, out)
+            report(what + '/12-bit containers vs float32 frames (differing elements)', nd, 0.0)
+            assert nd == 0, (what, '12-bit containers differ from the float32 frames', nd)

@@ -114,3 +114,22 @@ def test_tile_walk_covers_every_tile_once_in_even_shares(emulation):
                 counts = np.bincount(owner, minlength=nblk)
                 assert counts.min() == counts.max() == 8
                 assert most == counts.max()
+
+
+# ---- the flat grid-stride kernels past one grid pass (R2L_GRID_FLAT: min(computed grid, cap)) and the shapes around them ----
+def test_staged_kernels_walk_several_pixels_per_lane(golden, emulation):
+    pc.check_staged_multipass(golden, 'cpu')
+
+
+def test_raw2rgb_walks_several_items_per_lane(emulation):
+    pc.check_raw2rgb_multipass('cpu')
+
+
+def test_permutation_shapes(emulation):
+    pc.check_permutation_shapes('cpu')
+
+
+@pytest.mark.parametrize('shapes', [pc.STATIC_PLANE_SHAPES[:4], pc.STATIC_PLANE_SHAPES[4:]], ids=['first-four', 'last-four'])
+@pytest.mark.parametrize('chain', pc.STATIC_PLANE_CHAINS, ids=['|'.join(c) + ('|5x5' if o else '') for c, o in pc.STATIC_PLANE_CHAINS])
+def test_static_plane_pass_shapes_around_the_fast_path(chain, shapes, emulation):
+    pc.check_static_plane_shapes('cpu', shapes=shapes, chains=[chain])

@@ -980,3 +980,61 @@ def test_fused_forward_streaming_kernel(shape, dev):
         e2 = (y - yt).abs().max().item()
         pc.report(f'fwd-stream/{shape}/bn={bn}/streaming vs tile kernel', e2, 2e-5 * (float(c['istd'].max()) if bn else 1.0))
         assert e2 <= 2e-5 * (float(c['istd'].max()) if bn else 1.0), (shape, bn, e2)
+
+
+# ---- the flat grid-stride kernels past one grid pass: stage-by-stage kernels, raw2rgb, the permutation; the static plane
+# passes around their interior fast path (tests/parity_checks.py; every case inside the NaN-poisoned guarded arena) -----------
+def test_staged_kernels_walk_several_pixels_per_lane(golden, dev):
+    """diagnostic build, R2L_GRID_FLAT = 1, 3, 8"""
+    pc.check_staged_multipass(golden, dev)
+
+
+@pytest.mark.parametrize('bn', ['none', 'train', 'eval'])
+def test_staged_kernels_beyond_one_grid_pass(bn, dev):
+    """the shipped library on 16x256x384 = 1.5 Mpx: r2l_stage_grid capped at 2048 workgroups, a ragged second pass"""
+    from raw2logit_amd import _lib
+    lib = _lib.device_library()
+    assert lib.path == _lib.LIB_PATH
+    _, names = pc.kernels_launched(lib, lambda: pc.check_staged_beyond_one_pass(dev, bn))
+    for k in ('conv33_fwd', 'conv33_bwd', 'mix3_fwd', 'mix3_bwd', 'pconv_fwd', 'pconv_bwd', 'point', 'raw2rgb_fwd', 'raw2rgb_bwd'):
+        assert any(n.startswith('r2l_launch_' + k) for n in names), (k, sorted(names))
+
+
+def test_raw2rgb_walks_several_items_per_lane(dev):
+    """diagnostic build, R2L_GRID_FLAT = 1, 3"""
+    pc.check_raw2rgb_multipass(dev)
+
+
+@pytest.mark.parametrize('reduce_size', [False, True])
+def test_raw2rgb_beyond_one_grid_pass(reduce_size, dev):
+    """the shipped library on 72x512x512 = 18.9 Mpx: past the forward's 4096 and the backward's 2048 workgroups"""
+    from raw2logit_amd import _lib
+    assert _lib.device_library().path == _lib.LIB_PATH
+    pc.check_raw2rgb_beyond_one_pass(dev, reduce_size)
+
+
+def test_permutation_shapes(dev):
+    pc.check_permutation_shapes(dev)
+
+
+def test_permutation_element_wise_kernel_beyond_one_grid_pass(dev):
+    from raw2logit_amd import _lib
+    lib = _lib.device_library()
+    assert lib.path == _lib.LIB_PATH
+    _, names = pc.kernels_launched(lib, lambda: pc.check_permutation_beyond_one_pass(dev))
+    assert names.get('r2l_launch_aug_kernel', 0) == 4 and not any('aug_tiled' in n for n in names), sorted(names)
+
+
+@pytest.mark.parametrize('shapes', [pc.STATIC_PLANE_SHAPES[:4], pc.STATIC_PLANE_SHAPES[4:]], ids=['first-four', 'last-four'])
+@pytest.mark.parametrize('chain', pc.STATIC_PLANE_CHAINS, ids=['|'.join(c) + ('|5x5' if o else '') for c, o in pc.STATIC_PLANE_CHAINS])
+def test_static_plane_pass_shapes_around_the_fast_path(chain, shapes, dev):
+    from raw2logit_amd import _lib
+    _, names = pc.kernels_launched(_lib.device_library(), lambda: pc.check_static_plane_shapes(dev, shapes=shapes, chains=[chain]))
+    # On the GPU (malvar2004, unsharp_masking, 3x3 median) and (malvar2004, none, gaussian) run as the row-streaming luma-chain
+    # kernel wherever it takes the frame (nothing is required of them here): the plane filter's unsharp / 3x3-median / 5x5-median / fft-neighbour forms (reach 1, 2, 4) are reached through the
+    # Menon2007, 5x5-median and fft chains, its gaussian form on the serial emulation only (tests/test_emul_parity.py)
+    (deb, sh, dn), opts = chain
+    plane_passes = (deb == 'menon2007' and sh != 'none') or dn == 'fft_denoising' or bool(opts)
+    want = [k for k, on in (('r2l_launch_static_menon', deb == 'menon2007'), ('r2l_launch_plane_filter', plane_passes)) if on]
+    for k in want:
+        assert any(n.startswith(k) for n in names), (k, sorted(names))
