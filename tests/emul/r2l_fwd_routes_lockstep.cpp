@@ -1,7 +1,7 @@
-// r2l_fwd_routes_lockstep.cpp -- stand-alone driver (own main, no Python) that writes down what the host route of the training
-// step's forward (and of the backward's recomputing BatchNorm-sums pass) does: one text line per call of the C ABI, on the
-// lock-step emulation's sources (r2l_lockstep.cpp, unchanged) compiled into one program with -fsanitize=address,undefined.
-// TEST INFRASTRUCTURE: built and run by tests/test_fwd_routes.py, which compares the output line by line with
+// r2l_fwd_routes_lockstep.cpp -- driver `fwd_routes` of r2l_lockstep_drivers.cpp (stand-alone, no Python) that writes down what the
+// host route of the training step's forward (and of the backward's recomputing BatchNorm-sums pass) does: one text line per call
+// of the C ABI, on the lock-step emulation's sources (r2l_lockstep.cpp, unchanged) under -fsanitize=address,undefined.
+// TEST INFRASTRUCTURE: run by tests/test_fwd_routes.py, which compares the output line by line with
 // tests/golden/fwd_routes.txt (tests/README.md: how that file is regenerated).  Every launch is seen through the observer of
 // r2l_ls::launch, which decodes the kernel's argument block:
 //   P  plans, dry (the observer lets no workgroup run; every pointer is a made-up address that nothing dereferences): the full
@@ -13,32 +13,10 @@
 //      Its workspace is a malloc block of EXACTLY r2l_isp_workspace_bytes, `out` EXACTLY 3 B H W elements
 //   S  the same call with one byte less of workspace
 //   X  calls that fail before a launch
-//   usage: r2l_fwd_routes_lockstep
-#define R2L_TEST_HOOKS 1
-#include "r2l_lockstep.cpp"
+//   usage: r2l_lockstep_drivers fwd_routes
+namespace r2l_drv::fwd_routes {
 
-#include <stdio.h>
-
-#include <map>
-#include <vector>
-
-static unsigned lcg_state = 24680u;
-static float lcg01() {
-  lcg_state = lcg_state * 1664525u + 1013904223u;
-  return (float)(lcg_state >> 8) * (1.0f / 16777216.0f);
-}
-struct Block {  // (malloc, not new[]: no cookie in front, the block ends at its last byte)
-  char* p;
-  size_t n;
-  explicit Block(size_t n_, int fill = 0xff) : p((char*)malloc(n_ ? n_ : 1)), n(n_) { memset(p, fill, n_); }
-  ~Block() { free(p); }
-  Block(const Block&) = delete;
-};
-static unsigned long long fnv1a(const void* p, size_t n) {
-  unsigned long long h = 1469598103934665603ull;
-  for (size_t i = 0; i < n; ++i) h = (h ^ ((const unsigned char*)p)[i]) * 1099511628211ull;
-  return h;
-}
+static Lcg lcg01{24680u};
 static int failures = 0;
 
 // ---- the packed parameters: the drone camera, a bilinear debayer, the reference's sharpening and blur kernels ----------------
@@ -61,9 +39,7 @@ static void make_params() {
   const float m2[9] = {1.f, 0.f, 1.13988303f, 1.f, -0.394642334f, -0.58062185f, 1.f, 2.03206185f, 0.f};
   memcpy(P + R2L_P_M_RGB2YUV, m1, sizeof m1);
   memcpy(P + R2L_P_M_YUV2RGB, m2, sizeof m2);
-  static const int off[9] = {R2L_P_BLACK_LEVEL, R2L_P_WHITE_BALANCE, R2L_P_CCM, R2L_P_GAMMA, R2L_P_DEBAYER, R2L_P_SHARPEN,
-                             R2L_P_BLUR, R2L_P_M_RGB2YUV, R2L_P_M_YUV2RGB};
-  for (int i = 0; i < 9; ++i) TABLE[i] = P + off[i];
+  param_table(P, TABLE);
 }
 
 // ---- the observer: every launch as text -------------------------------------------------------------------------------------
@@ -140,9 +116,7 @@ static void begin_call(int B, int H, int W) {
   call_B = B, call_H = H, call_W = W;
   luma_offset = r2l_isp_step_offset(R2L_STEP_LUMA, B, H, W);
   launches.clear();
-  std::lock_guard<std::mutex> g(r2l_ls_record_mutex);
-  r2l_ls_record.clear();
-  r2l_ls_record_on = true;
+  record_begin();
 }
 static std::string end_call_record() {
   r2l_ls_record_on = false;
@@ -383,11 +357,7 @@ static void run(const Run& q) {
   const int B = q.B, H = q.H, W = q.W;
   const size_t px = (size_t)B * H * W, esz = q.io == R2L_IO_F32 ? 4 : 2, nws = r2l_isp_workspace_bytes(B, H, W);
   Block raw(px * (q.u16 ? 2 : 4)), add(q.additive ? 3 * 256 * 256 * 4 : 0), cot(3 * px * esz);
-  for (size_t i = 0; i < px; ++i) {  // values below the black level, inside, and (after white balance) above the clip
-    const float v = 0.02f + 0.9f * lcg01();
-    if (q.u16) ((unsigned short*)raw.p)[i] = (unsigned short)(v * 65535.f);
-    else ((float*)raw.p)[i] = v;
-  }
+  fill_raw(lcg01, raw.p, px, q.u16, 0.02f, 0.9f);  // values below the black level, inside, and (after white balance) above the clip
   for (size_t i = 0; i < add.n / 4; ++i) ((float*)add.p)[i] = 0.1f * (lcg01() - 0.5f);
   for (size_t i = 0; i < 3 * px; ++i) {
     const float g = 2.f * lcg01() - 1.f;
@@ -737,7 +707,7 @@ static void refusals() {
   too_large();
 }
 
-int main() {
+int run(int, char**) {
   static const char* const OVERRIDES[13][2] = {{"R2L_FWD_TILED", "1"},        {"R2L_FORCE_SPLIT", "1"},      {"R2L_FWD_APPLY_RECOMPUTE", "1"},
                                                {"R2L_FWD_STATS_SPLIT", "1"},  {"R2L_FWD_STATS_STREAM", "1"}, {"R2L_FS_BAND", "32"},
                                                {"R2L_FL_BAND", "12"},         {"R2L_FST_BAND", "12"},        {"R2L_FA_BAND", "12"},
@@ -771,3 +741,6 @@ int main() {
   fflush(stdout);
   return failures ? 1 : 0;
 }
+#undef BAD
+
+}  // namespace r2l_drv::fwd_routes

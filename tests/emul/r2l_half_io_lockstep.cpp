@@ -1,51 +1,22 @@
-// r2l_half_io_lockstep.cpp -- stand-alone driver (own main, no Python) of the 16-bit output / cotangent kernels in their DEVICE
-// forms on the CPU: the lock-step emulation's sources (r2l_lockstep.cpp, unchanged) compiled into one program with
-// -fsanitize=address,undefined.  TEST INFRASTRUCTURE: built and run by tests/test_half_io.py.
+// r2l_half_io_lockstep.cpp -- driver `half_io` of r2l_lockstep_drivers.cpp (stand-alone, no Python) of the 16-bit output / cotangent
+// kernels in their DEVICE forms on the CPU: the lock-step emulation's sources (r2l_lockstep.cpp, unchanged) under
+// -fsanitize=address,undefined.  TEST INFRASTRUCTURE: run by tests/test_half_io.py.
 // Every buffer is a heap block of exactly the size the C ABI asks for, so an access past a 2-byte tensor is an ASan report.  The
 // 16-bit calls are compared bit for bit with the io = R2L_IO_F32 calls of the same build: out16 = narrow(out32), and the gradients of
 // the widened cotangent on the plane route (R2L_BWD_PLANES: the float32 calls take the plane passes at these sizes too).
-//   usage: r2l_half_io_lockstep params.bin     (150 float32: the packed parameter block, R2L_P_* order)
-#define R2L_TEST_HOOKS 1
-#include "r2l_lockstep.cpp"
+//   usage: r2l_lockstep_drivers half_io params.bin     (150 float32: the packed parameter block, R2L_P_* order)
+namespace r2l_drv::half_io {
 
-#include <stdio.h>
-
-static unsigned lcg_state = 12345u;
-static float lcg01() {
-  lcg_state = lcg_state * 1664525u + 1013904223u;
-  return (float)(lcg_state >> 8) * (1.0f / 16777216.0f);
-}
-template <class T>
-struct Buf {  // (malloc, not new[]: no cookie in front, the block ends at its last element)
-  T* p;
-  size_t n;
-  explicit Buf(size_t n_) : p((T*)malloc(n_ * sizeof(T) ? n_ * sizeof(T) : 1)), n(n_) { memset(p, 0xff, n_ * sizeof(T)); }
-  ~Buf() { free(p); }
-};
-#define CHECK(call)                                                                   \
-  do {                                                                                \
-    const int e_ = (call);                                                            \
-    if (e_) {                                                                         \
-      fprintf(stderr, "%s -> %d: %s\n", #call, e_, r2l_last_error());                 \
-      return 1;                                                                       \
-    }                                                                                 \
-  } while (0)
+static Lcg lcg01{12345u};
 
 static int run_case(const float* P, int B, int H, int W, int bn_mode, int io, int raw_u16) {
   const size_t px = (size_t)B * H * W, nws = r2l_isp_workspace_bytes(B, H, W);
   const int phase = R2L_STEP_ALL | R2L_STEP_KEEP_LUMA;
-  static const int off[9] = {R2L_P_BLACK_LEVEL, R2L_P_WHITE_BALANCE, R2L_P_CCM, R2L_P_GAMMA, R2L_P_DEBAYER, R2L_P_SHARPEN,
-                             R2L_P_BLUR, R2L_P_M_RGB2YUV, R2L_P_M_YUV2RGB};
   const float* table[9];
-  for (int i = 0; i < 9; ++i) table[i] = P + off[i];
-  Buf<float> rawf(raw_u16 ? 0 : px);
-  Buf<unsigned short> rawu(raw_u16 ? px : 0);
-  for (size_t i = 0; i < px; ++i) {
-    const float v = 0.15f + 0.7f * lcg01();
-    if (raw_u16) rawu.p[i] = (unsigned short)(v * 65535.f);
-    else rawf.p[i] = v;
-  }
-  const void* raw = raw_u16 ? (const void*)rawu.p : (const void*)rawf.p;
+  param_table(P, table);
+  Block rawb(px * raw_bytes(raw_u16));
+  fill_raw(lcg01, rawb.p, px, raw_u16, 0.15f, 0.7f);
+  const void* raw = rawb.p;
   if (r2l_isp_io_supported(io, raw_u16, 0, B, H, W, phase) != 1) return fprintf(stderr, "not supported?\n"), 1;
   Buf<char> ws32(nws), ws16(nws);
   Buf<float> out32(3 * px), cot32(3 * px), gp32(R2L_P_NTRAIN), gp16(R2L_P_NTRAIN), gr32(raw_u16 ? 0 : px), gr16(raw_u16 ? 0 : px);
@@ -88,13 +59,10 @@ static int run_case(const float* P, int B, int H, int W, int bn_mode, int io, in
   return bad ? 1 : 0;
 }
 
-int main(int argc, char** argv) {
-  if (argc != 2) return 2;
-  setenv("R2L_BWD_PLANES", "1", 1);
+int run(int argc, char** argv) {
   float P[R2L_P_COUNT];
-  FILE* f = fopen(argv[1], "rb");
-  if (!f || fread(P, sizeof(float), R2L_P_COUNT, f) != R2L_P_COUNT) return 2;
-  fclose(f);
+  if (argc != 2 || !read_params(argv[1], P)) return 2;
+  setenv("R2L_BWD_PLANES", "1", 1);
   static const int shapes[3][3] = {{2, 4, 4}, {2, 4, 260}, {1, 70, 260}};
   int rc = 0, n = 0;
   for (const auto& s : shapes)
@@ -118,3 +86,5 @@ int main(int argc, char** argv) {
   }
   return rc;
 }
+
+}  // namespace r2l_drv::half_io

@@ -1,29 +1,22 @@
-// r2l_limits_lockstep.cpp -- stand-alone driver (own main, no Python): the refusals at the documented size limits, on the lock-step
-// emulation's sources (r2l_lockstep.cpp, unchanged: the device's host route) compiled into one program with
-// -fsanitize=address,undefined.  TEST INFRASTRUCTURE: built and run by tests/test_large_index.py, which reads the lines
+// r2l_limits_lockstep.cpp -- driver `limits` of r2l_lockstep_drivers.cpp (stand-alone, no Python): the refusals at the documented
+// size limits, on the lock-step emulation's sources (r2l_lockstep.cpp, unchanged: the device's host route) under
+// -fsanitize=address,undefined.  TEST INFRASTRUCTURE: run by tests/test_large_index.py, which reads the lines
 //   <tag> -> <code> [<error text>]
 // Every call here must fail BEFORE the launch that would use the sizes it names: the frames, outputs and cotangents are blocks of a
 // few bytes and the workspace holds only its fixed head (the parameter fold of a step's forward runs, in that head), so a missed
 // refusal is an ASan report, not a pass.  Never run these shapes on a GPU.
-//   usage: r2l_limits_lockstep
-#define R2L_TEST_HOOKS 1
-#include "r2l_lockstep.cpp"
-
-#include <stdio.h>
-
-static const double CAMERA[16] = {0.0625,      0.0626,      0.0625,      0.0626,     2.86653646,  1.,          1.73079425, 1.50768983,
-                                  -0.33571374, -0.17197604, -0.23048614, 1.70698738, -0.47650126, -0.03119153, -0.32803956, 1.35923111};
+//   usage: r2l_lockstep_drivers limits
+namespace r2l_drv::limits {
 
 static void line(const char* tag, int e) { printf("%s -> %d [%s]\n", tag, e, e ? r2l_last_error() : ""); }
 
-int main() {
+int run(int, char**) {
   const size_t head = r2l_isp_workspace_bytes(1, 4, 4);  // more than the shape-independent head of any workspace
   std::vector<char> ws(head, 0), small(4096, 0);
   std::vector<float> params(256, 0.5f), grad(R2L_P_NTRAIN, 0.f), rm(3, 0.f), rv(3, 1.f);
   long long nbt = 0;
-  const int at[9] = {0, 4, 7, 16, 17, 98, 107, 132, 141};  // (sizes 4, 3, 9, 1, 81, 9, 25, 9, 9)
   const float* table[9];
-  for (int i = 0; i < 9; ++i) table[i] = params.data() + at[i];
+  param_table(params.data(), table);
   void* raw = small.data();
   float* out = (float*)small.data();
   const size_t all = ~(size_t)0;  // "the workspace is large enough": the calls below must fail before they believe it
@@ -66,3 +59,5 @@ int main() {
   }
   return 0;
 }
+
+}  // namespace r2l_drv::limits

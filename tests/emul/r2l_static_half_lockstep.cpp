@@ -1,46 +1,22 @@
-// r2l_static_half_lockstep.cpp -- stand-alone driver (own main, no Python) of the static chains' 16-bit-output kernels in their
-// DEVICE forms on the CPU: the lock-step emulation's sources (r2l_lockstep.cpp, unchanged) compiled into one program with
-// -fsanitize=address,undefined.  TEST INFRASTRUCTURE: built and run by tests/test_static_half_io.py.
+// r2l_static_half_lockstep.cpp -- driver `static_half` of r2l_lockstep_drivers.cpp (stand-alone, no Python) of the static chains'
+// 16-bit-output kernels in their DEVICE forms on the CPU: the lock-step emulation's sources (r2l_lockstep.cpp, unchanged) under
+// -fsanitize=address,undefined.  TEST INFRASTRUCTURE: run by tests/test_static_half_io.py.
 // Every buffer is a heap block of exactly the size the C ABI asks for: the 16-bit output is half the float32 one, so a store
 // that is too wide, or lands at a float32 offset, is an ASan report.  Each 16-bit call (r2l_static_fwd_io, R2L_IO_BF16 / _F16) is
 // compared bit for bit with the out_io = R2L_IO_F32 call of the same build narrowed by the host helpers of r2l_common.h.
-//   usage: r2l_static_half_lockstep
-#define R2L_TEST_HOOKS 1
-#include "r2l_lockstep.cpp"
+//   usage: r2l_lockstep_drivers static_half
+namespace r2l_drv::static_half {
 
-#include <stdio.h>
-
-static unsigned lcg_state = 2468u;
-static float lcg01() {
-  lcg_state = lcg_state * 1664525u + 1013904223u;
-  return (float)(lcg_state >> 8) * (1.0f / 16777216.0f);
-}
-template <class T>
-struct Buf {  // (malloc, not new[]: no cookie in front, the block ends at its last element)
-  T* p;
-  size_t n;
-  explicit Buf(size_t n_) : p((T*)malloc(n_ * sizeof(T) ? n_ * sizeof(T) : 1)), n(n_) { memset(p, 0xff, n_ * sizeof(T)); }
-  ~Buf() { free(p); }
-};
-
-// Drone camera: black level, white balance, colour matrix (oracle/isp_oracle.py: DRONE_CAMERA_PARAMS)
-static const double CAMERA[16] = {0.0625,      0.0626,      0.0625,      0.0626,     2.86653646,  1.,          1.73079425, 1.50768983,
-                                  -0.33571374, -0.17197604, -0.23048614, 1.70698738, -0.47650126, -0.03119153, -0.32803956, 1.35923111};
-static const float MEAN_STD[6] = {0.35f, 0.36f, 0.35f, 0.12f, 0.11f, 0.12f};  // train.py:157-158
+static Lcg lcg01{2468u};
 
 static const char* const launched_suffix[3] = {"", "_bf16_kernel", "_f16_kernel"};
 
 static int run_case(int B, int H, int W, int debayer, int sharpening, int denoising, int frames, int io, bool norm) {
   const size_t px = (size_t)B * H * W;
-  Buf<float> rawf(frames == R2L_FRAMES_F32 ? px : 0);
-  Buf<unsigned short> rawu(frames == R2L_FRAMES_U16 ? px : 0);
+  Block rawb(px * raw_bytes(frames));
   // values below the black level, inside, and (after white balance) above the clip
-  for (size_t i = 0; i < px; ++i) {
-    const float v = 0.02f + 0.9f * lcg01();
-    if (frames == R2L_FRAMES_U16) rawu.p[i] = (unsigned short)(v * 65535.f);
-    else rawf.p[i] = v;
-  }
-  const void* raw = frames == R2L_FRAMES_U16 ? (const void*)rawu.p : (const void*)rawf.p;
+  fill_raw(lcg01, rawb.p, px, frames, 0.02f, 0.9f);
+  const void* raw = rawb.p;
   const char* why = r2l_static_io_supported(frames, H, W, debayer, sharpening, denoising, nullptr);
   if (why) return fprintf(stderr, "not served: %s\n", why), 1;
   if (r2l_static_workspace_bytes(B, H, W, debayer, sharpening, denoising) != 0) return fprintf(stderr, "workspace?\n"), 1;
@@ -50,11 +26,7 @@ static int run_case(int B, int H, int W, int debayer, int sharpening, int denois
   int e = r2l_static_fwd_io(raw, frames, 65535.f, out32.p, R2L_IO_F32, B, H, W, CAMERA, debayer, sharpening, denoising, 2.2, nullptr, ms,
                             nullptr, 0, nullptr);
   if (e) return fprintf(stderr, "float32 call -> %d: %s\n", e, r2l_last_error()), 1;
-  {
-    std::lock_guard<std::mutex> g(r2l_ls_record_mutex);
-    r2l_ls_record.clear();
-    r2l_ls_record_on = true;
-  }
+  record_begin();
   e = r2l_static_fwd_io(raw, frames, 65535.f, out16.p, io, B, H, W, CAMERA, debayer, sharpening, denoising, 2.2, nullptr, ms, nullptr, 0,
                         nullptr);
   r2l_ls_record_on = false;
@@ -84,7 +56,7 @@ static int run_case(int B, int H, int W, int debayer, int sharpening, int denois
   return bad ? 1 : 0;
 }
 
-int main() {
+int run(int, char**) {
   static const int shapes[3][3] = {{1, 6, 80}, {1, 10, 260}, {1, 4, 4}};
   // the short chain (r2l_static_stream.h) and the luma chain (r2l_static_chain.h: Gaussian and median outputs) x both demosaics
   static const int chains[3][2] = {{R2L_SHARPEN_NONE, R2L_DENOISE_NONE}, {R2L_SHARPEN_FILTER, R2L_DENOISE_GAUSSIAN},
@@ -146,3 +118,5 @@ int main() {
   }
   return rc;
 }
+
+}  // namespace r2l_drv::static_half

@@ -1,37 +1,16 @@
-// r2l_static_routes_lockstep.cpp -- stand-alone driver (own main, no Python) that writes down what the static chains' host route
-// does: one text line per call of the C ABI, on the lock-step emulation's sources (r2l_lockstep.cpp, unchanged) compiled into one
-// program with -fsanitize=address,undefined.  TEST INFRASTRUCTURE: built and run by tests/test_static_routes.py, which compares
+// r2l_static_routes_lockstep.cpp -- driver `static_routes` of r2l_lockstep_drivers.cpp (stand-alone, no Python) that writes down what
+// the static chains' host route does: one text line per call of the C ABI, on the lock-step emulation's sources (r2l_lockstep.cpp,
+// unchanged) under -fsanitize=address,undefined.  TEST INFRASTRUCTURE: run by tests/test_static_routes.py, which compares
 // the output line by line with tests/golden/static_routes.txt (tests/README.md: how that file is regenerated).
 //   Q  what the workspace and 16-bit queries answer, over the full product of frame kind x chain x median size x shape
 //   R  a call that runs: return code, error text, launch record (kernel*count, sorted), FNV-1a 64 of the output bytes.  Its
 //      workspace is a malloc block of EXACTLY the size the matching query returned: a write past it is an ASan report
 //   S  the same call with one byte less of workspace
 //   X  calls that fail before a launch
-//   usage: r2l_static_routes_lockstep
-#define R2L_TEST_HOOKS 1
-#include "r2l_lockstep.cpp"
+//   usage: r2l_lockstep_drivers static_routes
+namespace r2l_drv::static_routes {
 
-#include <stdio.h>
-
-#include <vector>
-
-static unsigned lcg_state = 97531u;
-static float lcg01() {
-  lcg_state = lcg_state * 1664525u + 1013904223u;
-  return (float)(lcg_state >> 8) * (1.0f / 16777216.0f);
-}
-struct Block {  // (malloc, not new[]: no cookie in front, the block ends at its last byte)
-  char* p;
-  size_t n;
-  explicit Block(size_t n_, int fill = 0xff) : p((char*)malloc(n_ ? n_ : 1)), n(n_) { memset(p, fill, n_); }
-  ~Block() { free(p); }
-  Block(const Block&) = delete;
-};
-
-// Drone camera: black level, white balance, colour matrix (oracle/isp_oracle.py: DRONE_CAMERA_PARAMS)
-static const double CAMERA[16] = {0.0625,      0.0626,      0.0625,      0.0626,     2.86653646,  1.,          1.73079425, 1.50768983,
-                                  -0.33571374, -0.17197604, -0.23048614, 1.70698738, -0.47650126, -0.03119153, -0.32803956, 1.35923111};
-static const float MEAN_STD[6] = {0.35f, 0.36f, 0.35f, 0.12f, 0.11f, 0.12f};  // train.py:157-158
+static Lcg lcg01{97531u};
 static const double MEDIANS[3] = {3.0, 5.0, 2.5};
 
 struct Chain {
@@ -78,33 +57,19 @@ static void queries(int tiled) {
 }
 
 // ---- R / S lines ------------------------------------------------------------------------------------------------------------
-static unsigned long long fnv1a(const void* p, size_t n) {
-  unsigned long long h = 1469598103934665603ull;
-  for (size_t i = 0; i < n; ++i) h = (h ^ ((const unsigned char*)p)[i]) * 1099511628211ull;
-  return h;
-}
 static int failures = 0;
 static void run(const char* tag, int frames, int io, int B, int H, int W, const Chain& c, bool norm = false) {
   const size_t px = (size_t)B * H * W;
-  Block raw(px * (frames == R2L_FRAMES_F64 ? 8 : (frames == R2L_FRAMES_U16 ? 2 : 4)));
+  Block raw(px * raw_bytes(frames));
   // values below the black level, inside, and (after white balance) above the clip
-  for (size_t i = 0; i < px; ++i) {
-    const float v = 0.02f + 0.9f * lcg01();
-    if (frames == R2L_FRAMES_U16) ((unsigned short*)raw.p)[i] = (unsigned short)(v * 65535.f);
-    else if (frames == R2L_FRAMES_F64) ((double*)raw.p)[i] = (double)v;
-    else ((float*)raw.p)[i] = v;
-  }
+  fill_raw(lcg01, raw.p, px, frames, 0.02f, 0.9f);
   double o[R2L_SOPT_COUNT];
   options(c.med, o);
   const double* opts = c.med == 3.0 ? nullptr : o;
   const size_t ws_bytes = r2l_static_workspace_bytes_opts(frames, B, H, W, c.deb, c.sh, c.dn, opts);
   for (int less = 0; less <= (ws_bytes ? 1 : 0); ++less) {
     Block ws(ws_bytes - less), out(3 * px * (io == R2L_IO_F32 ? 4 : 2));
-    {
-      std::lock_guard<std::mutex> g(r2l_ls_record_mutex);
-      r2l_ls_record.clear();
-      r2l_ls_record_on = true;
-    }
+    record_begin();
     const int e = r2l_static_fwd_io(raw.p, frames, 65535.f, out.p, io, B, H, W, CAMERA, c.deb, c.sh, c.dn, 2.2, opts, norm ? MEAN_STD : nullptr,
                                     ws.n ? ws.p : nullptr, ws.n, nullptr);
     r2l_ls_record_on = false;
@@ -297,7 +262,7 @@ static void refusals() {
   }
 }
 
-int main() {
+int run(int, char**) {
   for (const char* v : {"R2L_STATIC_TILED", "R2L_CHAIN_BAND", "R2L_STREAM_BANDS", "R2L_GRID_STATIC", "R2L_GRID_STATIC_FULL"}) unsetenv(v);
   puts("# Q<R2L_STATIC_TILED> frames debayer|sharpening|denoising median: for W in 8 10 260 1028 2052, for BxH in 1x8 2x12:");
   puts("#   r2l_static_workspace_bytes,_f64,_opts (=: as the first),r2l_static_io_supported (k: the text of line 'W k', -: served)");
@@ -312,3 +277,5 @@ int main() {
   fflush(stdout);
   return failures ? 1 : 0;
 }
+
+}  // namespace r2l_drv::static_routes

@@ -21,6 +21,7 @@ import channels_last_checks as cc  # noqa: E402
 import emul_hook  # noqa: E402
 import half_io_checks as hc  # noqa: E402
 import kernel_resources  # noqa: E402
+import lockstep_driver  # noqa: E402
 import parity_checks as pc  # noqa: E402
 import raw_grad_checks as rc  # noqa: E402
 from oracle import isp_oracle as orc  # noqa: E402
@@ -30,29 +31,17 @@ from raw2logit_amd import functional as F_  # noqa: E402
 from raw2logit_amd.processing import pipeline_torch as ppt  # noqa: E402
 
 NEW_SYMBOLS = ('r2l_isp_layout_supported', 'r2l_isp_step_fwd_layout', 'r2l_isp_step_bwd_layout')
-BUILD = os.path.join(HERE, '_build')
-SANITIZE = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer', '-g']
 CL = torch.channels_last
 KEEP = 8
-LOCKSTEP_PLAIN = os.path.join(BUILD, 'libr2l_lockstep_plain.so')
-
-
-def _lockstep_deps():
-    csrc = os.path.join(REPO, 'raw2logit_amd', 'csrc')
-    return [os.path.join(HERE, 'emul', 'r2l_lockstep.cpp'), os.path.join(HERE, 'emul', 'r2l_lockstep_rt.h'),
-            os.path.join(REPO, 'include', 'r2l_isp.h')] + [os.path.join(csrc, f) for f in os.listdir(csrc)]
-
-
-def _fresh(target, deps):
-    return os.path.exists(target) and all(os.path.getmtime(target) >= os.path.getmtime(d) for d in deps)
+LOCKSTEP_PLAIN = os.path.join(lockstep_driver.BUILD, 'libr2l_lockstep_plain.so')
 
 
 @pytest.fixture(scope='module')
 def lockstep():
     """CPU tensors served by the lock-step emulation (every kernel in its device form, one fiber per lane) for the duration of a
     test: a build WITHOUT the sanitizers, so that it loads into this process; the sanitized run is the stand-alone program below"""
-    if not _fresh(LOCKSTEP_PLAIN, _lockstep_deps()):
-        os.makedirs(BUILD, exist_ok=True)
+    if not lockstep_driver.fresh(LOCKSTEP_PLAIN, lockstep_driver.lockstep_deps()):
+        os.makedirs(lockstep_driver.BUILD, exist_ok=True)
         tmp = LOCKSTEP_PLAIN + f'.{os.getpid()}.tmp'
         subprocess.run(['g++', '-std=c++17', '-O0', '-DR2L_TEST_HOOKS', '-shared', '-fPIC',
                         os.path.join(HERE, 'emul', 'r2l_lockstep.cpp'), '-o', tmp], check=True)
@@ -225,20 +214,13 @@ def test_module_on_the_lock_step_emulation_bitwise(lockstep, B, H, W, bn, traini
 
 
 def test_device_form_kernels_under_the_sanitizers(tmp_path):
-    """tests/emul/r2l_channels_last_lockstep.cpp: the lock-step emulation's sources + a main, -fsanitize=address,undefined, no
-    Python in the process.  (2,6,80) and (1,4,260) -- a last strip of one lane; float32 / bfloat16 / float16; BatchNorm none /
-    train / eval; both frame containers; d/d raw: the R2L_LAYOUT_NHWC calls against the R2L_LAYOUT_NCHW calls of the same build,
-    bit for bit, `out` and `grad_out` exactly 3 B H W elements long.  -O0 like the lock-step library"""
-    src = os.path.join(HERE, 'emul', 'r2l_channels_last_lockstep.cpp')
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, 'r2l_channels_last_lockstep')
-    if not _fresh(exe, [src] + _lockstep_deps()):
-        tmp = exe + f'.{os.getpid()}.tmp'
-        subprocess.run(['g++', '-std=c++17', '-O0', *SANITIZE, '-I' + os.path.join(HERE, 'emul'), src, '-o', tmp], check=True)
-        os.replace(tmp, exe)
+    """tests/emul/r2l_channels_last_lockstep.cpp (tests/lockstep_driver.py: the lock-step emulation's sources + a main,
+    -fsanitize=address,undefined, no Python in the process).  (2,6,80) and (1,4,260) -- a last strip of one lane; float32 /
+    bfloat16 / float16; BatchNorm none / train / eval; both frame containers; d/d raw: the R2L_LAYOUT_NHWC calls against the
+    R2L_LAYOUT_NCHW calls of the same build, bit for bit, `out` and `grad_out` exactly 3 B H W elements long"""
     params = tmp_path / 'params.bin'
     ppt.ParametrizedProcessing(orc.DRONE_CAMERA_PARAMS).packed_parameters().detach().numpy().astype('<f4').tofile(params)
-    r = subprocess.run([exe, str(params)], capture_output=True, text=True, timeout=900)
+    r = lockstep_driver.run('channels_last', params, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert r.stdout.count(': 0 mismatches') == 12, r.stdout
 

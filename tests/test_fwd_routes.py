@@ -4,38 +4,25 @@ bands and argument block over the full product of the entries and their switches
 the launches and the bytes written -- with a workspace of exactly the queried size, under the sanitizers.  No GPU."""
 import os
 import re
-import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 import fwd_routes_record as rec  # noqa: E402
+import lockstep_driver  # noqa: E402
 
-BUILD = os.path.join(HERE, '_build')
-SANITIZE = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer', '-g']
 OVERRIDES = ('FWD_TILED', 'FORCE_SPLIT', 'FWD_APPLY_RECOMPUTE', 'FWD_STATS_SPLIT', 'FWD_STATS_STREAM', 'FS_BAND', 'FL_BAND', 'FST_BAND',
              'FA_BAND', 'GRID_FWD', 'BNR_BAND', 'GRID_BNR', 'BWD_PLANES')
 IO_SUFFIXES = ('_bf16', '_f16', '_nhwc', '_bf16_nhwc', '_f16_nhwc')
 
 
 def test_every_forward_call_plans_launches_and_writes_what_the_parent_did():
-    """tests/emul/r2l_fwd_routes_lockstep.cpp: the lock-step emulation's sources + a main, -fsanitize=address,undefined, no Python in
-    the process; its output line by line against tests/golden/fwd_routes.txt.  The workspace of every run is a malloc block of exactly
-    r2l_isp_workspace_bytes and `out` one of exactly 3 B H W elements: a kernel that writes past either is an ASan report.  -O0 like
-    the lock-step library: the optimiser needs many minutes for these sources under the sanitizers"""
-    src = os.path.join(HERE, 'emul', 'r2l_fwd_routes_lockstep.cpp')
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, 'r2l_fwd_routes_lockstep')
-    csrc = os.path.join(REPO, 'raw2logit_amd', 'csrc')
-    deps = [src, os.path.join(HERE, 'emul', 'r2l_lockstep.cpp'), os.path.join(HERE, 'emul', 'r2l_lockstep_rt.h'),
-            os.path.join(REPO, 'include', 'r2l_isp.h')] + [os.path.join(csrc, f) for f in os.listdir(csrc)]
-    if not (os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in deps)):
-        tmp = exe + f'.{os.getpid()}.tmp'
-        subprocess.run(['g++', '-std=c++17', '-O0', *SANITIZE, '-I' + os.path.join(HERE, 'emul'), src, '-o', tmp], check=True)
-        os.replace(tmp, exe)
+    """tests/emul/r2l_fwd_routes_lockstep.cpp (tests/lockstep_driver.py: the lock-step emulation's sources + a main,
+    -fsanitize=address,undefined, no Python in the process); its output line by line against tests/golden/fwd_routes.txt.  The
+    workspace of every run is a malloc block of exactly r2l_isp_workspace_bytes and `out` one of exactly 3 B H W elements: a kernel
+    that writes past either is an ASan report"""
     env = {k: v for k, v in os.environ.items() if not k.startswith('R2L_')}
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=900, env=env)
+    r = lockstep_driver.run('fwd_routes', env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     assert 'Sanitizer' not in r.stderr and 'runtime error' not in r.stderr, r.stderr[-3000:]
     got, want = r.stdout.splitlines(), rec.lines()

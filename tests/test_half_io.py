@@ -18,6 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 import kernel_resources  # noqa: E402
+import lockstep_driver  # noqa: E402
 import parity_checks as pc  # noqa: E402
 from oracle import isp_oracle as orc  # noqa: E402
 from oracle.golden_cases import PARAM_CASES  # noqa: E402
@@ -26,8 +27,7 @@ from raw2logit_amd import functional as F_  # noqa: E402
 from raw2logit_amd.processing import pipeline_torch as ppt  # noqa: E402
 
 NEW_SYMBOLS = ('r2l_isp_io_supported', 'r2l_isp_step_fwd_io', 'r2l_isp_step_bwd_io')
-BUILD = os.path.join(HERE, '_build')
-SANITIZE = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer', '-g']
+SANITIZE = lockstep_driver.SANITIZE
 
 
 def test_abi_declares_exports_and_binds_the_new_entry_points():
@@ -195,23 +195,13 @@ def test_conversion_helpers_bit_for_bit_against_torch(tmp_path):
 
 
 def test_device_form_kernels_under_the_sanitizers(tmp_path):
-    """tests/emul/r2l_half_io_lockstep.cpp: the lock-step emulation's sources + a main, -fsanitize=address,undefined, no Python in the
-    process.  (2,4,4), (2,4,260), (1,70,260); BatchNorm none / train / eval; both frame types; both 16-bit types; d/d raw: the
-    16-bit calls against the io = R2L_IO_F32 calls of the same build, bit for bit, every buffer exactly as large as the ABI says.
-    -O0 like the lock-step library: the optimiser needs many minutes for these sources under the sanitizers"""
-    src = os.path.join(HERE, 'emul', 'r2l_half_io_lockstep.cpp')
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, 'r2l_half_io_lockstep')
-    csrc = os.path.join(REPO, 'raw2logit_amd', 'csrc')
-    deps = [src, os.path.join(HERE, 'emul', 'r2l_lockstep.cpp'), os.path.join(HERE, 'emul', 'r2l_lockstep_rt.h'),
-            os.path.join(REPO, 'include', 'r2l_isp.h')] + [os.path.join(csrc, f) for f in os.listdir(csrc)]
-    if not (os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in deps)):
-        tmp = exe + f'.{os.getpid()}.tmp'
-        subprocess.run(['g++', '-std=c++17', '-O0', *SANITIZE, '-I' + os.path.join(HERE, 'emul'), src, '-o', tmp], check=True)
-        os.replace(tmp, exe)
+    """tests/emul/r2l_half_io_lockstep.cpp (tests/lockstep_driver.py: the lock-step emulation's sources + a main,
+    -fsanitize=address,undefined, no Python in the process).  (2,4,4), (2,4,260), (1,70,260); BatchNorm none / train / eval; both
+    frame types; both 16-bit types; d/d raw: the 16-bit calls against the io = R2L_IO_F32 calls of the same build, bit for bit,
+    every buffer exactly as large as the ABI says"""
     params = tmp_path / 'params.bin'
     ppt.ParametrizedProcessing(orc.DRONE_CAMERA_PARAMS).packed_parameters().detach().numpy().astype('<f4').tofile(params)
-    r = subprocess.run([exe, str(params)], capture_output=True, text=True, timeout=900)
+    r = lockstep_driver.run('half_io', params, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert r.stdout.count(': 0 mismatches') == 12, r.stdout
 

@@ -4,7 +4,6 @@ frames and at 2^40-pixel batches, and the refusals at the documented limits on t
 allocation."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,13 +11,10 @@ import pytest
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 import guarded_arena as ga  # noqa: E402
 import large_index_checks as lc  # noqa: E402
-
-BUILD = os.path.join(HERE, '_build')
-SANITIZE = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer', '-g']
+import lockstep_driver  # noqa: E402
 
 
 # ---- the comparison logic ---------------------------------------------------------------------------------------------------
@@ -184,21 +180,11 @@ def test_size_queries_are_the_closed_forms(emulation):
 
 # ---- the refusals at the documented limits ----------------------------------------------------------------------------------
 def test_refusals_at_the_documented_limits():
-    """tests/emul/r2l_limits_lockstep.cpp: the lock-step emulation's sources (the device's host route) + a main under
-    -fsanitize=address,undefined, no Python in the process.  Each call names a shape past a limit and hands over buffers of a few
-    bytes: it must come back with the documented code and text before any launch could use the shape"""
-    src = os.path.join(HERE, 'emul', 'r2l_limits_lockstep.cpp')
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, 'r2l_limits_lockstep')
-    csrc = os.path.join(REPO, 'raw2logit_amd', 'csrc')
-    deps = [src, os.path.join(HERE, 'emul', 'r2l_lockstep.cpp'), os.path.join(HERE, 'emul', 'r2l_lockstep_rt.h'),
-            os.path.join(REPO, 'include', 'r2l_isp.h')] + [os.path.join(csrc, f) for f in os.listdir(csrc)]
-    if not (os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in deps)):
-        tmp = exe + f'.{os.getpid()}.tmp'
-        subprocess.run(['g++', '-std=c++17', '-O0', *SANITIZE, '-I' + os.path.join(HERE, 'emul'), src, '-o', tmp], check=True)
-        os.replace(tmp, exe)
+    """tests/emul/r2l_limits_lockstep.cpp (tests/lockstep_driver.py: the lock-step emulation's sources -- the device's host route
+    -- + a main under -fsanitize=address,undefined, no Python in the process).  Each call names a shape past a limit and hands over
+    buffers of a few bytes: it must come back with the documented code and text before any launch could use the shape"""
     env = {k: v for k, v in os.environ.items() if not k.startswith('R2L_')}
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    r = lockstep_driver.run('limits', env=env, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     got = dict(line.split(' -> ', 1) for line in r.stdout.splitlines())
     frame, batch, many = 'frame 2^29 + 2 * 2048 px', 'batch 4097x16384x16384', '2^30 + 2 frames of 4x4'

@@ -6,7 +6,6 @@ import ctypes
 import os
 import pickle
 import re
-import subprocess
 import sys
 
 import pytest
@@ -17,14 +16,13 @@ REPO = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 import half_io_checks as hc  # noqa: E402
 import kernel_resources  # noqa: E402
+import lockstep_driver  # noqa: E402
 import static_half_checks as sh  # noqa: E402
 from oracle import isp_oracle as orc  # noqa: E402
 from raw2logit_amd import _lib  # noqa: E402
 from raw2logit_amd import functional as F_  # noqa: E402
 from raw2logit_amd.processing import pipeline_numpy as ppn  # noqa: E402
 
-BUILD = os.path.join(HERE, '_build')
-SANITIZE = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer', '-g']
 both = pytest.mark.parametrize('dtype', sh.DTYPES, ids=sh.DTYPE_IDS)
 
 
@@ -140,22 +138,12 @@ def test_serial_emulation_module_is_the_float32_module_and_a_cast(emulation, cha
 
 
 def test_device_form_kernels_under_the_sanitizers():
-    """tests/emul/r2l_static_half_lockstep.cpp: the lock-step emulation's sources + a main, -fsanitize=address,undefined, no Python
-    in the process.  1x6x80, 1x10x260 (two strips), 1x4x4; short chain, sharpening_filter + gaussian / median; both demosaics;
-    float32 and 16-bit-container frames; bf16 and f16; with and without Normalize: each 16-bit output against the float32
-    instantiation's narrowed by the host helper, bit for bit, every buffer exactly as large as the ABI says.  -O0 like the
-    lock-step library: the optimiser needs many minutes for these sources under the sanitizers"""
-    src = os.path.join(HERE, 'emul', 'r2l_static_half_lockstep.cpp')
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, 'r2l_static_half_lockstep')
-    csrc = os.path.join(REPO, 'raw2logit_amd', 'csrc')
-    deps = [src, os.path.join(HERE, 'emul', 'r2l_lockstep.cpp'), os.path.join(HERE, 'emul', 'r2l_lockstep_rt.h'),
-            os.path.join(REPO, 'include', 'r2l_isp.h')] + [os.path.join(csrc, f) for f in os.listdir(csrc)]
-    if not (os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in deps)):
-        tmp = exe + f'.{os.getpid()}.tmp'
-        subprocess.run(['g++', '-std=c++17', '-O0', *SANITIZE, '-I' + os.path.join(HERE, 'emul'), src, '-o', tmp], check=True)
-        os.replace(tmp, exe)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=900)
+    """tests/emul/r2l_static_half_lockstep.cpp (tests/lockstep_driver.py: the lock-step emulation's sources + a main,
+    -fsanitize=address,undefined, no Python in the process).  1x6x80, 1x10x260 (two strips), 1x4x4; short chain,
+    sharpening_filter + gaussian / median; both demosaics; float32 and 16-bit-container frames; bf16 and f16; with and without
+    Normalize: each 16-bit output against the float32 instantiation's narrowed by the host helper, bit for bit, every buffer
+    exactly as large as the ABI says"""
+    r = lockstep_driver.run('static_half', timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     # 3 shapes x 3 chains x 2 demosaics x 2 frame types x 2 output types, 2 behind unsharp_masking, 2 on float64 frames
     assert r.stdout.count(': 0 mismatches') == 76 and r.stdout.count('mismatches') == 76, r.stdout
