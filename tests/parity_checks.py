@@ -713,6 +713,25 @@ def midtone_frames(B, H, W, seed):
     return (u16.astype(np.float32) / np.float32(4095)).astype(np.float32)
 
 
+def frame_shapes_grad_limit(ref, lo, hi, cot_size, bn, g32=None):
+    """check_frame_shapes' limit on |grad - float64 oracle| of one parameter (shared with tests/bn_checks.py): 3e-5 of the
+    gradient's scale + twice the effect of torch.clip's step gradient flipping at a threshold (`lo` / `hi`: the oracle's gradient
+    with the pass band shifted by -/+ 1e-6); with BatchNorm 1e-7 * cot_size; with `g32` (conditioning=True: the float32 oracle's
+    gradient) twice its distance from the float64 one + 7e-8 * sqrt(cot_size)."""
+    ref = np.asarray(ref)
+    flip = max(np.abs(np.asarray(lo) - ref).max(), np.abs(np.asarray(hi) - ref).max())
+    lim = 3e-5 * (np.abs(ref).max() + 1e-6) + 2 * flip
+    if bn:      # BatchNorm's backward cancels: float32 round-off of a sum of B*3*H*W terms of size ~1
+        lim += 1e-7 * cot_size
+    if g32 is not None:
+        lim += 2 * np.abs(np.asarray(g32, dtype=np.float64).reshape(ref.shape) - ref).max()
+        # ... and the random walk of the float32 roundings of cot_size terms of magnitude <= ~1/4 each: a gradient whose
+        # terms cancel (gamma_correct under a random cotangent: |ref| 2e-3 from terms summing to 400 in magnitude) has no
+        # 3e-5 of ITSELF to spend (random frame shapes on the lock-step emulation, round 5: 1e-6 absolute on 34x16)
+        lim += 7e-8 * np.sqrt(cot_size)
+    return lim
+
+
 def check_frame_shapes(device, shapes=FRAME_SHAPES, B=2, conditioning=False):
     """Fused forward + every parameter gradient against the float64 oracle over frame shapes that put the image
     edge at every distance (0, 2, 4, 6 pixels) from a tile boundary, below the halo width and in frames smaller
@@ -756,16 +775,7 @@ def check_frame_shapes(device, shapes=FRAME_SHAPES, B=2, conditioning=False):
             for k in g:
                 ref = np.asarray(g[k])
                 got = NAME2ATTR[k](m).grad.detach().cpu().numpy().reshape(ref.shape)
-                flip = max(np.abs(np.asarray(glo[k]) - ref).max(), np.abs(np.asarray(ghi[k]) - ref).max())
-                lim = 3e-5 * (np.abs(ref).max() + 1e-6) + 2 * flip
-                if bn:      # BatchNorm's backward cancels: float32 round-off of a sum of B*3*H*W terms of size ~1
-                    lim += 1e-7 * cot.size
-                if g32 is not None:
-                    lim += 2 * np.abs(np.asarray(g32[k], dtype=np.float64).reshape(ref.shape) - ref).max()
-                    # ... and the random walk of the float32 roundings of cot.size terms of magnitude <= ~1/4 each: a gradient whose
-                    # terms cancel (gamma_correct under a random cotangent: |ref| 2e-3 from terms summing to 400 in magnitude) has no
-                    # 3e-5 of ITSELF to spend (random frame shapes on the lock-step emulation, round 5: 1e-6 absolute on 34x16)
-                    lim += 7e-8 * np.sqrt(cot.size)
+                lim = frame_shapes_grad_limit(ref, glo[k], ghi[k], cot.size, bn, None if g32 is None else g32[k])
                 worst = max(worst, np.abs(got - ref).max() / lim)
                 assert np.abs(got - ref).max() <= lim, (H, W, bn, k, np.abs(got - ref).max(), lim)
     return worst
