@@ -1396,79 +1396,131 @@ size_t r2l_isp_step_offset(int which, int B, int H, int W) {
     default: return 0;
   }
 }
-// r2l_isp_step_fwd and r2l_isp_step_fwd_io: `out` holds elements of type io (R2L_IO_*)
-static int r2l_isp_step_fwd_impl(const void* raw, int raw_u16, float denom, const float* const* params_host,
-                                 const float* additive, int bn_mode, float* running_mean, float* running_var,
-                                 long long* num_batches_tracked, double eps, double momentum, float* out, int io,
-                                 void* workspace, size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
-                                 const double* gathered_stats, void* stream) {
-  const int keep = (phase & R2L_STEP_KEEP_LUMA) ? R2L_F_KEEP_LUMA : 0;
+// 16-bit and channels-last output / cotangent (include/r2l_isp.h: R2L_IO_*, R2L_LAYOUT_*)
+// why a 16-bit or channels-last call is not served, or null: the ONE predicate of r2l_isp_io_supported, r2l_isp_layout_supported and
+// the r2l_isp_step_{fwd,bwd}_{io,layout} calls
+static const char* r2l_io_why(int raw_u16, bool has_additive, int B, int H, int W, int phase) {
+  (void)raw_u16;  // (both frame types are served)
+  if (!R2L_PLANE_PASSES) return "the serial emulation has no row-streaming forward and no plane passes";
+  if (B < 1 || H < 4 || W < 4 || (H & 1) || (W & 1)) return "H and W must be even and >= 4, B >= 1";
+  if (has_additive) return "not with an additive layer";
+  if ((W & 3) || W > 2048) return "needs W % 4 == 0 and W <= 2048";
+  if (r2l_env_int("R2L_FWD_TILED", 0)) return "needs the row-streaming forward (R2L_FWD_TILED is set)";
+  if (phase & R2L_STEP_EPI_MASK) return "not with an output epilogue";
+  if (!(phase & R2L_STEP_KEEP_LUMA)) return "needs R2L_STEP_KEEP_LUMA in `phase` of both calls";
+  return nullptr;
+}
+// 0, or the error of a call whose `out` / `grad_out` is not planar float32.  layout = R2L_LAYOUT_NHWC is served where a 16-bit call
+// is, float32 included (r2l_isp_layout_supported)
+static int r2l_io_check(const char* who, int io, int layout, const void* tensor, int raw_u16, bool has_additive, int B, int H,
+                        int W, int phase) {
+  if (io != R2L_IO_F32 && io != R2L_IO_BF16 && io != R2L_IO_F16) return r2l_fail(-1, std::string(who) + ": io must be one of R2L_IO_*");
+  if (layout != R2L_LAYOUT_NCHW && layout != R2L_LAYOUT_NHWC)
+    return r2l_fail(-1, std::string(who) + ": layout must be one of R2L_LAYOUT_*");
+  if (io == R2L_IO_F32 && layout == R2L_LAYOUT_NCHW) return 0;
+  const bool nhwc = layout == R2L_LAYOUT_NHWC;
+  if (const char* why = r2l_io_why(raw_u16, has_additive, B, H, W, phase))
+    return r2l_fail(-3, std::string(who) + (nhwc ? ": a channels-last output / cotangent is not served here: "
+                                                 : ": a 16-bit output / cotangent is not served here: ") + why);
+  if (nhwc && io == R2L_IO_F32) {
+    if ((uintptr_t)tensor % 16) return r2l_fail(-1, std::string(who) + ": the channels-last float32 tensor must be 16-byte aligned");
+  } else if ((uintptr_t)tensor % 8) {
+    return r2l_fail(-1, std::string(who) + ": the 16-bit tensor must be 8-byte aligned");
+  }
+  return 0;
+}
+// r2l_isp_step_fwd, r2l_isp_step_fwd_io and r2l_isp_step_fwd_layout: one implementation, what they ask of it
+struct R2LStepFwd {
+  const void* raw;
+  int raw_u16;
+  float denom;
+  const float* const* params_host;
+  const float* additive;
+  int bn_mode;
+  float *running_mean, *running_var;
+  long long* num_batches_tracked;
+  double eps, momentum;
+  float* out;
+  int io, layout;  // R2L_IO_*, R2L_LAYOUT_* as the entry got them; behind r2l_step_fwd's check io carries R2L_IO_NHWC too
+  void* workspace;
+  size_t workspace_bytes;
+  int B, H, W, nranks, phase;
+  const double* gathered_stats;
+  void* stream;
+};
+// `who`: the entry point r2l_last_error() names where io / layout are refused
+static int r2l_step_fwd(const char* who, R2LStepFwd q) {
+  if (int e = r2l_io_check(who, q.io, q.layout, q.out, q.raw_u16, q.additive != nullptr, q.B, q.H, q.W, q.phase)) return e;
+  if (q.layout == R2L_LAYOUT_NHWC) q.io |= R2L_IO_NHWC;
+  const int B = q.B, H = q.H, W = q.W;
+  const int keep = (q.phase & R2L_STEP_KEEP_LUMA) ? R2L_F_KEEP_LUMA : 0;
   R2LEpi ep;
   if (int e = r2l_check_dims(B, H, W)) return e;
-  if (int e = r2l_epi_from_phase(phase, H, W, ep)) return e;
-  phase &= ~(R2L_STEP_KEEP_LUMA | R2L_STEP_EPI_MASK);
-  if (!raw || !out || !workspace) return r2l_fail(-1, "r2l_isp_step_fwd: null pointer");
-  if (bn_mode != R2L_BN_NONE && bn_mode != R2L_BN_TRAIN && bn_mode != R2L_BN_EVAL)
+  if (int e = r2l_epi_from_phase(q.phase, H, W, ep)) return e;
+  const int phase = q.phase & ~(R2L_STEP_KEEP_LUMA | R2L_STEP_EPI_MASK);
+  if (!q.raw || !q.out || !q.workspace) return r2l_fail(-1, "r2l_isp_step_fwd: null pointer");
+  if (q.bn_mode != R2L_BN_NONE && q.bn_mode != R2L_BN_TRAIN && q.bn_mode != R2L_BN_EVAL)
     return r2l_fail(-1, "r2l_isp_step_fwd: bn_mode must be R2L_BN_NONE, R2L_BN_TRAIN or R2L_BN_EVAL");
   if (phase != R2L_STEP_ALL && phase != R2L_STEP_A && phase != R2L_STEP_B)
     return r2l_fail(-1, "r2l_isp_step_fwd: unknown phase");
-  if (nranks < 1 || (nranks > 1 && phase == R2L_STEP_ALL && bn_mode == R2L_BN_TRAIN))
+  if (q.nranks < 1 || (q.nranks > 1 && phase == R2L_STEP_ALL && q.bn_mode == R2L_BN_TRAIN))
     return r2l_fail(-1, "r2l_isp_step_fwd: several ranks exchange the statistics between phase A and phase B");
-  if (phase != R2L_STEP_ALL && bn_mode != R2L_BN_TRAIN)
+  if (phase != R2L_STEP_ALL && q.bn_mode != R2L_BN_TRAIN)
     return r2l_fail(-1, "r2l_isp_step_fwd: only train-mode BatchNorm has two phases");
-  if (phase == R2L_STEP_B && !gathered_stats) return r2l_fail(-1, "r2l_isp_step_fwd: phase B needs the gathered statistics");
-  if (bn_mode == R2L_BN_EVAL && (!running_mean || !running_var))
+  if (phase == R2L_STEP_B && !q.gathered_stats) return r2l_fail(-1, "r2l_isp_step_fwd: phase B needs the gathered statistics");
+  if (q.bn_mode == R2L_BN_EVAL && (!q.running_mean || !q.running_var))
     return r2l_fail(-1, "r2l_isp_step_fwd: eval-mode BatchNorm needs the running statistics");
-  if ((running_mean == nullptr) != (running_var == nullptr))
+  if ((q.running_mean == nullptr) != (q.running_var == nullptr))
     return r2l_fail(-1, "r2l_isp_step_fwd: running_mean and running_var go together");
-  const R2LRaw rw = r2l_raw_any(raw, raw_u16, denom);
-  const R2LWorkspace ws = r2l_carve(workspace, B, H, W);
-  if (workspace_bytes < ws.total) return r2l_fail(-2, "r2l_isp_step_fwd: workspace too small (r2l_isp_workspace_bytes)");
+  const R2LRaw rw = r2l_raw_any(q.raw, q.raw_u16, q.denom);
+  const R2LWorkspace ws = r2l_carve(q.workspace, B, H, W);
+  if (q.workspace_bytes < ws.total) return r2l_fail(-2, "r2l_isp_step_fwd: workspace too small (r2l_isp_workspace_bytes)");
   if (phase != R2L_STEP_B) {
-    if (!params_host) return r2l_fail(-1, "r2l_isp_step_fwd: null parameter table");
+    if (!q.params_host) return r2l_fail(-1, "r2l_isp_step_fwd: null parameter table");
     R2LPackFoldArgs pa;
     for (int i = 0; i < 9; ++i) {
-      if (!params_host[i]) return r2l_fail(-1, "r2l_isp_step_fwd: null parameter pointer");
-      pa.src[i] = params_host[i];
+      if (!q.params_host[i]) return r2l_fail(-1, "r2l_isp_step_fwd: null parameter pointer");
+      pa.src[i] = q.params_host[i];
     }
     pa.packed = ws.packed;
     pa.F = ws.folded;
     pa.counters = ws.counters;
-    pa.running_mean = bn_mode == R2L_BN_EVAL ? running_mean : nullptr;
-    pa.running_var = running_var;
+    pa.running_mean = q.bn_mode == R2L_BN_EVAL ? q.running_mean : nullptr;
+    pa.running_var = q.running_var;
     pa.bn = ws.bn;
-    pa.eps = eps;
-    if (int e = r2l_launch_pack_fold(pa, 1, stream)) return e;
+    pa.eps = q.eps;
+    if (int e = r2l_launch_pack_fold(pa, 1, q.stream)) return e;
   }
-  if (bn_mode == R2L_BN_TRAIN && phase != R2L_STEP_B) {
+  if (q.bn_mode == R2L_BN_TRAIN && phase != R2L_STEP_B) {
     // statistics pass; one rank: the last workgroup also does the BatchNorm bookkeeping
-    R2LBnFinalizeArgs f{ws.stats, 1, ws.bn, ws.moments, running_mean, running_var, eps, momentum, num_batches_tracked};
-    const R2LFwdCall c{rw, ws.packed, additive, nullptr, nullptr, ws.stats, phase == R2L_STEP_ALL ? &f : nullptr,
-                       R2LEpi{0, 0, 0, 0}, R2L_IO_F32, R2L_FWD_STATS_PASS, B, H, W, stream};
-    if (int e = r2l_isp_fwd_impl(c, R2L_F_STATS_ONLY | R2L_F_FOLDED_VALID | keep, workspace, workspace_bytes)) return e;
+    R2LBnFinalizeArgs f{ws.stats, 1, ws.bn, ws.moments, q.running_mean, q.running_var, q.eps, q.momentum, q.num_batches_tracked};
+    const R2LFwdCall c{rw, ws.packed, q.additive, nullptr, nullptr, ws.stats, phase == R2L_STEP_ALL ? &f : nullptr,
+                       R2LEpi{0, 0, 0, 0}, R2L_IO_F32, R2L_FWD_STATS_PASS, B, H, W, q.stream};
+    if (int e = r2l_isp_fwd_impl(c, R2L_F_STATS_ONLY | R2L_F_FOLDED_VALID | keep, q.workspace, q.workspace_bytes)) return e;
     if (phase == R2L_STEP_A) return 0;
   }
   if (phase == R2L_STEP_B) {
-    R2LBnFinalizeArgs f{gathered_stats, nranks, ws.bn, ws.moments, running_mean, running_var, eps, momentum,
-                        num_batches_tracked};
-    if (int e = r2l_launch_bn_finalize(f, 1, stream)) return e;
+    R2LBnFinalizeArgs f{q.gathered_stats, q.nranks, ws.bn, ws.moments, q.running_mean, q.running_var, q.eps, q.momentum,
+                        q.num_batches_tracked};
+    if (int e = r2l_launch_bn_finalize(f, 1, q.stream)) return e;
   }
   // (train mode: the statistics pass of this call -- or of phase A of this step -- has left Y' in the workspace wherever the
   // row-streaming forward runs, and the apply pass reads it)
-  const R2LFwdCall c{rw, ws.packed, additive, bn_mode == R2L_BN_NONE ? nullptr : ws.bn, out, nullptr, nullptr, ep, io,
-                     bn_mode == R2L_BN_TRAIN ? R2L_FWD_APPLY_PASS : R2L_FWD_WHOLE, B, H, W, stream};
-  return r2l_isp_fwd_impl(c, R2L_F_FOLDED_VALID | keep, workspace, workspace_bytes);
+  const R2LFwdCall c{rw, ws.packed, q.additive, q.bn_mode == R2L_BN_NONE ? nullptr : ws.bn, q.out, nullptr, nullptr, ep, q.io,
+                     q.bn_mode == R2L_BN_TRAIN ? R2L_FWD_APPLY_PASS : R2L_FWD_WHOLE, B, H, W, q.stream};
+  return r2l_isp_fwd_impl(c, R2L_F_FOLDED_VALID | keep, q.workspace, q.workspace_bytes);
 }
 int r2l_isp_step_fwd(const void* raw, int raw_u16, float denom, const float* const* params_host,
                      const float* additive, int bn_mode, float* running_mean, float* running_var,
                      long long* num_batches_tracked, double eps, double momentum, float* out, void* workspace,
                      size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
                      const double* gathered_stats, void* stream) {
-  return r2l_isp_step_fwd_impl(raw, raw_u16, denom, params_host, additive, bn_mode, running_mean, running_var,
-                               num_batches_tracked, eps, momentum, out, R2L_IO_F32, workspace, workspace_bytes, B, H, W, nranks,
-                               phase, gathered_stats, stream);
+  return r2l_step_fwd("r2l_isp_step_fwd",
+                      R2LStepFwd{raw, raw_u16, denom, params_host, additive, bn_mode, running_mean, running_var, num_batches_tracked,
+                                 eps, momentum, out, R2L_IO_F32, R2L_LAYOUT_NCHW, workspace, workspace_bytes, B, H, W, nranks, phase,
+                                 gathered_stats, stream});
 }
-// r2l_isp_step_bwd, r2l_isp_step_bwd_raw and r2l_isp_step_bwd_select: one implementation, what they ask of it
+// r2l_isp_step_bwd and its _raw, _select, _io and _layout forms: one implementation, what they ask of it
 struct R2LStepBwd {
   const void* raw;
   int raw_u16;
@@ -1483,7 +1535,8 @@ struct R2LStepBwd {
   void* stream;
   float *grad_raw, *guv;  // d/d raw and its scratch (the chroma gradient planes), or null
   unsigned grad_mask;     // R2L_GRAD_* bits (r2l_isp_step_bwd_select), 0 = every parameter gradient
-  int io;                 // the type behind grad_out (R2L_IO_*, r2l_isp_step_bwd_io; `out` is then not read)
+  int io, layout;         // of grad_out, R2L_IO_*, R2L_LAYOUT_* as the entry got them; behind r2l_step_bwd's check io carries
+                          // R2L_IO_NHWC too (not planar float32: `out` is not read)
 };
 static int r2l_isp_step_bwd_impl(const R2LStepBwd& q) {
   const int B = q.B, H = q.H, W = q.W;
@@ -1569,13 +1622,33 @@ static int r2l_raw_grad_preconditions(const R2LStepBwd& q, size_t raw_grad_scrat
     return r2l_fail(-1, "r2l_isp_step_bwd_raw: grad_raw and raw_grad_scratch must be 16-byte aligned");
   return 0;
 }
+// the one way into r2l_isp_step_bwd_impl.  `who`: the entry point r2l_last_error() names; masked: the entry takes a grad_mask (a
+// planar float32 call words what it refuses of the mask as r2l_isp_step_bwd_select)
+static int r2l_step_bwd(const char* who, bool masked, R2LStepBwd q, size_t raw_grad_scratch_bytes) {
+  if (int e = r2l_io_check(who, q.io, q.layout, q.grad_out, q.raw_u16, q.additive != nullptr, q.B, q.H, q.W, q.phase)) return e;
+  if (q.layout == R2L_LAYOUT_NHWC) q.io |= R2L_IO_NHWC;
+  if (masked) {
+    const char* w = q.io == R2L_IO_F32 ? "r2l_isp_step_bwd_select" : who;
+    if (q.grad_mask & ~(unsigned)(R2L_GRAD_ALL_PARAMS | R2L_GRAD_RAW))
+      return r2l_fail(-1, std::string(w) + ": unknown bits in grad_mask");
+    if ((q.grad_raw != nullptr) != ((q.grad_mask & R2L_GRAD_RAW) != 0))
+      return r2l_fail(-1, std::string(w) + ": grad_raw goes with R2L_GRAD_RAW in grad_mask");
+    if (q.grad_mask && !q.grad_params) return r2l_fail(-1, std::string(w) + ": a gradient is asked for but grad_params is null");
+  }
+  if (int e = q.grad_raw ? r2l_raw_grad_preconditions(q, raw_grad_scratch_bytes) : 0) return e;
+  // (phase A computes the BatchNorm sums only: the gradient kernels, and with them d/d raw, run in phase B / ALL.  A mask without
+  // a reduced route runs exactly r2l_isp_step_bwd / r2l_isp_step_bwd_raw: r2l_bwd_plan)
+  return r2l_isp_step_bwd_impl(q);
+}
 int r2l_isp_step_bwd(const void* raw, int raw_u16, float denom, const float* additive, const float* grad_out,
                      const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
                      size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
                      const double* gathered_sums, void* stream) {
-  return r2l_isp_step_bwd_impl(R2LStepBwd{raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode,
-                                          workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, nullptr,
-                                          nullptr, 0, R2L_IO_F32});
+  return r2l_step_bwd("r2l_isp_step_bwd", false,
+                      R2LStepBwd{raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode, workspace,
+                                 workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, nullptr, nullptr, 0, R2L_IO_F32,
+                                 R2L_LAYOUT_NCHW},
+                      0);
 }
 int r2l_isp_step_bwd_raw(const void* raw, int raw_u16, float denom, const float* additive, const float* grad_out,
                          const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
@@ -1583,66 +1656,25 @@ int r2l_isp_step_bwd_raw(const void* raw, int raw_u16, float denom, const float*
                          const double* gathered_sums, void* stream, float* grad_raw, void* raw_grad_scratch,
                          size_t raw_grad_scratch_bytes) {
   // (without grad_raw: r2l_isp_step_bwd, the scratch is not looked at)
-  const R2LStepBwd q{raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode, workspace,
-                     workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw,
-                     grad_raw ? (float*)raw_grad_scratch : nullptr, 0, R2L_IO_F32};
-  if (grad_raw)
-    if (int e = r2l_raw_grad_preconditions(q, raw_grad_scratch_bytes)) return e;
-  // (phase A computes the BatchNorm sums only: the gradient kernels, and with them d/d raw, run in phase B / ALL)
-  return r2l_isp_step_bwd_impl(q);
+  return r2l_step_bwd("r2l_isp_step_bwd_raw", false,
+                      R2LStepBwd{raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode, workspace,
+                                 workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw,
+                                 grad_raw ? (float*)raw_grad_scratch : nullptr, 0, R2L_IO_F32, R2L_LAYOUT_NCHW},
+                      raw_grad_scratch_bytes);
 }
 int r2l_isp_step_bwd_select(const void* raw, int raw_u16, float denom, const float* additive, const float* grad_out,
                             const float* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
                             size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
                             const double* gathered_sums, void* stream, float* grad_raw, void* raw_grad_scratch,
                             size_t raw_grad_scratch_bytes, unsigned grad_mask) {
-  if (grad_mask & ~(unsigned)(R2L_GRAD_ALL_PARAMS | R2L_GRAD_RAW))
-    return r2l_fail(-1, "r2l_isp_step_bwd_select: unknown bits in grad_mask");
-  if ((grad_raw != nullptr) != ((grad_mask & R2L_GRAD_RAW) != 0))
-    return r2l_fail(-1, "r2l_isp_step_bwd_select: grad_raw goes with R2L_GRAD_RAW in grad_mask");
-  if (grad_mask && !grad_params) return r2l_fail(-1, "r2l_isp_step_bwd_select: a gradient is asked for but grad_params is null");
-  const R2LStepBwd q{raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode, workspace,
-                     workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw, (float*)raw_grad_scratch,
-                     grad_mask, R2L_IO_F32};
-  if (grad_raw)
-    if (int e = r2l_raw_grad_preconditions(q, raw_grad_scratch_bytes)) return e;
-  // (a mask without a reduced route runs exactly r2l_isp_step_bwd / r2l_isp_step_bwd_raw: r2l_bwd_plan)
-  return r2l_isp_step_bwd_impl(q);
+  return r2l_step_bwd("r2l_isp_step_bwd_select", true,
+                      R2LStepBwd{raw, raw_u16, denom, additive, grad_out, out, grad_params, grad_additive, bn_mode, workspace,
+                                 workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw,
+                                 (float*)raw_grad_scratch, grad_mask, R2L_IO_F32, R2L_LAYOUT_NCHW},
+                      raw_grad_scratch_bytes);
 }
 
 // ---- 16-bit and channels-last output / cotangent (include/r2l_isp.h: R2L_IO_*, R2L_LAYOUT_*) -----------------------------------
-// why a 16-bit or channels-last call is not served, or null: the ONE predicate of r2l_isp_io_supported, r2l_isp_layout_supported and
-// the r2l_isp_step_{fwd,bwd}_{io,layout} calls
-static const char* r2l_io_why(int raw_u16, bool has_additive, int B, int H, int W, int phase) {
-  (void)raw_u16;  // (both frame types are served)
-  if (!R2L_PLANE_PASSES) return "the serial emulation has no row-streaming forward and no plane passes";
-  if (B < 1 || H < 4 || W < 4 || (H & 1) || (W & 1)) return "H and W must be even and >= 4, B >= 1";
-  if (has_additive) return "not with an additive layer";
-  if ((W & 3) || W > 2048) return "needs W % 4 == 0 and W <= 2048";
-  if (r2l_env_int("R2L_FWD_TILED", 0)) return "needs the row-streaming forward (R2L_FWD_TILED is set)";
-  if (phase & R2L_STEP_EPI_MASK) return "not with an output epilogue";
-  if (!(phase & R2L_STEP_KEEP_LUMA)) return "needs R2L_STEP_KEEP_LUMA in `phase` of both calls";
-  return nullptr;
-}
-// 0, or the error of a call whose `out` / `grad_out` is not planar float32.  layout = R2L_LAYOUT_NHWC is served where a 16-bit call
-// is, float32 included (r2l_isp_layout_supported)
-static int r2l_io_check(const char* who, int io, int layout, const void* tensor, int raw_u16, bool has_additive, int B, int H,
-                        int W, int phase) {
-  if (io != R2L_IO_F32 && io != R2L_IO_BF16 && io != R2L_IO_F16) return r2l_fail(-1, std::string(who) + ": io must be one of R2L_IO_*");
-  if (layout != R2L_LAYOUT_NCHW && layout != R2L_LAYOUT_NHWC)
-    return r2l_fail(-1, std::string(who) + ": layout must be one of R2L_LAYOUT_*");
-  if (io == R2L_IO_F32 && layout == R2L_LAYOUT_NCHW) return 0;
-  const bool nhwc = layout == R2L_LAYOUT_NHWC;
-  if (const char* why = r2l_io_why(raw_u16, has_additive, B, H, W, phase))
-    return r2l_fail(-3, std::string(who) + (nhwc ? ": a channels-last output / cotangent is not served here: "
-                                                 : ": a 16-bit output / cotangent is not served here: ") + why);
-  if (nhwc && io == R2L_IO_F32) {
-    if ((uintptr_t)tensor % 16) return r2l_fail(-1, std::string(who) + ": the channels-last float32 tensor must be 16-byte aligned");
-  } else if ((uintptr_t)tensor % 8) {
-    return r2l_fail(-1, std::string(who) + ": the 16-bit tensor must be 8-byte aligned");
-  }
-  return 0;
-}
 int r2l_isp_layout_supported(int io, int layout, int raw_u16, int has_additive, int B, int H, int W, int phase) {
   if (io != R2L_IO_F32 && io != R2L_IO_BF16 && io != R2L_IO_F16) return 0;
   if (layout != R2L_LAYOUT_NCHW && layout != R2L_LAYOUT_NHWC) return 0;
@@ -1652,74 +1684,48 @@ int r2l_isp_layout_supported(int io, int layout, int raw_u16, int has_additive, 
 int r2l_isp_io_supported(int io, int raw_u16, int has_additive, int B, int H, int W, int phase) {
   return r2l_isp_layout_supported(io, R2L_LAYOUT_NCHW, raw_u16, has_additive, B, H, W, phase);
 }
-// both public forwards and both public backwards share one implementation; `who`: the entry point r2l_last_error() names
-static int r2l_step_fwd_layout_impl(const char* who, const void* raw, int raw_u16, float denom, const float* const* params_host,
-                            const float* additive, int bn_mode, float* running_mean, float* running_var,
-                            long long* num_batches_tracked, double eps, double momentum, void* out, int io, int layout,
-                            void* workspace, size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
-                            const double* gathered_stats, void* stream) {
-  if (int e = r2l_io_check(who, io, layout, out, raw_u16, additive != nullptr, B, H, W, phase)) return e;
-  return r2l_isp_step_fwd_impl(raw, raw_u16, denom, params_host, additive, bn_mode, running_mean, running_var,
-                               num_batches_tracked, eps, momentum, (float*)out, io | (layout == R2L_LAYOUT_NHWC ? R2L_IO_NHWC : 0),
-                               workspace, workspace_bytes, B, H, W, nranks, phase, gathered_stats, stream);
-}
+// the forwards and backwards that take io [and layout]: r2l_step_fwd / r2l_step_bwd above, like the planar float32 entries
 int r2l_isp_step_fwd_layout(const void* raw, int raw_u16, float denom, const float* const* params_host,
                             const float* additive, int bn_mode, float* running_mean, float* running_var,
                             long long* num_batches_tracked, double eps, double momentum, void* out, int io, int layout,
                             void* workspace, size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
                             const double* gathered_stats, void* stream) {
-  return r2l_step_fwd_layout_impl("r2l_isp_step_fwd_layout", raw, raw_u16, denom, params_host, additive, bn_mode, running_mean,
-                                  running_var, num_batches_tracked, eps, momentum, out, io, layout, workspace, workspace_bytes, B,
-                                  H, W, nranks, phase, gathered_stats, stream);
+  return r2l_step_fwd("r2l_isp_step_fwd_layout",
+                      R2LStepFwd{raw, raw_u16, denom, params_host, additive, bn_mode, running_mean, running_var, num_batches_tracked,
+                                 eps, momentum, (float*)out, io, layout, workspace, workspace_bytes, B, H, W, nranks, phase,
+                                 gathered_stats, stream});
 }
 int r2l_isp_step_fwd_io(const void* raw, int raw_u16, float denom, const float* const* params_host,
                         const float* additive, int bn_mode, float* running_mean, float* running_var,
                         long long* num_batches_tracked, double eps, double momentum, void* out, int io, void* workspace,
                         size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
                         const double* gathered_stats, void* stream) {
-  return r2l_step_fwd_layout_impl("r2l_isp_step_fwd_io", raw, raw_u16, denom, params_host, additive, bn_mode, running_mean,
-                                  running_var, num_batches_tracked, eps, momentum, out, io, R2L_LAYOUT_NCHW, workspace,
-                                  workspace_bytes, B, H, W, nranks, phase, gathered_stats, stream);
-}
-static int r2l_step_bwd_layout_impl(const char* who, const void* raw, int raw_u16, float denom, const float* additive, const void* grad_out, int io,
-                            int layout, const void* out, float* grad_params, float* grad_additive, int bn_mode,
-                            void* workspace, size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
-                            const double* gathered_sums, void* stream, float* grad_raw, void* raw_grad_scratch,
-                            size_t raw_grad_scratch_bytes, unsigned grad_mask) {
-  if (io == R2L_IO_F32 && layout == R2L_LAYOUT_NCHW)
-    return r2l_isp_step_bwd_select(raw, raw_u16, denom, additive, (const float*)grad_out, (const float*)out, grad_params,
-                                   grad_additive, bn_mode, workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums,
-                                   stream, grad_raw, raw_grad_scratch, raw_grad_scratch_bytes, grad_mask);
-  if (int e = r2l_io_check(who, io, layout, grad_out, raw_u16, additive != nullptr, B, H, W, phase)) return e;
-  if (grad_mask & ~(unsigned)(R2L_GRAD_ALL_PARAMS | R2L_GRAD_RAW))
-    return r2l_fail(-1, std::string(who) + ": unknown bits in grad_mask");
-  if ((grad_raw != nullptr) != ((grad_mask & R2L_GRAD_RAW) != 0))
-    return r2l_fail(-1, std::string(who) + ": grad_raw goes with R2L_GRAD_RAW in grad_mask");
-  if (grad_mask && !grad_params) return r2l_fail(-1, std::string(who) + ": a gradient is asked for but grad_params is null");
-  const R2LStepBwd q{raw, raw_u16, denom, additive, (const float*)grad_out, (const float*)out, grad_params, grad_additive,
-                     bn_mode, workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream, grad_raw,
-                     (float*)raw_grad_scratch, grad_mask, io | (layout == R2L_LAYOUT_NHWC ? R2L_IO_NHWC : 0)};
-  if (grad_raw)
-    if (int e = r2l_raw_grad_preconditions(q, raw_grad_scratch_bytes)) return e;
-  return r2l_isp_step_bwd_impl(q);
+  return r2l_step_fwd("r2l_isp_step_fwd_io",
+                      R2LStepFwd{raw, raw_u16, denom, params_host, additive, bn_mode, running_mean, running_var, num_batches_tracked,
+                                 eps, momentum, (float*)out, io, R2L_LAYOUT_NCHW, workspace, workspace_bytes, B, H, W, nranks, phase,
+                                 gathered_stats, stream});
 }
 int r2l_isp_step_bwd_layout(const void* raw, int raw_u16, float denom, const float* additive, const void* grad_out, int io,
                             int layout, const void* out, float* grad_params, float* grad_additive, int bn_mode,
                             void* workspace, size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
                             const double* gathered_sums, void* stream, float* grad_raw, void* raw_grad_scratch,
                             size_t raw_grad_scratch_bytes, unsigned grad_mask) {
-  return r2l_step_bwd_layout_impl("r2l_isp_step_bwd_layout", raw, raw_u16, denom, additive, grad_out, io, layout, out, grad_params,
-                                  grad_additive, bn_mode, workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream,
-                                  grad_raw, raw_grad_scratch, raw_grad_scratch_bytes, grad_mask);
+  return r2l_step_bwd("r2l_isp_step_bwd_layout", true,
+                      R2LStepBwd{raw, raw_u16, denom, additive, (const float*)grad_out, (const float*)out, grad_params,
+                                 grad_additive, bn_mode, workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream,
+                                 grad_raw, (float*)raw_grad_scratch, grad_mask, io, layout},
+                      raw_grad_scratch_bytes);
 }
 int r2l_isp_step_bwd_io(const void* raw, int raw_u16, float denom, const float* additive, const void* grad_out, int io,
                         const void* out, float* grad_params, float* grad_additive, int bn_mode, void* workspace,
                         size_t workspace_bytes, int B, int H, int W, int nranks, int phase,
                         const double* gathered_sums, void* stream, float* grad_raw, void* raw_grad_scratch,
                         size_t raw_grad_scratch_bytes, unsigned grad_mask) {
-  return r2l_step_bwd_layout_impl("r2l_isp_step_bwd_io", raw, raw_u16, denom, additive, grad_out, io, R2L_LAYOUT_NCHW, out,
-                                  grad_params, grad_additive, bn_mode, workspace, workspace_bytes, B, H, W, nranks, phase,
-                                  gathered_sums, stream, grad_raw, raw_grad_scratch, raw_grad_scratch_bytes, grad_mask);
+  return r2l_step_bwd("r2l_isp_step_bwd_io", true,
+                      R2LStepBwd{raw, raw_u16, denom, additive, (const float*)grad_out, (const float*)out, grad_params,
+                                 grad_additive, bn_mode, workspace, workspace_bytes, B, H, W, nranks, phase, gathered_sums, stream,
+                                 grad_raw, (float*)raw_grad_scratch, grad_mask, io, R2L_LAYOUT_NCHW},
+                      raw_grad_scratch_bytes);
 }
 
 static int r2l_raw2rgb_fwd_impl(const R2LRaw& raw, const float* black_level, float* out, int B, int H, int W,
@@ -2191,38 +2197,55 @@ static int r2l_static_launch(const R2LStaticPlan& p, const R2LStaticArgs& a, voi
   }
 }
 
-static int r2l_static_fwd_impl(const R2LRaw& raw, float* out, int B, int H, int W, const double* camera_host,
-                               int debayer, int sharpening, int denoising, double gamma, void* workspace,
-                               size_t workspace_bytes, void* stream, const float* mean_std_host = nullptr,
-                               const R2LStaticOpts& opt = R2LStaticOpts(), int io = R2L_IO_F32) {
-  // (io != R2L_IO_F32: `out` points to 2-byte elements and r2l_static_io_why has said that a 16-bit kernel serves the call)
-  if (int e = r2l_check_dims(B, H, W)) return e;
-  if (int e = r2l_check_raw(raw, W, "r2l_static_fwd")) return e;
-  if (mean_std_host)
+// the six r2l_static_fwd* entries: one implementation, what they ask of it
+struct R2LStaticCall {
+  const void* raw;  // the frames as the entries take them: pointer, R2L_FRAMES_*, denom (read for 16-bit containers)
+  int frames;
+  float denom;
+  float* out;  // (io != R2L_IO_F32: 2-byte elements, and r2l_static_io_why has said that a 16-bit kernel serves the call)
+  int io, B, H, W;
+  const double* camera_host;
+  int debayer, sharpening, denoising;
+  double gamma;
+  const float* mean_std_host;  // or null
+  R2LStaticOpts opt;
+  void* workspace;
+  size_t workspace_bytes;
+  void* stream;
+};
+static int r2l_static_fwd_impl(const R2LStaticCall& c) {
+  if (c.frames != R2L_FRAMES_F32 && c.frames != R2L_FRAMES_U16 && c.frames != R2L_FRAMES_F64)
+    return r2l_fail(-1, "r2l_static_fwd_norm: frames must be R2L_FRAMES_F32, _U16 or _F64");
+  const R2LRaw raw = c.frames == R2L_FRAMES_F64 ? r2l_raw_f64((const double*)c.raw)
+                                                : r2l_raw_any(c.raw, c.frames == R2L_FRAMES_U16, c.denom);
+  if (int e = r2l_check_dims(c.B, c.H, c.W)) return e;
+  if (int e = r2l_check_raw(raw, c.W, "r2l_static_fwd")) return e;
+  if (c.mean_std_host)
     for (int k = 0; k < 3; ++k)
-      if (!(mean_std_host[3 + k] != 0.f)) return r2l_fail(-1, "r2l_static_fwd_norm: std must be non-zero");
-  if (!out || !camera_host) return r2l_fail(-1, "r2l_static_fwd: null pointer");
-  if (debayer != R2L_DEBAYER_BILINEAR && debayer != R2L_DEBAYER_MALVAR2004 && debayer != R2L_DEBAYER_MENON2007)
+      if (!(c.mean_std_host[3 + k] != 0.f)) return r2l_fail(-1, "r2l_static_fwd_norm: std must be non-zero");
+  if (!c.out || !c.camera_host) return r2l_fail(-1, "r2l_static_fwd: null pointer");
+  if (c.debayer != R2L_DEBAYER_BILINEAR && c.debayer != R2L_DEBAYER_MALVAR2004 && c.debayer != R2L_DEBAYER_MENON2007)
     return r2l_fail(-1, "r2l_static_fwd: unknown debayer");
-  if (sharpening != R2L_SHARPEN_NONE && sharpening != R2L_SHARPEN_FILTER && sharpening != R2L_SHARPEN_UNSHARP)
+  if (c.sharpening != R2L_SHARPEN_NONE && c.sharpening != R2L_SHARPEN_FILTER && c.sharpening != R2L_SHARPEN_UNSHARP)
     return r2l_fail(-1, "r2l_static_fwd: unknown sharpening");
-  if (denoising != R2L_DENOISE_NONE && denoising != R2L_DENOISE_GAUSSIAN && denoising != R2L_DENOISE_MEDIAN &&
-      denoising != R2L_DENOISE_FFT)
+  if (c.denoising != R2L_DENOISE_NONE && c.denoising != R2L_DENOISE_GAUSSIAN && c.denoising != R2L_DENOISE_MEDIAN &&
+      c.denoising != R2L_DENOISE_FFT)
     return r2l_fail(-4, "r2l_static_fwd: denoising must be none, gaussian_denoising, median_denoising or fft_denoising");
-  if (!(gamma > 0)) return r2l_fail(-1, "r2l_static_fwd: gamma must be > 0");
-  if (const char* why = r2l_static_opts_problem(opt, sharpening, denoising)) return r2l_fail(-4, std::string("r2l_static_fwd: ") + why);
+  if (!(c.gamma > 0)) return r2l_fail(-1, "r2l_static_fwd: gamma must be > 0");
+  if (const char* why = r2l_static_opts_problem(c.opt, c.sharpening, c.denoising))
+    return r2l_fail(-4, std::string("r2l_static_fwd: ") + why);
   R2LStaticArgs a;
-  r2l_static_setup(a, raw, out, B, H, W, camera_host, debayer, sharpening, denoising, gamma, mean_std_host, opt);
-  const int frames = raw.u16 ? R2L_FRAMES_U16 : (raw.f64 ? R2L_FRAMES_F64 : R2L_FRAMES_F32);
-  const R2LStaticPlan p = r2l_static_plan(frames, B, H, W, debayer, sharpening, denoising, opt, io);
-  if (io != R2L_IO_F32 && p.no_io)
+  r2l_static_setup(a, raw, c.out, c.B, c.H, c.W, c.camera_host, c.debayer, c.sharpening, c.denoising, c.gamma, c.mean_std_host,
+                   c.opt);
+  const R2LStaticPlan p = r2l_static_plan(c.frames, c.B, c.H, c.W, c.debayer, c.sharpening, c.denoising, c.opt, c.io);
+  if (c.io != R2L_IO_F32 && p.no_io)
     return r2l_fail(-3, "r2l_static_fwd_io: no 16-bit form of the kernels this call takes (r2l_static_io_supported)");
   if (p.refused) return r2l_fail(-4, p.refused);
   if (p.err) return p.err;
-  if (p.workspace_bytes && (!workspace || workspace_bytes < p.workspace_bytes))
+  if (p.workspace_bytes && (!c.workspace || c.workspace_bytes < p.workspace_bytes))
     return r2l_fail(-2, "r2l_static_fwd: workspace too small (r2l_static_workspace_bytes)");
   if (p.too_large) return r2l_fail(-1, "r2l_static_fwd: batch too large");
-  return r2l_static_launch(p, a, workspace, stream);
+  return r2l_static_launch(p, a, c.workspace, c.stream);
 }
 
 int r2l_isp_fwd(const float* raw, const float* params, const float* additive,
@@ -2291,70 +2314,49 @@ int r2l_raw2rgb_fwd_u16(const unsigned short* raw, float denom, const float* bla
   return r2l_raw2rgb_fwd_impl(r2l_raw_u16(raw, denom), black_level, out, B, H, W, reduce_size, out_channels,
                               stream);
 }
-static size_t r2l_static_ws(int frames, int B, int H, int W, int debayer, int sharpening, int denoising,
-                            const R2LStaticOpts& opt = R2LStaticOpts()) {
-  return r2l_static_plan(frames, B, H, W, debayer, sharpening, denoising, opt, R2L_IO_F32).workspace_bytes;
-}
 size_t r2l_static_workspace_bytes(int B, int H, int W, int debayer, int sharpening, int denoising) {
-  return r2l_static_ws(R2L_FRAMES_F32, B, H, W, debayer, sharpening, denoising);
+  return r2l_static_plan(R2L_FRAMES_F32, B, H, W, debayer, sharpening, denoising, R2LStaticOpts(), R2L_IO_F32)
+      .workspace_bytes;
 }
 size_t r2l_static_workspace_bytes_f64(int B, int H, int W, int debayer, int sharpening, int denoising) {
-  return r2l_static_ws(R2L_FRAMES_F64, B, H, W, debayer, sharpening, denoising);
+  return r2l_static_plan(R2L_FRAMES_F64, B, H, W, debayer, sharpening, denoising, R2LStaticOpts(), R2L_IO_F32)
+      .workspace_bytes;
 }
 size_t r2l_static_workspace_bytes_opts(int frames, int B, int H, int W, int debayer, int sharpening, int denoising,
                                        const double* options_host) {
-  return r2l_static_ws(frames, B, H, W, debayer, sharpening, denoising, r2l_static_opts(options_host, 3));
+  return r2l_static_plan(frames, B, H, W, debayer, sharpening, denoising, r2l_static_opts(options_host, 3), R2L_IO_F32)
+      .workspace_bytes;
 }
 int r2l_static_fwd_f64(const double* raw, float* out, int B, int H, int W, const double* camera_host,
                        int debayer, int sharpening, int denoising, double gamma, void* workspace,
                        size_t workspace_bytes, void* stream) {
-  return r2l_static_fwd_impl(r2l_raw_f64(raw), out, B, H, W, camera_host, debayer, sharpening, denoising, gamma,
-                             workspace, workspace_bytes, stream);
+  return r2l_static_fwd_impl(R2LStaticCall{raw, R2L_FRAMES_F64, 1.f, out, R2L_IO_F32, B, H, W, camera_host, debayer, sharpening,
+                                           denoising, gamma, nullptr, R2LStaticOpts(), workspace, workspace_bytes, stream});
 }
 int r2l_static_fwd(const float* raw, float* out, int B, int H, int W, const double* camera_host,
                    int debayer, int sharpening, int denoising, double gamma, void* workspace,
                    size_t workspace_bytes, void* stream) {
-  return r2l_static_fwd_impl(r2l_raw_f32(raw), out, B, H, W, camera_host, debayer, sharpening, denoising, gamma,
-                             workspace, workspace_bytes, stream);
+  return r2l_static_fwd_impl(R2LStaticCall{raw, R2L_FRAMES_F32, 1.f, out, R2L_IO_F32, B, H, W, camera_host, debayer, sharpening,
+                                           denoising, gamma, nullptr, R2LStaticOpts(), workspace, workspace_bytes, stream});
 }
 int r2l_static_fwd_u16(const unsigned short* raw, float denom, float* out, int B, int H, int W,
                        const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
                        void* workspace, size_t workspace_bytes, void* stream) {
-  return r2l_static_fwd_impl(r2l_raw_u16(raw, denom), out, B, H, W, camera_host, debayer, sharpening, denoising,
-                             gamma, workspace, workspace_bytes, stream);
+  return r2l_static_fwd_impl(R2LStaticCall{raw, R2L_FRAMES_U16, denom, out, R2L_IO_F32, B, H, W, camera_host, debayer, sharpening,
+                                           denoising, gamma, nullptr, R2LStaticOpts(), workspace, workspace_bytes, stream});
 }
-static int r2l_static_fwd_any(const void* raw, int frames, float denom, float* out, int B, int H, int W,
-                              const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
-                              const float* mean_std_host, const R2LStaticOpts& opt, void* workspace, size_t workspace_bytes,
-                              void* stream, int io = R2L_IO_F32);
 int r2l_static_fwd_norm(const void* raw, int frames, float denom, float* out, int B, int H, int W,
                         const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
                         const float* mean_std_host, void* workspace, size_t workspace_bytes, void* stream) {
-  return r2l_static_fwd_any(raw, frames, denom, out, B, H, W, camera_host, debayer, sharpening, denoising, gamma, mean_std_host,
-                            R2LStaticOpts(), workspace, workspace_bytes, stream);
+  return r2l_static_fwd_impl(R2LStaticCall{raw, frames, denom, out, R2L_IO_F32, B, H, W, camera_host, debayer, sharpening, denoising,
+                                           gamma, mean_std_host, R2LStaticOpts(), workspace, workspace_bytes, stream});
 }
 int r2l_static_fwd_opts(const void* raw, int frames, float denom, float* out, int B, int H, int W,
                         const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
                         const double* options_host, const float* mean_std_host, void* workspace, size_t workspace_bytes,
                         void* stream) {
-  return r2l_static_fwd_any(raw, frames, denom, out, B, H, W, camera_host, debayer, sharpening, denoising, gamma, mean_std_host,
-                            r2l_static_opts(options_host), workspace, workspace_bytes, stream);
-}
-static int r2l_static_fwd_any(const void* raw, int frames, float denom, float* out, int B, int H, int W,
-                              const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
-                              const float* mean_std_host, const R2LStaticOpts& opt, void* workspace, size_t workspace_bytes,
-                              void* stream, int io) {
-  R2LRaw rw;
-  if (frames == R2L_FRAMES_F32)
-    rw = r2l_raw_f32((const float*)raw);
-  else if (frames == R2L_FRAMES_U16)
-    rw = r2l_raw_u16((const unsigned short*)raw, denom);
-  else if (frames == R2L_FRAMES_F64)
-    rw = r2l_raw_f64((const double*)raw);
-  else
-    return r2l_fail(-1, "r2l_static_fwd_norm: frames must be R2L_FRAMES_F32, _U16 or _F64");
-  return r2l_static_fwd_impl(rw, out, B, H, W, camera_host, debayer, sharpening, denoising, gamma, workspace,
-                             workspace_bytes, stream, mean_std_host, opt, io);
+  return r2l_static_fwd_impl(R2LStaticCall{raw, frames, denom, out, R2L_IO_F32, B, H, W, camera_host, debayer, sharpening, denoising,
+                                           gamma, mean_std_host, r2l_static_opts(options_host), workspace, workspace_bytes, stream});
 }
 
 // ---- 16-bit output of the static chains (include/r2l_isp.h: r2l_static_fwd_io) -------------------------------------------------
@@ -2369,16 +2371,16 @@ int r2l_static_fwd_io(const void* raw, int frames, float denom, void* out, int o
                       const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
                       const double* options_host, const float* mean_std_host, void* workspace, size_t workspace_bytes,
                       void* stream) {
-  if (out_io == R2L_IO_F32)
-    return r2l_static_fwd_opts(raw, frames, denom, (float*)out, B, H, W, camera_host, debayer, sharpening, denoising, gamma,
-                               options_host, mean_std_host, workspace, workspace_bytes, stream);
-  if (out_io != R2L_IO_BF16 && out_io != R2L_IO_F16) return r2l_fail(-1, "r2l_static_fwd_io: out_io must be one of R2L_IO_*");
-  const R2LStaticOpts o = r2l_static_opts(options_host);
-  if (const char* why = r2l_static_io_why(frames, H, W, debayer, sharpening, denoising, o))
-    return r2l_fail(-3, std::string("r2l_static_fwd_io: a 16-bit output is not served here: ") + why);
-  if ((uintptr_t)out % 8) return r2l_fail(-1, "r2l_static_fwd_io: the 16-bit output must be 8-byte aligned");
-  return r2l_static_fwd_any(raw, frames, denom, (float*)out, B, H, W, camera_host, debayer, sharpening, denoising, gamma,
-                            mean_std_host, o, workspace, workspace_bytes, stream, out_io);
+  if (out_io != R2L_IO_F32 && out_io != R2L_IO_BF16 && out_io != R2L_IO_F16)
+    return r2l_fail(-1, "r2l_static_fwd_io: out_io must be one of R2L_IO_*");
+  const R2LStaticCall c{raw, frames, denom, (float*)out, out_io, B, H, W, camera_host, debayer, sharpening, denoising, gamma, mean_std_host,
+                  r2l_static_opts(options_host), workspace, workspace_bytes, stream};
+  if (out_io != R2L_IO_F32) {
+    if (const char* why = r2l_static_io_why(frames, H, W, debayer, sharpening, denoising, c.opt))
+      return r2l_fail(-3, std::string("r2l_static_fwd_io: a 16-bit output is not served here: ") + why);
+    if ((uintptr_t)out % 8) return r2l_fail(-1, "r2l_static_fwd_io: the 16-bit output must be 8-byte aligned");
+  }
+  return r2l_static_fwd_impl(c);
 }
 
 // ---- staged (track_stages=True) entry points -------------------------------------------------------

@@ -313,7 +313,7 @@ _STEP_EPI_HFLIP, _STEP_EPI_VFLIP, _STEP_EPI_ROT_SHIFT = 16, 32, 6       # output
 
 
 def epilogue_bits(epilogue):
-    """(hflip, vflip, k) -> the bits r2l_isp_step_fwd / _bwd take in `phase` (include/r2l_isp.h: R2L_STEP_EPI_*)"""
+    """(hflip, vflip, k) -> the bits the step's calls take in `phase` (include/r2l_isp.h: R2L_STEP_EPI_*)"""
     if not epilogue:
         return 0
     hflip, vflip, k = epilogue
@@ -331,16 +331,19 @@ IO_F32, IO_BF16, IO_F16 = 0, 1, 2
 IO_CODES = {None: IO_F32, torch.float32: IO_F32, torch.bfloat16: IO_BF16, torch.float16: IO_F16}
 
 
-def io_supported(raw, module, dtype=None, keep=None):
-    """do the fused kernels write this module's output directly as `dtype` (default: module.output_dtype) for these frames
-    (r2l_isp_io_supported, the predicate r2l_isp_step_fwd_io / _bwd_io use)?  float32 / None: always.  A 16-bit type: no
-    additive layer, W % 4 == 0, W <= 2048, and a step whose backward will run (`keep`; default: grad mode is on and the frames or
-    a parameter require grad) -- elsewhere ParametrizedProcessing runs the float32 kernels and casts."""
+# the memory layouts of that output / cotangent (include/r2l_isp.h: R2L_LAYOUT_*)
+LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
+LAYOUT_CODES = {None: LAYOUT_NCHW, torch.contiguous_format: LAYOUT_NCHW, torch.channels_last: LAYOUT_NHWC}
+
+
+def _served(raw, module, dtype, layout, keep):
+    """io_supported and layout_supported: the library's answer (r2l_isp_layout_supported) for `dtype` (default:
+    module.output_dtype) in `layout` (LAYOUT_*)"""
     dtype = getattr(module, 'output_dtype', None) if dtype is None else dtype
     if dtype not in IO_CODES:
         raise _lib.R2LError(f'output_dtype must be None, torch.float32, torch.bfloat16 or torch.float16, got {dtype!r}')
     io = IO_CODES[dtype]
-    if io == IO_F32:
+    if io == IO_F32 and layout == LAYOUT_NCHW:
         return True
     if raw.ndim != 3 or not (raw.dtype == torch.float32 or raw.dtype in U16_DTYPES):
         return False
@@ -350,13 +353,16 @@ def io_supported(raw, module, dtype=None, keep=None):
             module.sharpening_filter.weight, module.gaussian_blur.weight)))
     lib, _ = _lib.library_for(raw)
     B, H, W = raw.shape
-    return bool(lib.r2l_isp_io_supported(io, int(raw.dtype in U16_DTYPES), int(module.additive_layer is not None), B, H, W,
-                                         _STEP_KEEP_LUMA if keep else 0))
+    return bool(lib.r2l_isp_layout_supported(io, layout, int(raw.dtype in U16_DTYPES), int(module.additive_layer is not None),
+                                             B, H, W, _STEP_KEEP_LUMA if keep else 0))
 
 
-# the memory layouts of that output / cotangent (include/r2l_isp.h: R2L_LAYOUT_*)
-LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
-LAYOUT_CODES = {None: LAYOUT_NCHW, torch.contiguous_format: LAYOUT_NCHW, torch.channels_last: LAYOUT_NHWC}
+def io_supported(raw, module, dtype=None, keep=None):
+    """do the fused kernels write this module's output directly as `dtype` (default: module.output_dtype) for these frames
+    (r2l_isp_layout_supported, the predicate r2l_isp_step_fwd_layout / _bwd_layout use)?  float32 / None: always.  A 16-bit type: no
+    additive layer, W % 4 == 0, W <= 2048, and a step whose backward will run (`keep`; default: grad mode is on and the frames or
+    a parameter require grad) -- elsewhere ParametrizedProcessing runs the float32 kernels and casts."""
+    return _served(raw, module, dtype, LAYOUT_NCHW, keep)
 
 
 def layout_supported(raw, module, memory_format=None, dtype=None, keep=None):
@@ -369,25 +375,11 @@ def layout_supported(raw, module, memory_format=None, dtype=None, keep=None):
     if memory_format not in LAYOUT_CODES:
         raise _lib.R2LError(f'output_memory_format must be None, torch.contiguous_format or torch.channels_last, '
                             f'got {memory_format!r}')
-    if LAYOUT_CODES[memory_format] == LAYOUT_NCHW:
-        return io_supported(raw, module, dtype, keep)
-    dtype = getattr(module, 'output_dtype', None) if dtype is None else dtype
-    if dtype not in IO_CODES:
-        raise _lib.R2LError(f'output_dtype must be None, torch.float32, torch.bfloat16 or torch.float16, got {dtype!r}')
-    if raw.ndim != 3 or not (raw.dtype == torch.float32 or raw.dtype in U16_DTYPES):
-        return False
-    if keep is None:
-        keep = torch.is_grad_enabled() and (raw.requires_grad or any(p.requires_grad for p in (
-            module.black_level, module.white_balance, module.colour_correction, module.gamma_correct, module.debayer.weight,
-            module.sharpening_filter.weight, module.gaussian_blur.weight)))
-    lib, _ = _lib.library_for(raw)
-    B, H, W = raw.shape
-    return bool(lib.r2l_isp_layout_supported(IO_CODES[dtype], LAYOUT_NHWC, int(raw.dtype in U16_DTYPES),
-                                             int(module.additive_layer is not None), B, H, W, _STEP_KEEP_LUMA if keep else 0))
+    return _served(raw, module, dtype, LAYOUT_CODES[memory_format], keep)
 
 
 def _raw_grad_why(f32, W, has_additive, epi=False):
-    """why r2l_isp_step_bwd_raw cannot produce d/d raw for such a call, or None if it can"""
+    """why the fused backward cannot produce d/d raw for such a call, or None if it can"""
     if epi:
         return 'the fused ISP kernels do not produce d/d raw with an output epilogue'
     if not f32:
@@ -404,14 +396,14 @@ def raw_grad_supported(raw, module):
     return _raw_grad_why(raw.dtype == torch.float32, raw.shape[-1], module.additive_layer is not None) is None
 
 
-# one bit per gradient of r2l_isp_step_bwd_select (include/r2l_isp.h: R2L_GRAD_*), in the order of _IspFused.forward's inputs:
+# one bit per gradient in the backward's grad_mask (include/r2l_isp.h: R2L_GRAD_*), in the order of _IspFused.forward's inputs:
 # raw, black_level, white_balance, colour_correction, gamma_correct, debayer.weight, sharpening_filter.weight, gaussian_blur.weight
 GRAD_RAW = 128
 _GRAD_BITS = (GRAD_RAW, 1, 2, 4, 8, 16, 32, 64)
 
 
 def grad_mask(needs_input_grad):
-    """autograd's needs_input_grad[0:8] of _IspFused -> the grad_mask of r2l_isp_step_bwd_select"""
+    """autograd's needs_input_grad[0:8] of _IspFused -> the grad_mask of r2l_isp_step_bwd_layout"""
     return sum(bit for bit, need in zip(_GRAD_BITS, needs_input_grad[:8]) if need)
 
 
@@ -432,19 +424,19 @@ def _step_layout(lib, B, H, W):
 
 class _IspFused(torch.autograd.Function):
     """out = f(raw, 7 parameter tensors, M_RGB_2_YUV, M_YUV_2_RGB, additive | None, ...): one C-ABI call for the
-    forward (r2l_isp_step_fwd: parameter gather + fold, BatchNorm statistics pass + bookkeeping, apply pass) and one
-    for the backward (r2l_isp_step_bwd: BatchNorm backward sums, both gradient kernels, additive-layer gradient).
+    forward (r2l_isp_step_fwd_layout: parameter gather + fold, BatchNorm statistics pass + bookkeeping, apply pass) and one
+    for the backward (r2l_isp_step_bwd_layout: BatchNorm backward sums, both gradient kernels, additive-layer gradient), whatever
+    the element type and layout of the output.
     The workspace tensor carries the step's state (packed parameters as the forward saw them, folded weights,
     BatchNorm constants) from one to the other; backward hands each parameter a view of the single 132-float
     gradient the kernels produce.  With several ranks and train-mode BatchNorm each call splits in two around an
     all-gather of 7 resp. 6 doubles (RCCL).  selective (ParametrizedProcessing.selective_backward): the backward hands
-    needs_input_grad to the library (r2l_isp_step_bwd_select), which runs reduced passes where only the gamma, blur or raw
+    needs_input_grad to the library as its grad_mask, which runs reduced passes where only the gamma, blur or raw
     gradients are asked for; parameters that did not ask get None either way.  out_dtype (ParametrizedProcessing.output_dtype):
     torch.bfloat16 / torch.float16 -- `out` is allocated and written in that type and the cotangent is read in it
-    (r2l_isp_step_fwd_io / r2l_isp_step_bwd_io; the caller has asked io_supported); None / torch.float32: the calls above.
+    (the caller has asked io_supported); None / torch.float32: planar float32.
     out_layout (ParametrizedProcessing.output_memory_format): torch.channels_last -- `out` has channels-last strides and the
-    cotangent is read in them, in float32 or 16 bits (r2l_isp_step_fwd_layout / r2l_isp_step_bwd_layout; the caller has asked
-    layout_supported); None / torch.contiguous_format: the calls above."""
+    cotangent is read in them, in float32 or 16 bits (the caller has asked layout_supported)."""
 
     @staticmethod
     def forward(ctx, raw, bl, wb, ccm, gamma, deb, sharp, blur, m1, m2, additive, bn_mode, bn_module, eps,
@@ -502,23 +494,13 @@ class _IspFused(torch.autograd.Function):
         # (needs_input_grad is also set under torch.no_grad(); grad_mode is the caller's torch.is_grad_enabled())
         keep = _STEP_KEEP_LUMA if (grad_mode and any(ctx.needs_input_grad[:8])) else 0
 
+        layout = LAYOUT_NHWC if nhwc else LAYOUT_NCHW
+
         def call(phase, gathered):
-            if nhwc:
-                lib.check(lib.r2l_isp_step_fwd_layout(ptr(raw), int(denom is not None), denom or 1.0, table, ptr(additive),
-                                                      bn_mode, ptr(rm), ptr(rv), ptr(nbt), float(eps), mom, ptr(out), io,
-                                                      LAYOUT_NHWC, ptr(ws), nws, B, H, W, nranks, phase | keep | epi,
-                                                      ptr(gathered), stream), 'r2l_isp_step_fwd_layout')
-                return
-            if io:
-                lib.check(lib.r2l_isp_step_fwd_io(ptr(raw), int(denom is not None), denom or 1.0, table, ptr(additive),
-                                                  bn_mode, ptr(rm), ptr(rv), ptr(nbt), float(eps), mom, ptr(out), io, ptr(ws),
-                                                  nws, B, H, W, nranks, phase | keep | epi, ptr(gathered), stream),
-                          'r2l_isp_step_fwd_io')
-                return
-            lib.check(lib.r2l_isp_step_fwd(ptr(raw), int(denom is not None), denom or 1.0, table, ptr(additive),
-                                           bn_mode, ptr(rm), ptr(rv), ptr(nbt), float(eps), mom, ptr(out), ptr(ws),
-                                           nws, B, H, W, nranks, phase | keep | epi, ptr(gathered), stream),
-                      'r2l_isp_step_fwd')
+            lib.check(lib.r2l_isp_step_fwd_layout(ptr(raw), int(denom is not None), denom or 1.0, table, ptr(additive),
+                                                  bn_mode, ptr(rm), ptr(rv), ptr(nbt), float(eps), mom, ptr(out), io, layout,
+                                                  ptr(ws), nws, B, H, W, nranks, phase | keep | epi, ptr(gathered), stream),
+                      'r2l_isp_step_fwd_layout')
         split = nranks > 1 or (bn_mode == BN_TRAIN and split_single_rank(group))
         if not split:
             call(_STEP_ALL, None)
@@ -580,38 +562,17 @@ class _IspFused(torch.autograd.Function):
             nscr = lib.r2l_isp_raw_grad_scratch_bytes(B, H, W)
             scratch = torch.empty(nscr, dtype=torch.uint8, device=raw.device)
 
-        mask = grad_mask(ctx.needs_input_grad) if ctx.selective else 0
+        # selective: what was asked for.  Otherwise every parameter gradient (+ d/d raw) wherever the gradient kernels run: a mask
+        # the library has no reduced route for, so it runs the full one (r2l_bwd_plan); only the additive gradient: 0
+        mask = (grad_mask(ctx.needs_input_grad) if ctx.selective else 0) or \
+            ((GRAD_RAW if need_r else 0) | (127 if (need_p or need_r) else 0))
+        layout = LAYOUT_NHWC if ctx.nhwc else LAYOUT_NCHW
 
         def call(phase, gathered):
-            if ctx.nhwc:    # (as a 16-bit call: the full route for any mask)
-                m = mask or ((GRAD_RAW if need_r else 0) | (127 if (need_p or need_r) else 0))
-                lib.check(lib.r2l_isp_step_bwd_layout(ptr(raw), int(denom is not None), denom or 1.0, ptr(additive), ptr(gout),
-                                                      ctx.io, LAYOUT_NHWC, ptr(out), ptr(gp), ptr(gadd), ctx.bn_mode, ptr(ws),
-                                                      nws, B, H, W, ctx.nranks, phase | ctx.keep, ptr(gathered), stream,
-                                                      ptr(graw), ptr(scratch), nscr, m), 'r2l_isp_step_bwd_layout')
-                return
-            if ctx.io:      # (the library runs the full route for any mask; grad_raw goes with GRAD_RAW)
-                m = mask or ((GRAD_RAW if need_r else 0) | (127 if (need_p or need_r) else 0))
-                lib.check(lib.r2l_isp_step_bwd_io(ptr(raw), int(denom is not None), denom or 1.0, ptr(additive), ptr(gout),
-                                                  ctx.io, ptr(out), ptr(gp), ptr(gadd), ctx.bn_mode, ptr(ws), nws, B, H, W,
-                                                  ctx.nranks, phase | ctx.keep, ptr(gathered), stream, ptr(graw),
-                                                  ptr(scratch), nscr, m), 'r2l_isp_step_bwd_io')
-                return
-            if mask:
-                lib.check(lib.r2l_isp_step_bwd_select(ptr(raw), int(denom is not None), denom or 1.0, ptr(additive), ptr(gout),
-                                                      ptr(out), ptr(gp), ptr(gadd), ctx.bn_mode, ptr(ws), nws, B, H, W,
-                                                      ctx.nranks, phase | ctx.keep, ptr(gathered), stream, ptr(graw),
-                                                      ptr(scratch), nscr, mask), 'r2l_isp_step_bwd_select')
-                return
-            if need_r:
-                lib.check(lib.r2l_isp_step_bwd_raw(ptr(raw), 0, 1.0, ptr(additive), ptr(gout), ptr(out), ptr(gp),
-                                                   ptr(gadd), ctx.bn_mode, ptr(ws), nws, B, H, W, ctx.nranks,
-                                                   phase | ctx.keep, ptr(gathered), stream, ptr(graw), ptr(scratch),
-                                                   nscr), 'r2l_isp_step_bwd_raw')
-                return
-            lib.check(lib.r2l_isp_step_bwd(ptr(raw), int(denom is not None), denom or 1.0, ptr(additive), ptr(gout),
-                                           ptr(out), ptr(gp), ptr(gadd), ctx.bn_mode, ptr(ws), nws, B, H, W,
-                                           ctx.nranks, phase | ctx.keep, ptr(gathered), stream), 'r2l_isp_step_bwd')
+            lib.check(lib.r2l_isp_step_bwd_layout(ptr(raw), int(denom is not None), denom or 1.0, ptr(additive), ptr(gout),
+                                                  ctx.io, layout, ptr(out), ptr(gp), ptr(gadd), ctx.bn_mode, ptr(ws), nws, B, H, W,
+                                                  ctx.nranks, phase | ctx.keep, ptr(gathered), stream, ptr(graw), ptr(scratch),
+                                                  nscr, mask), 'r2l_isp_step_bwd_layout')
         if need_p or need_a or need_r:
             if not ctx.split:
                 call(_STEP_ALL, None)
@@ -659,14 +620,14 @@ def static_pipeline(raw, camera_parameters, debayer='bilinear', sharpening='shar
                     median_kernel_size=3, gaussian_sigma=0.5, fft_fraction=0.3, out_dtype=None):
     """(B,H,W) raw on the GPU -> (B,3,H,W) float32, numpy semantics of the reference.
 
-    out_dtype = torch.bfloat16 / torch.float16 (opt-in; None and torch.float32: today's call): the result is
+    out_dtype = torch.bfloat16 / torch.float16 (opt-in; None and torch.float32: a float32 result): the result is
     float32_result.to(out_dtype) bit for bit.  Where one row-streaming kernel runs the chain (r2l_static_io_supported:
     bilinear / Malvar2004, W % 4 == 0, W <= 2048, no fft_denoising, no 5x5 median, float64 frames on the short chain only) that
-    kernel rounds its float32 values to the 16-bit type itself and stores 6 instead of 12 bytes per pixel (r2l_static_fwd_io);
-    everywhere else the float32 call runs and torch casts.
+    kernel rounds its float32 values to the 16-bit type itself and stores 6 instead of 12 bytes per pixel;
+    everywhere else the float32 call runs and torch casts.  Every call is one r2l_static_fwd_io.
 
     sharp_radius, sharp_amount, median_kernel_size, gaussian_sigma, fft_fraction: processing()'s numeric arguments
-    (pipeline_numpy.py:70-73, used at :117-122), launch arguments of the kernels (r2l_static_fwd_opts).  What the kernels'
+    (pipeline_numpy.py:70-73, used at :117-122), launch arguments of the kernels (r2l_static_fwd_io's options).  What the kernels'
     windows hold bounds them: gaussian_sigma in (0, 0.625), sharp_radius in (0, 1.125), fft_fraction in [0, 0.5],
     median_kernel_size 3 or 5 (5: the chain runs as luma-plane passes, W % 4 == 0) -- other values of an option the chain USES raise R2LError with the reason; an option of a stage the
     chain does not run is ignored like the reference's if-chains ignore it.
@@ -711,42 +672,21 @@ def static_pipeline(raw, camera_parameters, debayer='bilinear', sharpening='shar
     codes = (_DEBAYER[debayer], _SHARPEN.get(sharpening, 0), _DENOISE.get(denoising, 0))
     opts = dict(sharp_radius=sharp_radius, sharp_amount=sharp_amount, gaussian_sigma=gaussian_sigma,
                 fft_fraction=fft_fraction, median_kernel_size=median_kernel_size)
-    custom = opts != STATIC_OPTION_DEFAULTS
+    # R2L_SOPT_* order (include/r2l_isp.h); NULL: the reference's defaults
+    ov = (ctypes.c_double * 5)(float(sharp_radius), float(sharp_amount), float(gaussian_sigma), float(fft_fraction),
+                               float(median_kernel_size)) if opts != STATIC_OPTION_DEFAULTS else None
+    ms = (ctypes.c_float * 6)(*[float(v) for v in mean_std]) if mean_std is not None else None
     frames = 2 if f64 else (0 if denom is None else 1)
-    if IO_CODES[out_dtype] != IO_F32:
-        ov = (ctypes.c_double * 5)(float(sharp_radius), float(sharp_amount), float(gaussian_sigma), float(fft_fraction),
-                                   float(median_kernel_size)) if custom else None
-        if lib.r2l_static_io_supported(frames, H, W, *codes, ov) is None:        # (NULL: served; otherwise the reason)
-            out = torch.empty((B, 3, H, W), dtype=out_dtype, device=raw.device)
-            ms = (ctypes.c_float * 6)(*[float(v) for v in mean_std]) if mean_std is not None else None
-            lib.check(lib.r2l_static_fwd_io(ptr(raw), frames, float(denom or 1.0), ptr(out), IO_CODES[out_dtype], B, H, W, cam,
-                                            *codes, float(gamma), ov, ms, None, 0, stream), 'r2l_static_fwd_io')
-            return out
-        # no 16-bit form of the kernels this call takes: today's float32 call below, narrowed by torch -- the same values
-    out = torch.empty((B, 3, H, W), dtype=torch.float32, device=raw.device)
-    if custom:
-        ov = (ctypes.c_double * 5)(float(sharp_radius), float(sharp_amount), float(gaussian_sigma), float(fft_fraction),
-                                   float(median_kernel_size))         # R2L_SOPT_* order (include/r2l_isp.h)
-        nws = lib.r2l_static_workspace_bytes_opts(frames, B, H, W, *codes, ov)     # (a 5x5 median runs as plane passes)
-    else:
-        nws = (lib.r2l_static_workspace_bytes_f64 if f64 else lib.r2l_static_workspace_bytes)(B, H, W, *codes)
+    io = IO_CODES[out_dtype]
+    # a 16-bit output: written by the kernels where they have a 16-bit form of this call (NULL: served; otherwise the reason);
+    # elsewhere the float32 call, narrowed by torch -- the same values
+    direct = io != IO_F32 and lib.r2l_static_io_supported(frames, H, W, *codes, ov) is None
+    out = torch.empty((B, 3, H, W), dtype=out_dtype if direct else torch.float32, device=raw.device)
+    nws = lib.r2l_static_workspace_bytes_opts(frames, B, H, W, *codes, ov)     # (a 5x5 median runs as plane passes)
     ws = torch.empty(nws, dtype=torch.uint8, device=raw.device) if nws else None      # 0: single-launch chains
-    tail = (ptr(out), B, H, W, cam, *codes, float(gamma), ptr(ws), nws, stream)
-    if custom:
-        ms = (ctypes.c_float * 6)(*[float(v) for v in mean_std]) if mean_std is not None else None
-        lib.check(lib.r2l_static_fwd_opts(ptr(raw), frames, float(denom or 1.0), ptr(out), B, H, W, cam, *codes,
-                                          float(gamma), ov, ms, ptr(ws), nws, stream), 'r2l_static_fwd_opts')
-    elif mean_std is not None:
-        ms = (ctypes.c_float * 6)(*[float(v) for v in mean_std])
-        lib.check(lib.r2l_static_fwd_norm(ptr(raw), frames, float(denom or 1.0), ptr(out), B, H, W, cam, *codes,
-                                          float(gamma), ms, ptr(ws), nws, stream), 'r2l_static_fwd_norm')
-    elif f64:
-        lib.check(lib.r2l_static_fwd_f64(ptr(raw), *tail), 'r2l_static_fwd_f64')
-    elif denom is None:
-        lib.check(lib.r2l_static_fwd(ptr(raw), *tail), 'r2l_static_fwd')
-    else:
-        lib.check(lib.r2l_static_fwd_u16(ptr(raw), denom, *tail), 'r2l_static_fwd_u16')
-    return out if IO_CODES[out_dtype] == IO_F32 else out.to(out_dtype)
+    lib.check(lib.r2l_static_fwd_io(ptr(raw), frames, float(denom or 1.0), ptr(out), io if direct else IO_F32, B, H, W, cam,
+                                    *codes, float(gamma), ov, ms, ptr(ws), nws, stream), 'r2l_static_fwd_io')
+    return out if (direct or io == IO_F32) else out.to(out_dtype)
 
 
 def static_io_why(raw, debayer='bilinear', sharpening='sharpening_filter', denoising='gaussian_denoising', **options):

@@ -17,15 +17,16 @@
 #include "r2l_limits_lockstep.cpp"
 #include "r2l_static_half_lockstep.cpp"
 #include "r2l_static_routes_lockstep.cpp"
+#include "r2l_entries_lockstep.cpp"  // (behind fwd_routes: it uses that driver's parameter block)
 
 int main(int argc, char** argv) {
   static const struct {
     const char *name, *arguments;
     int (*run)(int, char**);
-  } DRIVERS[7] = {{"half_io", " <params.bin>", r2l_drv::half_io::run}, {"channels_last", " <params.bin>", r2l_drv::channels_last::run},
+  } DRIVERS[8] = {{"half_io", " <params.bin>", r2l_drv::half_io::run}, {"channels_last", " <params.bin>", r2l_drv::channels_last::run},
                   {"static_half", "", r2l_drv::static_half::run},      {"static_routes", "", r2l_drv::static_routes::run},
                   {"fwd_routes", "", r2l_drv::fwd_routes::run},        {"limits", "", r2l_drv::limits::run},
-                  {"bn_settings", "", r2l_drv::bn_settings::run}};
+                  {"bn_settings", "", r2l_drv::bn_settings::run},      {"entries", "", r2l_drv::entries::run}};
   for (const auto& d : DRIVERS)
     if (argc >= 2 && !strcmp(argv[1], d.name)) return d.run(argc - 1, argv + 1);
   fprintf(stderr, "usage: r2l_lockstep_drivers <subcommand> [arguments], the subcommands:\n");

@@ -1,4 +1,4 @@
-"""The stand-alone drivers of the lock-step emulation (tests/emul/r2l_lockstep_drivers.cpp: the emulation's sources + the seven
+"""The stand-alone drivers of the lock-step emulation (tests/emul/r2l_lockstep_drivers.cpp: the emulation's sources + the eight
 drivers + a main, -fsanitize=address,undefined, no Python in the process): ONE flag list, ONE dependency list, ONE build into
 tests/_build/r2l_lockstep_drivers, and run(<subcommand>, ...).  -O0 like the lock-step library: the optimiser needs many minutes
 for these sources under the sanitizers.  The library builds of conftest.build_lockstep() are not made here."""
@@ -12,7 +12,7 @@ BUILD = os.path.join(HERE, '_build')
 EXE = os.path.join(BUILD, 'r2l_lockstep_drivers')
 SANITIZE = ['-fsanitize=address,undefined', '-fno-sanitize-recover=undefined', '-fno-omit-frame-pointer', '-g']
 FLAGS = ['-std=c++17', '-O0', *SANITIZE]
-SUBCOMMANDS = ('half_io', 'channels_last', 'static_half', 'static_routes', 'fwd_routes', 'limits', 'bn_settings')
+SUBCOMMANDS = ('half_io', 'channels_last', 'static_half', 'static_routes', 'fwd_routes', 'limits', 'bn_settings', 'entries')
 DRIVER_SOURCES = ['r2l_lockstep_drivers.cpp', 'r2l_driver_util.h'] + [f'r2l_{name}_lockstep.cpp' for name in SUBCOMMANDS]
 
 
