@@ -416,6 +416,32 @@ int r2l_static_fwd_io(const void *raw, int frames, float denom, void *out, int o
                       const double *options_host, const float *mean_std_host, void *workspace, size_t workspace_bytes,
                       void *stream);
 
+/* ---- channel statistics: the mean / std of T.Normalize(mean, std) (get_statistics, pipeline_numpy.py:306-329) ------------------------
+ * r2l_static_stats runs a static chain WITHOUT storing its output and returns, in float64 on the device,
+ *   sums[0..2] = sum over all pixels of v, per channel;  sums[3..5] = sum of v * v;  sums[6] = the pixel count B * H * W
+ * -- the layout of r2l_isp_fwd's `stats`, unshifted -- where v is the float32 value r2l_static_fwd_opts(mean_std_host = NULL)
+ * writes for that pixel.  Both terms are exact in float64; the additions run in an order that the shape of the call fixes (no
+ * atomics): the same bits on every run of one build.  `sums` is overwritten.  The frames are read once (4 B/px, 2 for 16-bit
+ * containers), a few float64 per wavefront are written.
+ * It is served where r2l_static_fwd_io serves a 16-bit output -- one launch of a row-streaming kernel, see above -- and
+ * r2l_static_stats_supported returns NULL there, otherwise the reason (a static string).  An unserved call returns -3 with that
+ * reason in r2l_last_error() and writes nothing: the caller then runs r2l_static_fwd_opts and r2l_channel_sums on its output.
+ * Other codes as r2l_static_fwd_opts: -1 null pointers / bad arguments, -2 workspace smaller than
+ * r2l_static_stats_workspace_bytes (the partial sums: at most 768 KiB), -4 what that entry refuses.  A workspace must not be
+ * shared by two streams at once.
+ * r2l_channel_sums: the same sums of any contiguous (B,C,H,W) float32 tensor, 1 <= C <= 4, any H, W >= 1, x 4-byte aligned:
+ * sums[0..C-1], sums of squares [C..2C-1], B * H * W at [2C].  The result does not depend on the launch's grid.             */
+const char *r2l_static_stats_supported(int frames, int H, int W, int debayer, int sharpening, int denoising,
+                                       const double *options_host);
+size_t r2l_static_stats_workspace_bytes(int frames, int B, int H, int W, int debayer, int sharpening, int denoising,
+                                        const double *options_host);
+int r2l_static_stats(const void *raw, int frames, float denom, double *sums, int B, int H, int W,
+                     const double *camera_host, int debayer, int sharpening, int denoising, double gamma,
+                     const double *options_host, void *workspace, size_t workspace_bytes, void *stream);
+size_t r2l_channel_sums_workspace_bytes(int B, int C, int H, int W);
+int r2l_channel_sums(const float *x, double *sums, int B, int C, int H, int W, void *workspace, size_t workspace_bytes,
+                     void *stream);
+
 /* ---- staged execution (track_stages=True, pipeline_torch.py:197-221): one entry point per materialised
  * stage, each with its VJP, so that autograd can hold every stage tensor (retain_grad) and d/d raw exists.
  * Tensors are (B,3,H,W) float32.  Weight gradients are float32 arrays; workspace from

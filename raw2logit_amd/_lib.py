@@ -175,6 +175,15 @@ _SIGNATURES = {
                                          ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_double),
                                          ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_size_t,
                                          ctypes.c_void_p]),
+    'r2l_static_stats_supported': (ctypes.c_char_p, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_double)]),
+    'r2l_static_stats_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_double)]),
+    'r2l_static_stats': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_double, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_size_t,
+                                        ctypes.c_void_p]),
+    'r2l_channel_sums_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 4),
+    'r2l_channel_sums': (ctypes.c_int, [_c_float_p, ctypes.c_void_p] + [ctypes.c_int] * 4 +
+                         [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     'r2l_static_fwd': (ctypes.c_int, [_c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                       ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int,
                                       ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t,

@@ -25,6 +25,7 @@
 #include "r2l_aux_kernels.h"
 #include "r2l_augment_strong.h"
 #include "r2l_corruptions.h"
+#include "r2l_sums_kernels.h"
 
 static thread_local std::string r2l_err;
 static int r2l_fail(int code, const std::string& msg) {
@@ -421,6 +422,8 @@ R2L_STREAM_KERNEL(r2l_launch_static_luma_malvar_f64, 1, R2L_RAW_F64, true, 2)
   R2L_STREAM_KERNEL_IO(r2l_launch_static_stream_malvar_f64##sfx, 1, R2L_RAW_F64, IO, 2)
 R2L_STREAM_KERNELS_IO(_bf16, R2L_IO_BF16)
 R2L_STREAM_KERNELS_IO(_f16, R2L_IO_F16)
+// ... and storing nothing: the channel sums of what the float32 siblings store (r2l_static_stats)
+R2L_STREAM_KERNELS_IO(_stats, R2L_IO_STATS)
 #endif
 R2L_KERNEL(r2l_launch_plane_filter, R2LPlaneArgs, r2l_plane_filter_block, 4)
 R2L_KERNEL(r2l_launch_spec_mask, R2LSpecMaskArgs, r2l_spec_mask_block, 4)
@@ -491,6 +494,8 @@ R2L_CHAIN_KERNELS_IO(_bf16, R2L_RAW_F32, R2L_IO_BF16)
 R2L_CHAIN_KERNELS_IO(_u16_bf16, R2L_RAW_U16, R2L_IO_BF16)
 R2L_CHAIN_KERNELS_IO(_f16, R2L_RAW_F32, R2L_IO_F16)
 R2L_CHAIN_KERNELS_IO(_u16_f16, R2L_RAW_U16, R2L_IO_F16)
+R2L_CHAIN_KERNELS_IO(_stats, R2L_RAW_F32, R2L_IO_STATS)
+R2L_CHAIN_KERNELS_IO(_u16_stats, R2L_RAW_U16, R2L_IO_STATS)
 #endif
 R2L_KERNEL(r2l_launch_static_short, R2LStaticArgs, r2l_static_short_block<GStatic>,
            R2L_STATIC_SHORT_LDS_FLOATS)
@@ -525,6 +530,8 @@ R2L_KERNEL(r2l_launch_ssim, R2LSsimArgs, r2l_ssim_block, R2L_SSIM_LDS_FLOATS)
 R2L_KERNEL(r2l_launch_ssim_bwd, R2LSsimBwdArgs, r2l_ssim_bwd_block, R2L_SSIM_BWD_LDS_FLOATS)
 R2L_KERNEL(r2l_launch_l2, R2LL2Args, r2l_l2_block, R2L_RED_FLOATS_N(1))
 R2L_KERNEL(r2l_launch_pack_fold, R2LPackFoldArgs, r2l_pack_fold_block, R2L_P_COUNT + 2)
+R2L_KERNEL(r2l_launch_channel_sums, R2LChannelSumsArgs, r2l_channel_sums_block, R2L_SUMS_LDS_FLOATS)
+R2L_KERNEL(r2l_launch_sums_finish, R2LSumsFinishArgs, r2l_sums_finish_block, R2L_SUMS_LDS_FLOATS)
 
 // ---- grid sizing ------------------------------------------------------------------------------
 static_assert(R2L_MAX_BLOCKS == 2048 && 1 + R2L_MAX_GROUPS <= R2L_NT, "partials / arrival counters are laid out for at most 2048 workgroups");
@@ -1892,11 +1899,12 @@ typedef int (*R2LStreamLaunch)(const R2LStaticStreamArgs&, int, void*);
 #define R2L_STREAM_ROW(name, sfx)                                                                \
   {{name##_bilinear##sfx, name##_malvar##sfx}, {name##_bilinear_u16##sfx, name##_malvar_u16##sfx}, \
    {name##_bilinear_f64##sfx, name##_malvar_f64##sfx}}
-// [output: float32 | bfloat16 | float16][frames: float32 | 16-bit | float64][bilinear | Malvar2004]
+// [output: float32 | bfloat16 | float16 | none, statistics][frames: float32 | 16-bit | float64][bilinear | Malvar2004]
 static const R2LStreamLaunch r2l_static_stream_table[][3][2] = {R2L_STREAM_ROW(r2l_launch_static_stream, ),
 #ifndef R2L_SERIAL
                                                                 R2L_STREAM_ROW(r2l_launch_static_stream, _bf16),
-                                                                R2L_STREAM_ROW(r2l_launch_static_stream, _f16)
+                                                                R2L_STREAM_ROW(r2l_launch_static_stream, _f16),
+                                                                R2L_STREAM_ROW(r2l_launch_static_stream, _stats)
 #endif
 };
 static const R2LStreamLaunch r2l_static_luma_table[3][2] = R2L_STREAM_ROW(r2l_launch_static_luma, );
@@ -1908,10 +1916,11 @@ typedef int (*R2LChainLaunch)(const R2LStaticChainArgs&, int, void*);
     {r2l_launch_static_chain_unsharp##sfx, r2l_launch_static_chain_unsharp_median##sfx}},                           \
    {{r2l_launch_static_chain_malvar##sfx, r2l_launch_static_chain_malvar_median##sfx},                              \
     {r2l_launch_static_chain_malvar_unsharp##sfx, r2l_launch_static_chain_malvar_unsharp_median##sfx}}}
-// [output][frames][Malvar2004][unsharp_masking][median_denoising]; float64 frames with a 16-bit output: none
-static const R2LChainLaunch r2l_static_chain_table[3][3][2][2][2] = {{R2L_CHAIN_ROW(), R2L_CHAIN_ROW(_u16), R2L_CHAIN_ROW(_f64)},
+// [output][frames][Malvar2004][unsharp_masking][median_denoising]; float64 frames with a 16-bit output or none (statistics): none
+static const R2LChainLaunch r2l_static_chain_table[4][3][2][2][2] = {{R2L_CHAIN_ROW(), R2L_CHAIN_ROW(_u16), R2L_CHAIN_ROW(_f64)},
                                                                      {R2L_CHAIN_ROW(_bf16), R2L_CHAIN_ROW(_u16_bf16)},
-                                                                     {R2L_CHAIN_ROW(_f16), R2L_CHAIN_ROW(_u16_f16)}};
+                                                                     {R2L_CHAIN_ROW(_f16), R2L_CHAIN_ROW(_u16_f16)},
+                                                                     {R2L_CHAIN_ROW(_stats), R2L_CHAIN_ROW(_u16_stats)}};
 #undef R2L_CHAIN_ROW
 #endif
 
@@ -1924,6 +1933,8 @@ struct R2LStaticPlan {
   double fft_fraction;
   const char* refused;     // why the call cannot run at all (-4), or null
   const char* no_io;       // why a 16-bit output is not served (-3), or null
+  const char* no_stats;    // why r2l_static_stats is not served (-3), or null: the same kernels in their statistics form
+  int nparts;              // io = R2L_IO_STATS: the partials double[6] the launch leaves in the workspace, one per wavefront
   int err;                 // rocFFT could not plan the transforms (its text is in r2l_err)
   bool too_large;          // more workgroups than a launch takes
   // workspace of MENON: the (B,3,H,W) float64 image + five (B,H,W) planes; of PLANES: two planes, for fft_denoising the image
@@ -1937,7 +1948,7 @@ struct R2LStaticPlan {
   R2LChainLaunch chain;
 #endif
 };
-// frames: R2L_FRAMES_*; io: R2L_IO_* of the output.  The only reader of the static chains' overrides of diagnostic builds
+// frames: R2L_FRAMES_*; io: R2L_IO_* of the output, or R2L_IO_STATS: none, the channel sums (r2l_static_stats).  The only reader of the static chains' overrides of diagnostic builds
 // (R2L_STATIC_TILED, R2L_CHAIN_BAND, R2L_STREAM_BANDS, R2L_GRID_STATIC*).  sized = false: without rocFFT's work buffer in
 // `workspace_bytes` -- for callers that ask for `no_io` alone and must not open the library
 static R2LStaticPlan r2l_static_plan(int frames, int B, int H, int W, int debayer, int sharpening, int denoising,
@@ -1973,28 +1984,32 @@ static R2LStaticPlan r2l_static_plan(int frames, int B, int H, int W, int debaye
     p.refused = "r2l_static_fwd: menon2007 runs as plane passes, which need W % 4 == 0 (and frames of at least 4 x 4)";
   if (p.route == R2L_ROUTE_PLANES && !quads) p.refused = "r2l_static_fwd: this chain runs as plane passes, which need W % 4 == 0";
 
-  // a 16-bit output: what runs as one launch of a row-streaming kernel on frames up to 2048 columns
-  p.no_io = [&]() -> const char* {
+  // a 16-bit output, or none (the statistics form): what runs as one launch of a row-streaming kernel on frames up to 2048 columns
+  const auto one_launch = [&](bool stats) -> const char* {
     if (frames != R2L_FRAMES_F32 && frames != R2L_FRAMES_U16 && frames != R2L_FRAMES_F64) return "frames must be one of R2L_FRAMES_*";
     if (H < 4 || W < 4 || (H & 1) || (W & 1)) return "H and W must be even and >= 4";
 #ifdef R2L_SERIAL
-    return "the serial emulation has no 16-bit form of the static kernels";
+    return stats ? "the serial emulation has no statistics form of the static kernels (not expressible one lane at a time)"
+                 : "the serial emulation has no 16-bit form of the static kernels";
 #else
-    if (menon) return "menon2007 runs as plane passes, which store float32";
+    if (menon) return stats ? "menon2007 runs as plane passes, which have no statistics form" : "menon2007 runs as plane passes, which store float32";
     if (debayer != R2L_DEBAYER_BILINEAR && !malvar) return "unknown debayer";
     if (sharpening != R2L_SHARPEN_NONE && sharpening != R2L_SHARPEN_FILTER && !unsharp) return "unknown sharpening";
     if (denoising != R2L_DENOISE_NONE && denoising != R2L_DENOISE_GAUSSIAN && !median && !p.fft) return "unknown denoising";
-    if (p.fft) return "fft_denoising runs as plane passes, which store float32";
-    if (med5) return "the 5x5 median runs as a plane pass, which stores float32";
+    if (p.fft) return stats ? "fft_denoising runs as plane passes, which have no statistics form" : "fft_denoising runs as plane passes, which store float32";
+    if (med5) return stats ? "the 5x5 median runs as a plane pass, which has no statistics form" : "the 5x5 median runs as a plane pass, which stores float32";
     if (!quads) return "needs W % 4 == 0 (the row-streaming kernels)";
     if (W > 2048) return "needs W <= 2048";
     if (p.route == R2L_ROUTE_STREAM) return nullptr;
     if (p.route != R2L_ROUTE_CHAIN)
       return unsharp && W > 1024 ? "behind unsharp_masking the luma-chain kernel needs W <= 1024"
                                  : "needs the row-streaming kernels (R2L_STATIC_TILED is set)";
-    return f64 ? "float64 frames on a luma chain store float32" : nullptr;
+    if (f64) return stats ? "float64 frames on a luma chain have no statistics form" : "float64 frames on a luma chain store float32";
+    return nullptr;
 #endif
-  }();
+  };
+  p.no_io = one_launch(false);
+  p.no_stats = one_launch(true);
   if (B < 1 || H < 1 || W < 1) return p;
 
   const size_t px = (size_t)B * H * W;
@@ -2016,7 +2031,11 @@ static R2LStaticPlan r2l_static_plan(int frames, int B, int H, int W, int debaye
   // (the launch shape: of frames r2l_check_dims lets through, whose counts fit the arithmetic below)
   if ((size_t)H * W > ((size_t)1 << 29) || px > ((size_t)1 << 40)) return p;
 
-  const int kind = frames == R2L_FRAMES_U16 ? 1 : (f64 ? 2 : 0), out = p.no_io ? R2L_IO_F32 : io;
+  const bool stats = io == R2L_IO_STATS && !p.no_stats;
+  const int kind = frames == R2L_FRAMES_U16 ? 1 : (f64 ? 2 : 0), out = stats ? R2L_IO_STATS : ((p.no_io || io == R2L_IO_STATS) ? R2L_IO_F32 : io);
+  // the statistics forms: a workgroup walks the work items bid, bid + grid, ...; as many workgroups as the reduction trees take
+  long stats_cap = r2l_env_int("R2L_GRID_STATIC", R2L_MAX_BLOCKS);
+  if (stats_cap > R2L_MAX_BLOCKS) stats_cap = R2L_MAX_BLOCKS;
   long grid = 0;
   switch (p.route) {
     case R2L_ROUTE_MENON: {
@@ -2038,6 +2057,12 @@ static R2LStaticPlan r2l_static_plan(int frames, int B, int H, int W, int debaye
       p.nband = (H + p.band_h - 1) / p.band_h;
       p.nseg = W <= 256 ? 1 : (W <= 512 ? 2 : (W <= 1024 ? 4 : 8));
       grid = (long)B * p.nband;
+      if (stats) {
+        p.too_large = grid > (1L << 30);
+        grid = grid < stats_cap ? grid : stats_cap;
+        p.nparts = (int)grid * p.nseg;
+        p.workspace_bytes = sizeof(double) * 6 * (size_t)p.nparts;
+      }
       p.chain = r2l_static_chain_table[out][kind][malvar][unsharp][median];
 #endif
       break;
@@ -2067,6 +2092,11 @@ static R2LStaticPlan r2l_static_plan(int frames, int B, int H, int W, int debaye
       p.nitems = (int)nitems;
       grid = (nitems + wpb - 1) / wpb;
       p.too_large = nitems > (1L << 30);
+      if (stats) {
+        grid = grid < stats_cap ? grid : stats_cap;
+        p.nparts = (int)grid * wpb;
+        p.workspace_bytes = sizeof(double) * 6 * (size_t)p.nparts;
+      }
       p.stream = p.route == R2L_ROUTE_PLANES ? r2l_static_luma_table[kind][malvar] : r2l_static_stream_table[out][kind][malvar];
       break;
     }
@@ -2212,7 +2242,13 @@ struct R2LStaticCall {
   void* workspace;
   size_t workspace_bytes;
   void* stream;
+  double* sums = nullptr;  // r2l_static_stats (io = R2L_IO_STATS, out = null): double[7], instead of an output
 };
+// the partials a statistics launch left in the workspace -> sums[0..5], the pixel count -> sums[6]
+static int r2l_static_sums_finish(const R2LStaticPlan& p, const R2LStaticCall& c) {
+  R2LSumsFinishArgs f{(const double*)c.workspace, p.nparts, 6, (double)c.B * (double)c.H * (double)c.W, c.sums};
+  return r2l_launch_sums_finish(f, 1, c.stream);
+}
 static int r2l_static_fwd_impl(const R2LStaticCall& c) {
   if (c.frames != R2L_FRAMES_F32 && c.frames != R2L_FRAMES_U16 && c.frames != R2L_FRAMES_F64)
     return r2l_fail(-1, "r2l_static_fwd_norm: frames must be R2L_FRAMES_F32, _U16 or _F64");
@@ -2223,7 +2259,7 @@ static int r2l_static_fwd_impl(const R2LStaticCall& c) {
   if (c.mean_std_host)
     for (int k = 0; k < 3; ++k)
       if (!(c.mean_std_host[3 + k] != 0.f)) return r2l_fail(-1, "r2l_static_fwd_norm: std must be non-zero");
-  if (!c.out || !c.camera_host) return r2l_fail(-1, "r2l_static_fwd: null pointer");
+  if (!(c.io == R2L_IO_STATS ? (void*)c.sums : (void*)c.out) || !c.camera_host) return r2l_fail(-1, "r2l_static_fwd: null pointer");
   if (c.debayer != R2L_DEBAYER_BILINEAR && c.debayer != R2L_DEBAYER_MALVAR2004 && c.debayer != R2L_DEBAYER_MENON2007)
     return r2l_fail(-1, "r2l_static_fwd: unknown debayer");
   if (c.sharpening != R2L_SHARPEN_NONE && c.sharpening != R2L_SHARPEN_FILTER && c.sharpening != R2L_SHARPEN_UNSHARP)
@@ -2235,17 +2271,21 @@ static int r2l_static_fwd_impl(const R2LStaticCall& c) {
   if (const char* why = r2l_static_opts_problem(c.opt, c.sharpening, c.denoising))
     return r2l_fail(-4, std::string("r2l_static_fwd: ") + why);
   R2LStaticArgs a;
-  r2l_static_setup(a, raw, c.out, c.B, c.H, c.W, c.camera_host, c.debayer, c.sharpening, c.denoising, c.gamma, c.mean_std_host,
-                   c.opt);
+  // (the statistics forms store nothing: their `out` is where each wavefront leaves its partial, the workspace)
+  r2l_static_setup(a, raw, c.io == R2L_IO_STATS ? (float*)c.workspace : c.out, c.B, c.H, c.W, c.camera_host, c.debayer, c.sharpening,
+                   c.denoising, c.gamma, c.mean_std_host, c.opt);
   const R2LStaticPlan p = r2l_static_plan(c.frames, c.B, c.H, c.W, c.debayer, c.sharpening, c.denoising, c.opt, c.io);
-  if (c.io != R2L_IO_F32 && p.no_io)
+  if (c.io == R2L_IO_STATS && p.no_stats)
+    return r2l_fail(-3, std::string("r2l_static_stats: not served here: ") + p.no_stats);
+  if (c.io != R2L_IO_F32 && c.io != R2L_IO_STATS && p.no_io)
     return r2l_fail(-3, "r2l_static_fwd_io: no 16-bit form of the kernels this call takes (r2l_static_io_supported)");
   if (p.refused) return r2l_fail(-4, p.refused);
   if (p.err) return p.err;
   if (p.workspace_bytes && (!c.workspace || c.workspace_bytes < p.workspace_bytes))
     return r2l_fail(-2, "r2l_static_fwd: workspace too small (r2l_static_workspace_bytes)");
   if (p.too_large) return r2l_fail(-1, "r2l_static_fwd: batch too large");
-  return r2l_static_launch(p, a, c.workspace, c.stream);
+  if (int e = r2l_static_launch(p, a, c.workspace, c.stream)) return e;
+  return c.io == R2L_IO_STATS ? r2l_static_sums_finish(p, c) : 0;
 }
 
 int r2l_isp_fwd(const float* raw, const float* params, const float* additive,
@@ -2381,6 +2421,56 @@ int r2l_static_fwd_io(const void* raw, int frames, float denom, void* out, int o
     if ((uintptr_t)out % 8) return r2l_fail(-1, "r2l_static_fwd_io: the 16-bit output must be 8-byte aligned");
   }
   return r2l_static_fwd_impl(c);
+}
+
+// ---- channel statistics (include/r2l_isp.h: r2l_static_stats, r2l_channel_sums) ---------------------------------------------------
+const char* r2l_static_stats_supported(int frames, int H, int W, int debayer, int sharpening, int denoising, const double* options_host) {
+  return r2l_static_plan(frames, 1, H, W, debayer, sharpening, denoising, r2l_static_opts(options_host), R2L_IO_STATS, false).no_stats;
+}
+size_t r2l_static_stats_workspace_bytes(int frames, int B, int H, int W, int debayer, int sharpening, int denoising,
+                                        const double* options_host) {
+  const R2LStaticPlan p = r2l_static_plan(frames, B, H, W, debayer, sharpening, denoising, r2l_static_opts(options_host, 3), R2L_IO_STATS, false);
+  return p.no_stats ? 0 : p.workspace_bytes;
+}
+int r2l_static_stats(const void* raw, int frames, float denom, double* sums, int B, int H, int W, const double* camera_host, int debayer,
+                     int sharpening, int denoising, double gamma, const double* options_host, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+  R2LStaticCall c{raw, frames, denom, nullptr, R2L_IO_STATS, B, H, W, camera_host, debayer, sharpening, denoising, gamma, nullptr,
+                  r2l_static_opts(options_host), workspace, workspace_bytes, stream};
+  c.sums = sums;
+  return r2l_static_fwd_impl(c);
+}
+// the shares of r2l_channel_sums and where its 16-byte vectors start, from the shape and the pointer's alignment alone
+static R2LChannelSumsArgs r2l_channel_sums_args(const float* x, int B, int C, int H, int W) {
+  R2LChannelSumsArgs a = {};
+  a.x = x;
+  a.hw = (size_t)H * W;
+  a.n = (size_t)B * C * a.hw;
+  a.C = C;
+  a.head = (size_t)((16 - (uintptr_t)x % 16) % 16) / 4;
+  if (a.head > a.n) a.head = a.n;
+  a.nvec = (a.n - a.head) / 4;
+  const size_t nv = (a.nvec + R2L_NT - 1) / R2L_NT;
+  a.nv = nv > R2L_SUMS_MAX_SHARES ? R2L_SUMS_MAX_SHARES : (nv < 1 ? 1 : (int)nv);
+  return a;
+}
+size_t r2l_channel_sums_workspace_bytes(int B, int C, int H, int W) {
+  if (B < 1 || C < 1 || C > 4 || H < 1 || W < 1) return 0;
+  // (an unaligned tensor has at most one vector less than an aligned one: the aligned count bounds the shares)
+  return sizeof(double) * 2 * C * (size_t)r2l_channel_sums_args(nullptr, B, C, H, W).nv;
+}
+int r2l_channel_sums(const float* x, double* sums, int B, int C, int H, int W, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!x || !sums) return r2l_fail(-1, "r2l_channel_sums: null pointer");
+  if (B < 1 || C < 1 || C > 4 || H < 1 || W < 1) return r2l_fail(-1, "r2l_channel_sums: needs B, H, W >= 1 and 1 <= C <= 4");
+  if ((uintptr_t)x % 4) return r2l_fail(-1, "r2l_channel_sums: x must be 4-byte aligned");
+  if ((double)B * C * H * W > 1099511627776.0) return r2l_fail(-1, "r2l_channel_sums: tensor too large");
+  R2LChannelSumsArgs a = r2l_channel_sums_args(x, B, C, H, W);
+  if (!workspace || workspace_bytes < r2l_channel_sums_workspace_bytes(B, C, H, W))
+    return r2l_fail(-2, "r2l_channel_sums: workspace too small (r2l_channel_sums_workspace_bytes)");
+  a.partial = (double*)workspace;
+  if (int e = r2l_launch_channel_sums(a, r2l_flat_grid((size_t)a.nv), stream)) return e;
+  R2LSumsFinishArgs f{a.partial, a.nv, 2 * C, (double)B * (double)H * (double)W, sums};
+  return r2l_launch_sums_finish(f, 1, stream);
 }
 
 // ---- staged (track_stages=True) entry points -------------------------------------------------------

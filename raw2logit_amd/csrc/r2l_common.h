@@ -518,6 +518,9 @@ R2L_HD r2l_h4 r2l_load_h4_nt(const unsigned short* p) {
 // 0, 1, 2 mean what they meant; only r2l_fs_colour (the store) and r2l_bp_fetch_g (the load) look at the bit.
 #define R2L_IO_NHWC 4
 #define R2L_IO_ELEM(IO) ((IO) & 3)
+// Not a boundary tensor at all (the static chains' r2l_static_stats): the instantiation stores nothing and adds every float32 value
+// it would have stored, and its square, to six float64 sums per lane (r2l_stats_add_row, r2l_static_stream.h)
+#define R2L_IO_STATS 3
 // element i of a boundary tensor of type IO behind a float pointer (the argument blocks keep their float32 types)
 template <int IO>
 R2L_HD float* r2l_io_at(float* p, size_t i) {

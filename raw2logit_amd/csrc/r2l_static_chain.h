@@ -65,9 +65,9 @@ R2L_HD double r2l_wave_shl1_d(double x, double edge) {
 // (a float32 raw window, widened on the fly as in the short chain's Malvar2004 kernel, does not pay here: the chroma ring
 // in LDS, not the registers, keeps these kernels at two wavefronts per SIMD, and the extra conversions cost 2 %:
 // profiles/r03_static_windows.txt)
-template <int DEB, int SH, int DN>
+template <int DEB, int SH, int DN, class RWT = double>
 struct R2LChainState {
-  double rw[DEB ? 6 : 3][8];  // raw rows (slot = row mod 3 / mod 6): columns x0-2 .. x0+5, black level removed
+  RWT rw[DEB ? 6 : 3][8];  // raw rows (slot = row mod 3 / mod 6): columns x0-2 .. x0+5, black level removed
   // SH 0: luma rows q-2 .. q (slot = row mod 3).  SH 1 (unsharp_masking: 9 rows, which no ring that divides the
   // 6-fold unroll holds): rows q-8 .. q as a shift register, [8] = row q
   double yr[SH ? 9 : 3][4];
@@ -102,10 +102,10 @@ R2L_HD R2LStaticArgsK r2l_chain_consts() {
 #endif
 }
 
-template <int DEB, int SH, int DN, int K0, int IO = R2L_IO_F32>
-R2L_HD void r2l_chain_step(const R2LStaticArgs& a_, R2LChainState<DEB, SH, DN>& st, int q_, int y0, int y1, bool le,
+template <int DEB, int SH, int DN, int K0, int IO = R2L_IO_F32, class RWT = double>
+R2L_HD void r2l_chain_step(const R2LStaticArgs& a_, R2LChainState<DEB, SH, DN, RWT>& st, int q_, int y0, int y1, bool le,
                            bool re, int NW, int wave, int lane, double* ex, r2l_d2* fifo, float* outb, size_t plane,
-                           int x0, bool store_ok) {
+                           int x0, bool store_ok, double* acc = nullptr) {
   constexpr int PY = K0 & 1;
   constexpr int FR = R2L_CHAIN_FIFO_ROWS(SH);
   const int H = a_.H;
@@ -293,6 +293,10 @@ R2L_HD void r2l_chain_step(const R2LStaticArgs& a_, R2LChainState<DEB, SH, DN>& 
           x[k][c] = r2l_clip_gamma(rgb, a.inv_gamma);
         }
       }
+      if constexpr (IO == R2L_IO_STATS) {  // no output (r2l_static_stats): the row's values and squares to the lane's sums
+        r2l_stats_add_row(acc, x, store_ok);
+        return;
+      }
       r2l_static_normalize<4>(a, x);
       if constexpr (IO != R2L_IO_F32) {  // 16-bit output (r2l_static_fwd_io): one 8-byte store per channel
         r2l_stream_store_row<IO>(outb, plane, (size_t)y * a_.W + x0, x, store_ok);
@@ -368,6 +372,10 @@ R2L_HD void r2l_chain_step(const R2LStaticArgs& a_, R2LChainState<DEB, SH, DN>& 
         x[k][c] = r2l_clip_gamma(rgb, a.inv_gamma);
       }
     }
+    if constexpr (IO == R2L_IO_STATS) {
+      r2l_stats_add_row(acc, x, store_ok);
+      return;
+    }
     r2l_static_normalize<4>(a, x);
     if constexpr (IO != R2L_IO_F32) {
       r2l_stream_store_row<IO>(outb, plane, (size_t)y * a_.W + x0, x, store_ok);
@@ -387,9 +395,9 @@ R2L_HD void r2l_chain_step(const R2LStaticArgs& a_, R2LChainState<DEB, SH, DN>& 
   }
 }
 
-template <int RAWK, int DEB, int SH, int DN, int IO = R2L_IO_F32>
-R2L_BLOCKFN void r2l_static_chain_block(const R2LStaticChainArgs& ca, int bid, int nblk, float* lds_f) {
-  (void)nblk;
+// one band of one image: work item `bid` of B * nband
+template <int RAWK, int DEB, int SH, int DN, int IO>
+R2L_BLOCKFN void r2l_static_chain_band(const R2LStaticChainArgs& ca, int bid, float* lds_f, double* acc) {
   const R2LStaticArgs& a = ca.s;
   const int NW = ca.nw;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -404,8 +412,13 @@ R2L_BLOCKFN void r2l_static_chain_block(const R2LStaticChainArgs& ca, int bid, i
   const bool le = x0 == 0, re = x0 + 4 >= a.W;
   const size_t plane = (size_t)a.H * a.W;
   const size_t img = (size_t)b * plane;
-  float* outb = r2l_io_at<IO>(a.out, (size_t)b * 3 * plane);
-  R2LChainState<DEB, SH, DN> st;
+  float* outb = IO == R2L_IO_STATS ? nullptr : r2l_io_at<IO>(a.out, (size_t)b * 3 * plane);
+  // (the statistics form of bilinear + unsharp_masking: a float32 raw window, widened exactly where used as in the short chain's
+  // Malvar2004 kernel -- the same numbers; 201 .. 220 registers where the float64 window took 267 .. 288, over the 256 of two
+  // wavefronts per SIMD.  The forms that store keep their float64 window: see R2LChainState)
+  constexpr bool SLIM = IO == R2L_IO_STATS && SH == 1 && DEB == 0;
+  typedef typename R2LWinType<SLIM>::type RWT;
+  R2LChainState<DEB, SH, DN, RWT> st;
   R2L_PRAGMA_UNROLL
   for (int i = 0; i < (DN == 0 ? 6 : 3); ++i)
     R2L_PRAGMA_UNROLL
@@ -449,7 +462,7 @@ R2L_BLOCKFN void r2l_static_chain_block(const R2LStaticChainArgs& ca, int bid, i
   R2L_PRAGMA_UNROLL
   for (int i = -LA; i < LA; ++i) {
     R2L_CHAIN_FETCH(q0 + i, stage)
-    r2l_stream_convert_row<RAWK, LANES>(a, stage, le, re, st.rw[(i + NR) % NR]);
+    r2l_stream_convert_row<RAWK, LANES, RWT>(a, stage, le, re, st.rw[(i + NR) % NR]);
   }
   static_assert(6 % PF == 0, "the prefetch ring is indexed by the unroll position");
   R2LRowStageT<RAWK> pf[PF];  // ring: step K consumes pf[K % PF] (raw row q + LA) and refills it with row q + LA + PF
@@ -460,9 +473,9 @@ R2L_BLOCKFN void r2l_static_chain_block(const R2LStaticChainArgs& ca, int bid, i
 #define R2L_CHAIN_STEP(K)                                                                                         \
   if (BF || qb + K < q1) {                                                                                        \
     const int q = qb + K;                                                                                         \
-    r2l_stream_convert_row<RAWK, LANES>(a, pf[K % PF], le, re, st.rw[(K + LA) % NR]);                             \
+    r2l_stream_convert_row<RAWK, LANES, RWT>(a, pf[K % PF], le, re, st.rw[(K + LA) % NR]);                           \
     if (BF || q + PF < q1) R2L_CHAIN_FETCH(q + LA + PF, pf[K % PF])                                               \
-    r2l_chain_step<DEB, SH, DN, K, IO>(a, st, q, y0, y1, le, re, NW, wave, lane, ex, fifo, outb, plane, x0, store_ok); \
+    r2l_chain_step<DEB, SH, DN, K, IO>(a, st, q, y0, y1, le, re, NW, wave, lane, ex, fifo, outb, plane, x0, store_ok, acc); \
   }
     R2L_CHAIN_STEP(0)
     R2L_CHAIN_STEP(1)
@@ -473,6 +486,27 @@ R2L_BLOCKFN void r2l_static_chain_block(const R2LStaticChainArgs& ca, int bid, i
 #undef R2L_CHAIN_STEP
   }
 #undef R2L_CHAIN_FETCH
+}
+
+// A workgroup takes band `bid`.  The statistics form (IO = R2L_IO_STATS: at most R2L_MAX_BLOCKS workgroups) walks the bands bid,
+// bid + nblk, ... with its lanes' six sums running through all of them, and every wavefront stores ONE partial, double[6], at index
+// bid * nw + wave of the partials ca.s.out points to (r2l_static_stats: the workspace; r2l_sums_finish adds them up).  Between two
+// bands a barrier: the exchange area of the first steps of a band is the one the slower wavefronts may still be reading.
+template <int RAWK, int DEB, int SH, int DN, int IO = R2L_IO_F32>
+R2L_BLOCKFN void r2l_static_chain_block(const R2LStaticChainArgs& ca, int bid, int nblk, float* lds_f) {
+  if constexpr (IO == R2L_IO_STATS) {
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int nbands = ca.s.B * ca.nband;
+    for (int item = bid; item < nbands; item += nblk) {
+      r2l_static_chain_band<RAWK, DEB, SH, DN, IO>(ca, item, lds_f, acc);
+      R2L_LDS_BARRIER();
+    }
+    const int tid = threadIdx.x;
+    r2l_stats_wave_partial(acc, tid & 63, (double*)ca.s.out + ((size_t)bid * ca.nw + (tid >> 6)) * 6);
+  } else {
+    (void)nblk;
+    r2l_static_chain_band<RAWK, DEB, SH, DN, IO>(ca, bid, lds_f, nullptr);
+  }
 }
 
 #endif  // !R2L_SERIAL

@@ -272,9 +272,47 @@ R2L_HD void r2l_stream_store_row(float* outb, size_t plane, size_t off, const fl
     if (ok) r2l_store_h4_nt((unsigned short*)outb + (size_t)k * plane + off, r2l_io_narrow4<IO>(st));
   }
 }
+// IO = R2L_IO_STATS (r2l_static_stats): nothing is stored.  Where the other forms store the float32 values x[k][c] of a lane's 4
+// pixels -- under the same `ok` -- this one adds them and their squares to the lane's six float64 sums acc[k], acc[3 + k]; both
+// terms are exact in float64 (24-bit operands), so only the additions round: the row's 4 pixels pairwise, then one addition to the
+// running sum.  The values are the un-normalised ones.
+R2L_HD void r2l_stats_add_row(double* acc, const float x[3][4], bool ok) {
+  R2L_PRAGMA_UNROLL
+  for (int k = 0; k < 3; ++k) {
+    double v[4];
+    R2L_PRAGMA_UNROLL
+    for (int c = 0; c < 4; ++c) v[c] = ok ? (double)x[k][c] : 0.0;
+    // the row's 4 pixels pairwise, then ONE addition to each running sum: a dependent chain of one add per row and sum
+    acc[k] += (v[0] + v[1]) + (v[2] + v[3]);
+    acc[3 + k] += fma(v[1], v[1], v[0] * v[0]) + fma(v[3], v[3], v[2] * v[2]);
+#ifndef R2L_EMUL
+    // (the sums are pinned row by row: left alone hipcc defers the additions of the unrolled rows and keeps their terms alive --
+    // the short Malvar2004 kernel then needed 242 registers instead of 148 and spilled at three wavefronts per SIMD)
+    asm volatile("" : "+v"(acc[k]), "+v"(acc[3 + k]));
+#endif
+  }
+}
+#ifndef R2L_SERIAL
+// the six sums of a wavefront: the cross-lane tree of the BatchNorm sums (r2l_bnr_lane_sums), a fixed order; lane 0 stores them
+// with ordinary vector stores.  Reached by every lane of the wavefront.
+R2L_HD void r2l_stats_wave_partial(const double* acc, int lane, double* part) {
+  double t[6];
+  R2L_PRAGMA_UNROLL
+  for (int k = 0; k < 6; ++k) {
+    double v = acc[k];
+    R2L_PRAGMA_UNROLL
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    t[k] = v;
+  }
+  if (lane == 0) {
+    R2L_PRAGMA_UNROLL
+    for (int k = 0; k < 6; ++k) part[k] = t[k];
+  }
+}
+#endif
 template <int IO = R2L_IO_F32>
 R2L_HD void r2l_stream_finish_row(const R2LStaticArgs& a, const double d[4][3], float* outb, size_t plane,
-                                  size_t off, bool ok = true) {
+                                  size_t off, bool ok = true, double* acc = nullptr) {
   float x[3][4];
   R2L_PRAGMA_UNROLL
   for (int c = 0; c < 4; ++c)
@@ -282,6 +320,10 @@ R2L_HD void r2l_stream_finish_row(const R2LStaticArgs& a, const double d[4][3], 
   for (int k = 0; k < 3; ++k) {
     const double rgb = fma(a.wbccm[k * 3], d[c][0], fma(a.wbccm[k * 3 + 1], d[c][1], a.wbccm[k * 3 + 2] * d[c][2]));
     x[k][c] = r2l_clip_gamma(rgb, a.inv_gamma);
+  }
+  if constexpr (IO == R2L_IO_STATS) {
+    r2l_stats_add_row(acc, x, ok);
+    return;
   }
   r2l_static_normalize<4>(a, x);
   if constexpr (IO != R2L_IO_F32) {
@@ -523,24 +565,28 @@ R2L_HD void r2l_stream_malvar_rowT(const double* w0, const double* w1, const dou
 #endif
 // one lane's work item: image b, column strip seg (256 columns), row band
 template <int DEB, int RAWK, bool LUMA, int IO = R2L_IO_F32>
-R2L_HD void r2l_static_stream_item(const R2LStaticStreamArgs& sa, int item, int lane) {
+R2L_HD void r2l_static_stream_item(const R2LStaticStreamArgs& sa, int item, int lane, double* acc = nullptr) {
   static_assert(IO == R2L_IO_F32 || !LUMA, "the luma-plane passes store float32");
+  constexpr bool STATS = IO == R2L_IO_STATS;
   const R2LStaticArgs& a = sa.s;
   constexpr int HALO = DEB ? 2 : 1, NR = 2 * HALO + 1;
   constexpr bool LANES = (DEB == 0) && R2L_HAVE_LANE_SHIFTS && RAWK != R2L_RAW_F64;
   const int seg = item % sa.nseg, r = item / sa.nseg;
   const int band = r % sa.nband, b = r / sa.nband;
-  const int x0 = seg * 256 + 4 * lane;
-  if (x0 >= a.W) {
+  const int xs = seg * 256 + 4 * lane;
+  if (!STATS && xs >= a.W) {
     R2L_LANE_RETIRES();
     return;
   }
+  // (the statistics form: every lane stays for the wavefront's sums; one past the last column walks the last 4 columns, uncounted)
+  const bool in_w = !STATS || xs < a.W;
+  const int x0 = in_w ? xs : a.W - 4;
   const int y0 = band * sa.band_h;
   const int y1 = (y0 + sa.band_h < a.H) ? y0 + sa.band_h : a.H;
   const bool le = x0 == 0, re = x0 + 4 >= a.W;
   const size_t plane = (size_t)a.H * a.W;
   const size_t img = (size_t)b * plane;  // element offset of image b
-  float* outb = r2l_io_at<IO>(a.out, (size_t)b * 3 * plane);
+  float* outb = STATS ? nullptr : r2l_io_at<IO>(a.out, (size_t)b * 3 * plane);
   // Malvar2004 on float32 / 16-bit frames: a float32 window (r2l_stream_malvar_row_shared widens it)
   constexpr bool WF32 = (DEB == 1) && RAWK != R2L_RAW_F64;
   typename R2LWinType<WF32>::type win[NR][8];
@@ -600,7 +646,7 @@ R2L_HD void r2l_static_stream_item(const R2LStaticStreamArgs& sa, int item, int 
         else if (LUMA)
           r2l_stream_luma_in_row(a, d, sa.luma_in + img, outb, plane, (size_t)y * a.W + x0);
         else
-          r2l_stream_finish_row<IO>(a, d, outb, plane, (size_t)y * a.W + x0);
+          r2l_stream_finish_row<IO>(a, d, outb, plane, (size_t)y * a.W + x0, in_w, acc);
       }
     }
   }
@@ -620,7 +666,7 @@ R2L_HD void r2l_static_stream_item(const R2LStaticStreamArgs& sa, int item, int 
 #endif
 // (strip edges through scalar loads + lane shifts: measured slower, profiles/r04_ab_static_se.txt)
 template <int DEB, int RAWK, int IO = R2L_IO_F32>
-R2L_HD void r2l_static_stream_item_bf(const R2LStaticStreamArgs& sa, int item, int lane) {
+R2L_HD void r2l_static_stream_item_bf(const R2LStaticStreamArgs& sa, int item, int lane, double* acc = nullptr) {
   const R2LStaticArgs& a = sa.s;
   constexpr int HALO = DEB ? 2 : 1, NR = 2 * HALO + 1;
   constexpr bool LANES = DEB == 0 && R2L_HAVE_LANE_SHIFTS;
@@ -637,7 +683,7 @@ R2L_HD void r2l_static_stream_item_bf(const R2LStaticStreamArgs& sa, int item, i
   const bool le = x0 == 0, re = x0 + 4 >= a.W;
   const size_t plane = (size_t)a.H * a.W;
   const size_t img = (size_t)b * plane;
-  float* outb = r2l_io_at<IO>(a.out, (size_t)b * 3 * plane);
+  float* outb = IO == R2L_IO_STATS ? nullptr : r2l_io_at<IO>(a.out, (size_t)b * 3 * plane);
   // (float32 window for bilinear too: 24 registers instead of 48, widened exactly where used -- what makes room for the
   // deeper prefetch ring at three wavefronts per SIMD)
   typedef float WT;
@@ -698,7 +744,7 @@ R2L_HD void r2l_static_stream_item_bf(const R2LStaticStreamArgs& sa, int item, i
                                           win[(k + 4) % NR], d);
       }
       const int yc = y < y1 ? y : y1 - 1;  // (rows past the band's end: computed, not stored)
-      r2l_stream_finish_row<IO>(a, d, outb, plane, (size_t)yc * a.W + x0, in_w && y < y1);
+      r2l_stream_finish_row<IO>(a, d, outb, plane, (size_t)yc * a.W + x0, in_w && y < y1, acc);
     }
   }
 }
@@ -707,10 +753,35 @@ R2L_HD void r2l_static_stream_item_bf(const R2LStaticStreamArgs& sa, int item, i
 #undef R2L_BF_CONVERT
 
 #define R2L_STREAM_NT 256  // 4 independent wavefronts per workgroup
+#ifndef R2L_SERIAL
+// The statistics form (IO = R2L_IO_STATS): at most R2L_MAX_BLOCKS workgroups; a wavefront walks the work items bid * 4 + wave,
+// + nblk * 4, ... with its lanes' six sums running through all of them, and stores ONE partial, double[6], at index bid * 4 + wave
+// of the partials sa.s.out points to (r2l_static_stats: the workspace; r2l_sums_finish adds them up).  No LDS, like its siblings.
+template <int DEB, int RAWK>
+R2L_BLOCKFN void r2l_static_stream_stats_block(const R2LStaticStreamArgs& sa, int bid, int nblk) {
+  constexpr int WPB = R2L_STREAM_NT / 64;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (a SCALAR: the work item must not look lane-dependent)
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int item = bid * WPB + wave; item < sa.nitems; item += nblk * WPB) {
+    if constexpr (RAWK != R2L_RAW_F64 && DEB == 1)
+      r2l_static_stream_item_bf<DEB, RAWK, R2L_IO_STATS>(sa, item, lane, acc);
+    else
+      r2l_static_stream_item<DEB, RAWK, false, R2L_IO_STATS>(sa, item, lane, acc);
+  }
+  r2l_stats_wave_partial(acc, lane, (double*)sa.s.out + (size_t)(bid * WPB + wave) * 6);
+}
+#endif
 template <int DEB, int RAWK, bool LUMA, int IO = R2L_IO_F32>
 R2L_BLOCKFN void r2l_static_stream_block(const R2LStaticStreamArgs& sa, int bid, int nblk, float* lds) {
   (void)lds;
   (void)nblk;
+#ifndef R2L_SERIAL
+  if constexpr (IO == R2L_IO_STATS) {
+    r2l_static_stream_stats_block<DEB, RAWK>(sa, bid, nblk);
+    return;
+  }
+#endif
   R2L_PHASE_BEGIN_N(R2L_STREAM_NT)
   const int item = bid * (R2L_STREAM_NT / 64) + (tid >> 6);  // one work item per wavefront
 #ifndef R2L_SERIAL

@@ -615,6 +615,18 @@ _DENOISE = {'gaussian_denoising': 1, 'median_denoising': 2, 'fft_denoising': 3}
 STATIC_OPTION_DEFAULTS = dict(sharp_radius=1.0, sharp_amount=1.0, gaussian_sigma=0.5, fft_fraction=0.3, median_kernel_size=3)
 
 
+def _check_static_names(debayer, sharpening, denoising):
+    known_sharp = {'sharpening_filter', 'unsharp_masking'}
+    known_den = {'median_denoising', 'gaussian_denoising', 'fft_denoising', 'tv_chambolle', 'tv_bregman',
+                 'bilateral'}
+    if debayer not in _DEBAYER:
+        raise NotImplementedError(f"debayer '{debayer}' is not built for the GPU (have: {list(_DEBAYER)})")
+    if sharpening in known_sharp and sharpening not in _SHARPEN:
+        raise NotImplementedError(f"sharpening '{sharpening}' is not built for the GPU")
+    if denoising in known_den and denoising not in _DENOISE:
+        raise NotImplementedError(f"denoising '{denoising}' is not built for the GPU")
+
+
 def static_pipeline(raw, camera_parameters, debayer='bilinear', sharpening='sharpening_filter',
                     denoising='gaussian_denoising', gamma=2.2, bits=16, mean_std=None, sharp_radius=1.0, sharp_amount=1.0,
                     median_kernel_size=3, gaussian_sigma=0.5, fft_fraction=0.3, out_dtype=None):
@@ -654,15 +666,7 @@ def static_pipeline(raw, camera_parameters, debayer='bilinear', sharpening='shar
         raw, denom = (raw if raw.is_contiguous() else raw.contiguous()), None
     else:
         raw, denom = _raw_arg(raw, bits)
-    known_sharp = {'sharpening_filter', 'unsharp_masking'}
-    known_den = {'median_denoising', 'gaussian_denoising', 'fft_denoising', 'tv_chambolle', 'tv_bregman',
-                 'bilateral'}
-    if debayer not in _DEBAYER:
-        raise NotImplementedError(f"debayer '{debayer}' is not built for the GPU (have: {list(_DEBAYER)})")
-    if sharpening in known_sharp and sharpening not in _SHARPEN:
-        raise NotImplementedError(f"sharpening '{sharpening}' is not built for the GPU")
-    if denoising in known_den and denoising not in _DENOISE:
-        raise NotImplementedError(f"denoising '{denoising}' is not built for the GPU")
+    _check_static_names(debayer, sharpening, denoising)
     bl, wb, ccm = camera_parameters
     cam = (ctypes.c_double * 16)(*[float(v) for v in list(bl) + list(wb) + list(ccm)])
     B, H, W = raw.shape
@@ -705,6 +709,88 @@ def static_io_why(raw, debayer='bilinear', sharpening='sharpening_filter', denoi
     why = lib.r2l_static_io_supported(frames, raw.shape[1], raw.shape[2], _DEBAYER.get(debayer, -1), _SHARPEN.get(sharpening, 0),
                                       _DENOISE.get(denoising, 0), ov)
     return why.decode() if why is not None else None
+
+
+# --------------------------------------------------------------------------------------------------
+# channel statistics: the mean / std of T.Normalize (get_statistics, pipeline_numpy.py:306-329)
+# --------------------------------------------------------------------------------------------------
+def channel_sums(x):
+    """(B,C,H,W) float32, C <= 4 -> float64[2C+1] on x's device: per-channel sums, sums of squares (both accumulated in float64
+    from exact terms, in a fixed order) and the pixel count B*H*W (r2l_channel_sums)."""
+    assert x.ndim == 4, f"needs dims (B, C, H, W), got {x.shape}"
+    x = _f32c(x, 'x')
+    B, C, H, W = x.shape
+    lib, stream = _lib.library_for(x)
+    nws = lib.r2l_channel_sums_workspace_bytes(B, C, H, W)
+    ws = torch.empty(max(nws, 8), dtype=torch.uint8, device=x.device)
+    sums = torch.empty(2 * C + 1, dtype=torch.float64, device=x.device)
+    lib.check(lib.r2l_channel_sums(ptr(x), ptr(sums), B, C, H, W, ptr(ws), nws, stream), 'r2l_channel_sums')
+    return sums
+
+
+def _static_option_vector(options):
+    unknown = set(options) - set(STATIC_OPTION_DEFAULTS)
+    if unknown:
+        raise TypeError(f'unknown static options {sorted(unknown)} (have: {sorted(STATIC_OPTION_DEFAULTS)})')
+    o = {**STATIC_OPTION_DEFAULTS, **options}
+    if o == STATIC_OPTION_DEFAULTS:
+        return None
+    return (ctypes.c_double * 5)(float(o['sharp_radius']), float(o['sharp_amount']), float(o['gaussian_sigma']),
+                                 float(o['fft_fraction']), float(o['median_kernel_size']))
+
+
+def static_stats_why(raw, debayer='bilinear', sharpening='sharpening_filter', denoising='gaussian_denoising', **options):
+    """why static_statistics does not run these frames and this chain as one statistics-only launch (r2l_static_stats_supported,
+    the predicate r2l_static_stats uses), or None where it does.  options: static_pipeline's numeric arguments."""
+    ov = _static_option_vector(options)
+    if raw.ndim != 3:
+        return 'needs dims (B, H, W)'
+    frames = 2 if raw.dtype == torch.float64 else (1 if raw.dtype in U16_DTYPES else 0)
+    lib, _ = _lib.library_for(raw)
+    why = lib.r2l_static_stats_supported(frames, raw.shape[1], raw.shape[2], _DEBAYER.get(debayer, -1), _SHARPEN.get(sharpening, 0),
+                                         _DENOISE.get(denoising, 0), ov)
+    return why.decode() if why is not None else None
+
+
+def static_statistics(raw, camera_parameters, debayer='bilinear', sharpening='sharpening_filter', denoising='gaussian_denoising',
+                      gamma=2.2, bits=16, **options):
+    """float64[7] on raw's device: per-channel sums and sums of squares of static_pipeline(raw, ...)'s float32, un-normalised
+    output, and its pixel count B*H*W -- what mean_std_from_sums turns into T.Normalize's mean and std.
+
+    Where one row-streaming kernel runs the chain (static_stats_why is None: the chains static_io_why serves) this is ONE
+    r2l_static_stats call: the kernel adds what it would have stored and stores nothing -- the (B,3,H,W) output never exists.
+    Everywhere else static_pipeline runs and channel_sums reads its output once.  Arguments as static_pipeline's."""
+    assert raw.ndim == 3, f"needs dims (B, H, W), got {raw.shape}"
+    _check_static_names(debayer, sharpening, denoising)
+    ov = _static_option_vector(options)
+    if static_stats_why(raw, debayer, sharpening, denoising, **options) is not None:
+        return channel_sums(static_pipeline(raw, camera_parameters, debayer, sharpening, denoising, gamma, bits=bits, **options))
+    f64 = raw.dtype == torch.float64
+    raw, denom = ((raw if raw.is_contiguous() else raw.contiguous()), None) if f64 else _raw_arg(raw, bits)
+    bl, wb, ccm = camera_parameters
+    cam = (ctypes.c_double * 16)(*[float(v) for v in list(bl) + list(wb) + list(ccm)])
+    B, H, W = raw.shape
+    lib, stream = _lib.library_for(raw)
+    codes = (_DEBAYER[debayer], _SHARPEN.get(sharpening, 0), _DENOISE.get(denoising, 0))
+    frames = 2 if f64 else (0 if denom is None else 1)
+    nws = lib.r2l_static_stats_workspace_bytes(frames, B, H, W, *codes, ov)
+    ws = torch.empty(nws, dtype=torch.uint8, device=raw.device)
+    sums = torch.empty(7, dtype=torch.float64, device=raw.device)
+    lib.check(lib.r2l_static_stats(ptr(raw), frames, float(denom or 1.0), ptr(sums), B, H, W, cam, *codes, float(gamma), ov,
+                                   ptr(ws), nws, stream), 'r2l_static_stats')
+    return sums
+
+
+def mean_std_from_sums(sums, unbiased=True):
+    """float64[2C+1] (channel_sums / static_statistics, or a sum of such vectors: they are additive) -> (mean, std), float32 of
+    shape (C,1,1): torch.mean / torch.std over (0, 2, 3) as get_statistics takes them of 4-D images (pipeline_numpy.py:306-329;
+    torch.std's default is unbiased).  float64 on the device of `sums`: mean = S1 / n, var = (S2 - S1^2 / n) / (n - 1) (/ n if
+    not unbiased), clamped at 0.  No host synchronisation."""
+    C = (sums.numel() - 1) // 2
+    s1, s2, n = sums[:C], sums[C:2 * C], sums[2 * C]
+    mean = s1 / n
+    var = ((s2 - s1 * s1 / n) / (n - 1 if unbiased else n)).clamp_min(0.0)
+    return mean.to(torch.float32).reshape(C, 1, 1), var.sqrt().to(torch.float32).reshape(C, 1, 1)
 
 
 def normalize(rgb, mean_std):

@@ -122,6 +122,24 @@ class StaticProcessing(nn.Module):
         self.buffer['processed_rgb'] = rgb
         return rgb
 
+    @torch.no_grad()
+    def statistics(self, frames, unbiased=True):
+        """(mean, std), float32 of shape (3,1,1): torch.mean / torch.std over (0, 2, 3) of this chain's float32, un-normalised
+        output on `frames` -- what get_statistics (pipeline_numpy.py:306-329) returns for a training subset, i.e. the
+        ``mean=`` / ``std=`` of a StaticProcessing that normalises.  `frames`: a (B,H,W) tensor, or any iterable of such
+        tensors (a loader of raw batches; batch and frame sizes may differ): the seven float64 sums of
+        functional.static_statistics are additive and are added on the device in iteration order.  Where one row-streaming
+        kernel runs the chain the output is never stored.  The module's own mean / std and output_dtype play no part;
+        ``stages`` and ``buffer`` are left alone; ``raw_bits`` and the numeric options count as in forward."""
+        total = None
+        for raw in ([frames] if torch.is_tensor(frames) else frames):
+            s = F_.static_statistics(raw, self.camera_parameters, self.debayer, self.sharpening, self.denoising, self.gamma,
+                                     bits=self.raw_bits, **getattr(self, 'options', {}))
+            total = s if total is None else total + s
+        if total is None:
+            raise ValueError('statistics() needs at least one batch of frames')
+        return F_.mean_std_from_sums(total, unbiased)
+
     def _mean_std_host(self):
         """the six floats of the mean_std buffer on the host (the kernels take them as launch arguments), read
         back once per value of the buffer"""
