@@ -115,7 +115,9 @@ R2L_HD float r2l_row_shl1(float x, float edge) { return r2l_ls::dpp(edge, x, 0x1
 typedef float4 r2l_f4;
 typedef float2 r2l_f2;
 // v_log_f32 / v_exp_f32 are base-2 and 1 ULP; inputs here are >= 1e-5 (or exactly 0) so the
-// denormal pre-scaling of logf()/expf() is not needed.  v_rcp_f32 is 1 ULP.
+// denormal pre-scaling of logf()/expf() is not needed.  v_rcp_f32 is 1 ULP.  (">= 1e-5" holds for a NaN too only because the
+// clip in front, fminf(fmaxf(rgb, 1e-5f), 1.0f), returns 1e-5 for a NaN where torch.clip keeps it: a NaN frame value comes out
+// finite -- INTEGRATION.md, "Values outside the ordinary"; tests/value_domain_checks.py part D.)
 R2L_HD float r2l_log2(float x) { return __builtin_amdgcn_logf(x); }
 R2L_HD float r2l_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 R2L_HD float r2l_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
