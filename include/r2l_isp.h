@@ -416,6 +416,24 @@ int r2l_static_fwd_io(const void *raw, int frames, float denom, void *out, int o
                       const double *options_host, const float *mean_std_host, void *workspace, size_t workspace_bytes,
                       void *stream);
 
+/* ---- output epilogue of the static chains: the weak augmentation as part of the stores ------------------------------
+ * r2l_static_fwd_epilogue = r2l_static_fwd_io whose output is rot90^k(vflip(hflip(.))) of what that call writes, plane by plane:
+ * `epilogue` holds R2L_STEP_EPI_HFLIP / R2L_STEP_EPI_VFLIP / k << R2L_STEP_EPI_ROT_SHIFT, the encoding of the step's `phase`,
+ * and the result is bit for bit r2l_augment(r2l_static_fwd_io(...)), narrowed afterwards where out_io is a 16-bit type (the
+ * narrowing is element-wise: the order does not matter).  epilogue = 0 is exactly r2l_static_fwd_io.  Any other bit: -1.
+ * A call with an epilogue is served where ONE launch of a row-streaming kernel runs the chain (what r2l_static_io_supported
+ * serves) on float32 or 16-bit-container frames, for k even: pixel (y, x) goes to element s0 + sr y + sc x of its plane with
+ * sc = +-1, so a lane's 4 pixels stay one 16-byte (8-byte) store.  r2l_static_epilogue_supported returns NULL there and
+ * otherwise the reason (a static string): k odd, float64 frames, Menon2007 / fft_denoising / the 5x5 median (plane passes),
+ * W % 4 != 0, W > 2048 (1024 behind unsharp_masking), the serial emulation build; it needs no GPU.  An unserved call returns -3
+ * with that reason in r2l_last_error() and writes nothing: the caller then runs r2l_static_fwd_io and r2l_augment.            */
+const char *r2l_static_epilogue_supported(int frames, int H, int W, int debayer, int sharpening, int denoising,
+                                          const double *options_host, int out_io, int epilogue);
+int r2l_static_fwd_epilogue(const void *raw, int frames, float denom, void *out, int out_io, int B, int H, int W,
+                            const double *camera_host, int debayer, int sharpening, int denoising, double gamma,
+                            const double *options_host, const float *mean_std_host, void *workspace,
+                            size_t workspace_bytes, void *stream, int epilogue);
+
 /* ---- channel statistics: the mean / std of T.Normalize(mean, std) (get_statistics, pipeline_numpy.py:306-329) ------------------------
  * r2l_static_stats runs a static chain WITHOUT storing its output and returns, in float64 on the device,
  *   sums[0..2] = sum over all pixels of v, per channel;  sums[3..5] = sum of v * v;  sums[6] = the pixel count B * H * W

@@ -175,6 +175,13 @@ _SIGNATURES = {
                                          ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_double),
                                          ctypes.POINTER(ctypes.c_float), ctypes.c_void_p, ctypes.c_size_t,
                                          ctypes.c_void_p]),
+    'r2l_static_epilogue_supported': (ctypes.c_char_p, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_double), ctypes.c_int,
+                                                        ctypes.c_int]),
+    'r2l_static_fwd_epilogue': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                               ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.c_void_p,
+                                               ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int]),
     'r2l_static_stats_supported': (ctypes.c_char_p, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_double)]),
     'r2l_static_stats_workspace_bytes': (ctypes.c_size_t, [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_double)]),
     'r2l_static_stats': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,

@@ -424,6 +424,21 @@ R2L_STREAM_KERNELS_IO(_bf16, R2L_IO_BF16)
 R2L_STREAM_KERNELS_IO(_f16, R2L_IO_F16)
 // ... and storing nothing: the channel sums of what the float32 siblings store (r2l_static_stats)
 R2L_STREAM_KERNELS_IO(_stats, R2L_IO_STATS)
+// ... and storing every row at its augmented position (r2l_static_fwd_epilogue: R2LEpi with sc = +-1, launch arguments): float32 and
+// 16-bit-container frames x the three output types, at their siblings' occupancy
+#define R2L_STREAM_KERNEL_EPI(name, DEB, RAWK, IO, OCC)                                                  \
+  R2L_BLOCKFN void name##_block(const R2LStaticStreamArgs& sa, int bid, int nblk, float* lds) {          \
+    r2l_static_stream_block<DEB, RAWK, false, IO, true>(sa, bid, nblk, lds);                             \
+  }                                                                                                      \
+  R2L_KERNEL_NT(name, R2LStaticStreamArgs, name##_block, R2L_STREAM_NT, OCC)
+#define R2L_STREAM_KERNELS_EPI(sfx, IO)                                                                             \
+  R2L_STREAM_KERNEL_EPI(r2l_launch_static_stream_bilinear##sfx, 0, R2L_RAW_F32, IO, R2L_STREAM_OCC_BILINEAR)        \
+  R2L_STREAM_KERNEL_EPI(r2l_launch_static_stream_malvar##sfx, 1, R2L_RAW_F32, IO, R2L_STREAM_OCC_MALVAR)            \
+  R2L_STREAM_KERNEL_EPI(r2l_launch_static_stream_bilinear_u16##sfx, 0, R2L_RAW_U16, IO, R2L_STREAM_OCC_BILINEAR)    \
+  R2L_STREAM_KERNEL_EPI(r2l_launch_static_stream_malvar_u16##sfx, 1, R2L_RAW_U16, IO, R2L_STREAM_OCC_MALVAR)
+R2L_STREAM_KERNELS_EPI(_epi, R2L_IO_F32)
+R2L_STREAM_KERNELS_EPI(_bf16_epi, R2L_IO_BF16)
+R2L_STREAM_KERNELS_EPI(_f16_epi, R2L_IO_F16)
 #endif
 R2L_KERNEL(r2l_launch_plane_filter, R2LPlaneArgs, r2l_plane_filter_block, 4)
 R2L_KERNEL(r2l_launch_spec_mask, R2LSpecMaskArgs, r2l_spec_mask_block, 4)
@@ -442,19 +457,19 @@ R2L_KERNEL(r2l_launch_static_menon, R2LMenonArgs, r2l_static_menon_block, 4)
 // (the workgroup size and the LDS size follow the frame width at launch time: 64 threads and 16.1 KB per strip)
 #define R2L_MAX_DEVICES 64
 #ifdef R2L_LOCKSTEP
-#define R2L_CHAIN_KERNEL_IO(name, RAWK, DEB, SH, DN, IO)                                                      \
+#define R2L_CHAIN_KERNEL_IO(name, RAWK, DEB, SH, DN, IO, EPI)                                                 \
   static int name(const R2LStaticChainArgs& a, int grid, void* stream) {                                      \
     (void)stream;                                                                                             \
     r2l_ls_note(#name);                                                                                       \
     r2l_ls::launch(#name, grid, a.nw * 64, 2 * (size_t)R2L_CHAIN_LDS_DOUBLES(a.nw, SH), &a,                   \
-                   [&](int b_, float* lds_) { r2l_static_chain_block<RAWK, DEB, SH, DN, IO>(a, b_, grid, lds_); }); \
+                   [&](int b_, float* lds_) { r2l_static_chain_block<RAWK, DEB, SH, DN, IO, EPI>(a, b_, grid, lds_); }); \
     return 0;                                                                                                 \
   }
 #else
-#define R2L_CHAIN_KERNEL_IO(name, RAWK, DEB, SH, DN, IO)                                                      \
+#define R2L_CHAIN_KERNEL_IO(name, RAWK, DEB, SH, DN, IO, EPI)                                                 \
   __global__ __launch_bounds__((SH) ? 256 : 512, (SH) ? R2L_CHAIN_OCC_SH : R2L_CHAIN_OCC) void name##_kernel(const R2LStaticChainArgs a) { \
     extern __shared__ __attribute__((aligned(16))) float r2l_chain_lds[];                                     \
-    r2l_static_chain_block<RAWK, DEB, SH, DN, IO>(a, (int)blockIdx.x, (int)gridDim.x, r2l_chain_lds);         \
+    r2l_static_chain_block<RAWK, DEB, SH, DN, IO, EPI>(a, (int)blockIdx.x, (int)gridDim.x, r2l_chain_lds);    \
   }                                                                                                           \
   static int name(const R2LStaticChainArgs& a, int grid, void* stream) {                                      \
     const size_t lds_bytes = sizeof(double) * R2L_CHAIN_LDS_DOUBLES(a.nw, SH);                                \
@@ -477,15 +492,17 @@ R2L_KERNEL(r2l_launch_static_menon, R2LMenonArgs, r2l_static_menon_block, 4)
   }
 #endif
 // [16-bit / float64 frames] x [Malvar2004] x [unsharp_masking] x [median_denoising] x [16-bit output: float32 / 16-bit frames]
-#define R2L_CHAIN_KERNELS_IO(sfx, RAWK, IO)                                                   \
-  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain##sfx, RAWK, 0, 0, 0, IO)                        \
-  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_median##sfx, RAWK, 0, 0, 1, IO)                 \
-  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_unsharp##sfx, RAWK, 0, 1, 0, IO)                \
-  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_unsharp_median##sfx, RAWK, 0, 1, 1, IO)         \
-  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_malvar##sfx, RAWK, 1, 0, 0, IO)                 \
-  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_malvar_median##sfx, RAWK, 1, 0, 1, IO)          \
-  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_malvar_unsharp##sfx, RAWK, 1, 1, 0, IO)         \
-  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_malvar_unsharp_median##sfx, RAWK, 1, 1, 1, IO)
+// x [EPI: the output epilogue, r2l_static_fwd_epilogue: float32 / 16-bit frames, the three output types]
+#define R2L_CHAIN_KERNELS_IO_EPI(sfx, RAWK, IO, EPI)                                               \
+  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain##sfx, RAWK, 0, 0, 0, IO, EPI)                        \
+  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_median##sfx, RAWK, 0, 0, 1, IO, EPI)                 \
+  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_unsharp##sfx, RAWK, 0, 1, 0, IO, EPI)                \
+  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_unsharp_median##sfx, RAWK, 0, 1, 1, IO, EPI)         \
+  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_malvar##sfx, RAWK, 1, 0, 0, IO, EPI)                 \
+  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_malvar_median##sfx, RAWK, 1, 0, 1, IO, EPI)          \
+  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_malvar_unsharp##sfx, RAWK, 1, 1, 0, IO, EPI)         \
+  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_malvar_unsharp_median##sfx, RAWK, 1, 1, 1, IO, EPI)
+#define R2L_CHAIN_KERNELS_IO(sfx, RAWK, IO) R2L_CHAIN_KERNELS_IO_EPI(sfx, RAWK, IO, false)
 #define R2L_CHAIN_KERNELS(sfx, RAWK) R2L_CHAIN_KERNELS_IO(sfx, RAWK, R2L_IO_F32)
 R2L_CHAIN_KERNELS(, R2L_RAW_F32)
 R2L_CHAIN_KERNELS(_u16, R2L_RAW_U16)
@@ -496,6 +513,12 @@ R2L_CHAIN_KERNELS_IO(_f16, R2L_RAW_F32, R2L_IO_F16)
 R2L_CHAIN_KERNELS_IO(_u16_f16, R2L_RAW_U16, R2L_IO_F16)
 R2L_CHAIN_KERNELS_IO(_stats, R2L_RAW_F32, R2L_IO_STATS)
 R2L_CHAIN_KERNELS_IO(_u16_stats, R2L_RAW_U16, R2L_IO_STATS)
+R2L_CHAIN_KERNELS_IO_EPI(_epi, R2L_RAW_F32, R2L_IO_F32, true)
+R2L_CHAIN_KERNELS_IO_EPI(_u16_epi, R2L_RAW_U16, R2L_IO_F32, true)
+R2L_CHAIN_KERNELS_IO_EPI(_bf16_epi, R2L_RAW_F32, R2L_IO_BF16, true)
+R2L_CHAIN_KERNELS_IO_EPI(_u16_bf16_epi, R2L_RAW_U16, R2L_IO_BF16, true)
+R2L_CHAIN_KERNELS_IO_EPI(_f16_epi, R2L_RAW_F32, R2L_IO_F16, true)
+R2L_CHAIN_KERNELS_IO_EPI(_u16_f16_epi, R2L_RAW_U16, R2L_IO_F16, true)
 #endif
 R2L_KERNEL(r2l_launch_static_short, R2LStaticArgs, r2l_static_short_block<GStatic>,
            R2L_STATIC_SHORT_LDS_FLOATS)
@@ -1910,6 +1933,15 @@ static const R2LStreamLaunch r2l_static_stream_table[][3][2] = {R2L_STREAM_ROW(r
 static const R2LStreamLaunch r2l_static_luma_table[3][2] = R2L_STREAM_ROW(r2l_launch_static_luma, );
 #undef R2L_STREAM_ROW
 #ifndef R2L_SERIAL
+// the epilogue forms (r2l_static_fwd_epilogue): [output: float32 | bfloat16 | float16][frames: float32 | 16-bit][bilinear | Malvar2004]
+#define R2L_STREAM_ROW_EPI(sfx)                                                                  \
+  {{r2l_launch_static_stream_bilinear##sfx, r2l_launch_static_stream_malvar##sfx},               \
+   {r2l_launch_static_stream_bilinear_u16##sfx, r2l_launch_static_stream_malvar_u16##sfx}}
+static const R2LStreamLaunch r2l_static_stream_epi_table[3][2][2] = {R2L_STREAM_ROW_EPI(_epi), R2L_STREAM_ROW_EPI(_bf16_epi),
+                                                                     R2L_STREAM_ROW_EPI(_f16_epi)};
+#undef R2L_STREAM_ROW_EPI
+#endif
+#ifndef R2L_SERIAL
 typedef int (*R2LChainLaunch)(const R2LStaticChainArgs&, int, void*);
 #define R2L_CHAIN_ROW(sfx)                                                                                          \
   {{{r2l_launch_static_chain##sfx, r2l_launch_static_chain_median##sfx},                                            \
@@ -1921,6 +1953,10 @@ static const R2LChainLaunch r2l_static_chain_table[4][3][2][2][2] = {{R2L_CHAIN_
                                                                      {R2L_CHAIN_ROW(_bf16), R2L_CHAIN_ROW(_u16_bf16)},
                                                                      {R2L_CHAIN_ROW(_f16), R2L_CHAIN_ROW(_u16_f16)},
                                                                      {R2L_CHAIN_ROW(_stats), R2L_CHAIN_ROW(_u16_stats)}};
+// the epilogue forms: [output: float32 | bfloat16 | float16][frames: float32 | 16-bit][Malvar2004][unsharp_masking][median_denoising]
+static const R2LChainLaunch r2l_static_chain_epi_table[3][2][2][2][2] = {{R2L_CHAIN_ROW(_epi), R2L_CHAIN_ROW(_u16_epi)},
+                                                                         {R2L_CHAIN_ROW(_bf16_epi), R2L_CHAIN_ROW(_u16_bf16_epi)},
+                                                                         {R2L_CHAIN_ROW(_f16_epi), R2L_CHAIN_ROW(_u16_f16_epi)}};
 #undef R2L_CHAIN_ROW
 #endif
 
@@ -1934,6 +1970,7 @@ struct R2LStaticPlan {
   const char* refused;     // why the call cannot run at all (-4), or null
   const char* no_io;       // why a 16-bit output is not served (-3), or null
   const char* no_stats;    // why r2l_static_stats is not served (-3), or null: the same kernels in their statistics form
+  const char* no_epi;      // why an output epilogue is not served (-3), or null (also without one): the same kernels in their epilogue form
   int nparts;              // io = R2L_IO_STATS: the partials double[6] the launch leaves in the workspace, one per wavefront
   int err;                 // rocFFT could not plan the transforms (its text is in r2l_err)
   bool too_large;          // more workgroups than a launch takes
@@ -1950,9 +1987,10 @@ struct R2LStaticPlan {
 };
 // frames: R2L_FRAMES_*; io: R2L_IO_* of the output, or R2L_IO_STATS: none, the channel sums (r2l_static_stats).  The only reader of the static chains' overrides of diagnostic builds
 // (R2L_STATIC_TILED, R2L_CHAIN_BAND, R2L_STREAM_BANDS, R2L_GRID_STATIC*).  sized = false: without rocFFT's work buffer in
-// `workspace_bytes` -- for callers that ask for `no_io` alone and must not open the library
+// `workspace_bytes` -- for callers that ask for `no_io` alone and must not open the library.  epilogue: R2L_STEP_EPI_* bits (r2l_static_fwd_epilogue),
+// 0: none -- the plan of every other entry
 static R2LStaticPlan r2l_static_plan(int frames, int B, int H, int W, int debayer, int sharpening, int denoising,
-                                     const R2LStaticOpts& opt, int io, bool sized = true) {
+                                     const R2LStaticOpts& opt, int io, bool sized = true, int epilogue = 0) {
   R2LStaticPlan p = {};
   const bool f64 = frames == R2L_FRAMES_F64, menon = debayer == R2L_DEBAYER_MENON2007, malvar = debayer == R2L_DEBAYER_MALVAR2004;
   const bool unsharp = sharpening == R2L_SHARPEN_UNSHARP, median = denoising == R2L_DENOISE_MEDIAN;
@@ -1984,20 +2022,33 @@ static R2LStaticPlan r2l_static_plan(int frames, int B, int H, int W, int debaye
     p.refused = "r2l_static_fwd: menon2007 runs as plane passes, which need W % 4 == 0 (and frames of at least 4 x 4)";
   if (p.route == R2L_ROUTE_PLANES && !quads) p.refused = "r2l_static_fwd: this chain runs as plane passes, which need W % 4 == 0";
 
-  // a 16-bit output, or none (the statistics form): what runs as one launch of a row-streaming kernel on frames up to 2048 columns
-  const auto one_launch = [&](bool stats) -> const char* {
+  // a 16-bit output (form 0), none (1: the statistics form) or an output epilogue (2): what runs as one launch of a row-streaming
+  // kernel on frames up to 2048 columns
+  const auto one_launch = [&](int form) -> const char* {
+    const bool stats = form == 1, epi = form == 2;
     if (frames != R2L_FRAMES_F32 && frames != R2L_FRAMES_U16 && frames != R2L_FRAMES_F64) return "frames must be one of R2L_FRAMES_*";
     if (H < 4 || W < 4 || (H & 1) || (W & 1)) return "H and W must be even and >= 4";
+    if (epi && f64) return "float64 frames have no epilogue form of the static kernels";
 #ifdef R2L_SERIAL
-    return stats ? "the serial emulation has no statistics form of the static kernels (not expressible one lane at a time)"
-                 : "the serial emulation has no 16-bit form of the static kernels";
+    return epi     ? "the serial emulation has no epilogue form of the static kernels"
+           : stats ? "the serial emulation has no statistics form of the static kernels (not expressible one lane at a time)"
+                   : "the serial emulation has no 16-bit form of the static kernels";
 #else
-    if (menon) return stats ? "menon2007 runs as plane passes, which have no statistics form" : "menon2007 runs as plane passes, which store float32";
+    if (menon)
+      return epi     ? "menon2007 runs as plane passes, which have no epilogue form"
+             : stats ? "menon2007 runs as plane passes, which have no statistics form"
+                     : "menon2007 runs as plane passes, which store float32";
     if (debayer != R2L_DEBAYER_BILINEAR && !malvar) return "unknown debayer";
     if (sharpening != R2L_SHARPEN_NONE && sharpening != R2L_SHARPEN_FILTER && !unsharp) return "unknown sharpening";
     if (denoising != R2L_DENOISE_NONE && denoising != R2L_DENOISE_GAUSSIAN && !median && !p.fft) return "unknown denoising";
-    if (p.fft) return stats ? "fft_denoising runs as plane passes, which have no statistics form" : "fft_denoising runs as plane passes, which store float32";
-    if (med5) return stats ? "the 5x5 median runs as a plane pass, which has no statistics form" : "the 5x5 median runs as a plane pass, which stores float32";
+    if (p.fft)
+      return epi     ? "fft_denoising runs as plane passes, which have no epilogue form"
+             : stats ? "fft_denoising runs as plane passes, which have no statistics form"
+                     : "fft_denoising runs as plane passes, which store float32";
+    if (med5)
+      return epi     ? "the 5x5 median runs as a plane pass, which has no epilogue form"
+             : stats ? "the 5x5 median runs as a plane pass, which has no statistics form"
+                     : "the 5x5 median runs as a plane pass, which stores float32";
     if (!quads) return "needs W % 4 == 0 (the row-streaming kernels)";
     if (W > 2048) return "needs W <= 2048";
     if (p.route == R2L_ROUTE_STREAM) return nullptr;
@@ -2008,8 +2059,17 @@ static R2LStaticPlan r2l_static_plan(int frames, int B, int H, int W, int debaye
     return nullptr;
 #endif
   };
-  p.no_io = one_launch(false);
-  p.no_stats = one_launch(true);
+  p.no_io = one_launch(0);
+  p.no_stats = one_launch(1);
+  // an output epilogue: k even only -- a row-walking kernel's stores under a rotation by 90 degrees land one element per row of
+  // the rotated tensor, which the permutation kernel does better
+  const bool want_epi = (epilogue & R2L_STEP_EPI_MASK) != 0;
+  p.no_epi = !want_epi ? nullptr
+             : ((epilogue >> R2L_STEP_EPI_ROT_SHIFT) & 1)
+                 ? "a rotation by 90 or 270 degrees (k odd) is not part of the row-streaming kernels' stores"
+                 : one_launch(2);
+  const bool epi = want_epi && !p.no_epi;
+  (void)epi;
   if (B < 1 || H < 1 || W < 1) return p;
 
   const size_t px = (size_t)B * H * W;
@@ -2063,7 +2123,7 @@ static R2LStaticPlan r2l_static_plan(int frames, int B, int H, int W, int debaye
         p.nparts = (int)grid * p.nseg;
         p.workspace_bytes = sizeof(double) * 6 * (size_t)p.nparts;
       }
-      p.chain = r2l_static_chain_table[out][kind][malvar][unsharp][median];
+      p.chain = epi ? r2l_static_chain_epi_table[out][kind][malvar][unsharp][median] : r2l_static_chain_table[out][kind][malvar][unsharp][median];
 #endif
       break;
     }
@@ -2098,6 +2158,9 @@ static R2LStaticPlan r2l_static_plan(int frames, int B, int H, int W, int debaye
         p.workspace_bytes = sizeof(double) * 6 * (size_t)p.nparts;
       }
       p.stream = p.route == R2L_ROUTE_PLANES ? r2l_static_luma_table[kind][malvar] : r2l_static_stream_table[out][kind][malvar];
+#ifndef R2L_SERIAL
+      if (epi) p.stream = r2l_static_stream_epi_table[out][kind][malvar];
+#endif
       break;
     }
     default: {  // persistent 64 x 64 tile walkers
@@ -2158,7 +2221,9 @@ static int r2l_static_lowpass_finish(const R2LStaticPlan& p, const R2LStaticArgs
 }
 
 // a plan that is neither refused nor too large, and a workspace of its workspace_bytes
-static int r2l_static_launch(const R2LStaticPlan& p, const R2LStaticArgs& a, void* workspace, void* stream) {
+// ep: the map of an epilogue form the plan chose (STREAM / CHAIN), otherwise off
+static int r2l_static_launch(const R2LStaticPlan& p, const R2LStaticArgs& a, void* workspace, void* stream,
+                             const R2LEpi& ep = R2LEpi{0, 0, 0, 0}) {
   const size_t px = (size_t)a.B * a.H * a.W;
   switch (p.route) {
     case R2L_ROUTE_MENON: {
@@ -2193,6 +2258,7 @@ static int r2l_static_launch(const R2LStaticPlan& p, const R2LStaticArgs& a, voi
       ca.nband = p.nband;
       ca.band_h = p.band_h;
       ca.nw = p.nseg;
+      ca.ep = ep;
       return p.chain(ca, p.grid, stream);
     }
 #endif
@@ -2207,6 +2273,7 @@ static int r2l_static_launch(const R2LStaticPlan& p, const R2LStaticArgs& a, voi
       sa.luma_out = nullptr;
       sa.luma_in = nullptr;
       sa.lin_out = nullptr;
+      sa.ep = ep;
       if (p.route == R2L_ROUTE_STREAM) return p.stream(sa, p.grid, stream);
       double* cur = (double*)workspace;
       sa.luma_out = cur;
@@ -2243,6 +2310,9 @@ struct R2LStaticCall {
   size_t workspace_bytes;
   void* stream;
   double* sums = nullptr;  // r2l_static_stats (io = R2L_IO_STATS, out = null): double[7], instead of an output
+  // r2l_static_fwd_epilogue: where the output goes, as R2L_STEP_EPI_* bits; the affine map R2LEpi follows from them and the frame
+  // size (r2l_epi_from_phase) once the plan has said that an epilogue form serves the call.  0: none
+  int epilogue = 0;
 };
 // the partials a statistics launch left in the workspace -> sums[0..5], the pixel count -> sums[6]
 static int r2l_static_sums_finish(const R2LStaticPlan& p, const R2LStaticCall& c) {
@@ -2274,7 +2344,11 @@ static int r2l_static_fwd_impl(const R2LStaticCall& c) {
   // (the statistics forms store nothing: their `out` is where each wavefront leaves its partial, the workspace)
   r2l_static_setup(a, raw, c.io == R2L_IO_STATS ? (float*)c.workspace : c.out, c.B, c.H, c.W, c.camera_host, c.debayer, c.sharpening,
                    c.denoising, c.gamma, c.mean_std_host, c.opt);
-  const R2LStaticPlan p = r2l_static_plan(c.frames, c.B, c.H, c.W, c.debayer, c.sharpening, c.denoising, c.opt, c.io);
+  const R2LStaticPlan p = r2l_static_plan(c.frames, c.B, c.H, c.W, c.debayer, c.sharpening, c.denoising, c.opt, c.io, true, c.epilogue);
+  if (p.no_epi) return r2l_fail(-3, std::string("r2l_static_fwd_epilogue: an output epilogue is not served here: ") + p.no_epi);
+  R2LEpi ep = R2LEpi{0, 0, 0, 0};
+  if (c.epilogue)
+    if (int e = r2l_epi_from_phase(c.epilogue, c.H, c.W, ep)) return e;
   if (c.io == R2L_IO_STATS && p.no_stats)
     return r2l_fail(-3, std::string("r2l_static_stats: not served here: ") + p.no_stats);
   if (c.io != R2L_IO_F32 && c.io != R2L_IO_STATS && p.no_io)
@@ -2284,7 +2358,7 @@ static int r2l_static_fwd_impl(const R2LStaticCall& c) {
   if (p.workspace_bytes && (!c.workspace || c.workspace_bytes < p.workspace_bytes))
     return r2l_fail(-2, "r2l_static_fwd: workspace too small (r2l_static_workspace_bytes)");
   if (p.too_large) return r2l_fail(-1, "r2l_static_fwd: batch too large");
-  if (int e = r2l_static_launch(p, a, c.workspace, c.stream)) return e;
+  if (int e = r2l_static_launch(p, a, c.workspace, c.stream, ep)) return e;
   return c.io == R2L_IO_STATS ? r2l_static_sums_finish(p, c) : 0;
 }
 
@@ -2407,20 +2481,51 @@ static const char* r2l_static_io_why(int frames, int H, int W, int debayer, int 
 const char* r2l_static_io_supported(int frames, int H, int W, int debayer, int sharpening, int denoising, const double* options_host) {
   return r2l_static_io_why(frames, H, W, debayer, sharpening, denoising, r2l_static_opts(options_host));
 }
-int r2l_static_fwd_io(const void* raw, int frames, float denom, void* out, int out_io, int B, int H, int W,
-                      const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
-                      const double* options_host, const float* mean_std_host, void* workspace, size_t workspace_bytes,
-                      void* stream) {
+// r2l_static_fwd_io and r2l_static_fwd_epilogue (epilogue: R2L_STEP_EPI_* bits, 0 for the former)
+static int r2l_static_fwd_io_impl(const void* raw, int frames, float denom, void* out, int out_io, int B, int H, int W,
+                                  const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
+                                  const double* options_host, const float* mean_std_host, void* workspace, size_t workspace_bytes,
+                                  void* stream, int epilogue) {
   if (out_io != R2L_IO_F32 && out_io != R2L_IO_BF16 && out_io != R2L_IO_F16)
     return r2l_fail(-1, "r2l_static_fwd_io: out_io must be one of R2L_IO_*");
-  const R2LStaticCall c{raw, frames, denom, (float*)out, out_io, B, H, W, camera_host, debayer, sharpening, denoising, gamma, mean_std_host,
+  R2LStaticCall c{raw, frames, denom, (float*)out, out_io, B, H, W, camera_host, debayer, sharpening, denoising, gamma, mean_std_host,
                   r2l_static_opts(options_host), workspace, workspace_bytes, stream};
+  c.epilogue = epilogue;
+  if (epilogue)
+    if (const char* why = r2l_static_plan(frames, 1, H, W, debayer, sharpening, denoising, c.opt, out_io, false, epilogue).no_epi)
+      return r2l_fail(-3, std::string("r2l_static_fwd_epilogue: an output epilogue is not served here: ") + why);
   if (out_io != R2L_IO_F32) {
     if (const char* why = r2l_static_io_why(frames, H, W, debayer, sharpening, denoising, c.opt))
       return r2l_fail(-3, std::string("r2l_static_fwd_io: a 16-bit output is not served here: ") + why);
     if ((uintptr_t)out % 8) return r2l_fail(-1, "r2l_static_fwd_io: the 16-bit output must be 8-byte aligned");
   }
+  if (epilogue && out_io == R2L_IO_F32 && (uintptr_t)out % 16)
+    return r2l_fail(-1, "r2l_static_fwd_epilogue: the float32 output must be 16-byte aligned");
   return r2l_static_fwd_impl(c);
+}
+int r2l_static_fwd_io(const void* raw, int frames, float denom, void* out, int out_io, int B, int H, int W,
+                      const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
+                      const double* options_host, const float* mean_std_host, void* workspace, size_t workspace_bytes,
+                      void* stream) {
+  return r2l_static_fwd_io_impl(raw, frames, denom, out, out_io, B, H, W, camera_host, debayer, sharpening, denoising, gamma, options_host,
+                                mean_std_host, workspace, workspace_bytes, stream, 0);
+}
+
+// ---- output epilogue of the static chains (include/r2l_isp.h: r2l_static_fwd_epilogue) ---------------------------------------------
+const char* r2l_static_epilogue_supported(int frames, int H, int W, int debayer, int sharpening, int denoising, const double* options_host,
+                                          int out_io, int epilogue) {
+  if (out_io != R2L_IO_F32 && out_io != R2L_IO_BF16 && out_io != R2L_IO_F16) return "out_io must be one of R2L_IO_*";
+  if (epilogue & ~R2L_STEP_EPI_MASK) return "epilogue holds bits outside R2L_STEP_EPI_*";
+  const R2LStaticPlan p = r2l_static_plan(frames, 1, H, W, debayer, sharpening, denoising, r2l_static_opts(options_host), out_io, false, epilogue);
+  return (epilogue & R2L_STEP_EPI_MASK) ? p.no_epi : (out_io != R2L_IO_F32 ? p.no_io : nullptr);
+}
+int r2l_static_fwd_epilogue(const void* raw, int frames, float denom, void* out, int out_io, int B, int H, int W,
+                            const double* camera_host, int debayer, int sharpening, int denoising, double gamma,
+                            const double* options_host, const float* mean_std_host, void* workspace, size_t workspace_bytes,
+                            void* stream, int epilogue) {
+  if (epilogue & ~R2L_STEP_EPI_MASK) return r2l_fail(-1, "r2l_static_fwd_epilogue: epilogue holds bits outside R2L_STEP_EPI_*");
+  return r2l_static_fwd_io_impl(raw, frames, denom, out, out_io, B, H, W, camera_host, debayer, sharpening, denoising, gamma, options_host,
+                                mean_std_host, workspace, workspace_bytes, stream, epilogue);
 }
 
 // ---- channel statistics (include/r2l_isp.h: r2l_static_stats, r2l_channel_sums) ---------------------------------------------------

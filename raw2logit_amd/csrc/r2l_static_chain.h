@@ -39,6 +39,7 @@ struct R2LStaticChainArgs {
   R2LStaticArgs s;
   int nband, band_h;
   int nw;  // wavefronts per workgroup = 256-column strips per image row (1, 2, 4, 8)
+  R2LEpi ep;  // EPI instantiations (r2l_static_fwd_epilogue): where the output goes (R2LEpi, sc = +-1); behind everything else
 };
 
 // float64 value of x in the previous / next lane of the wavefront; lane 0 / lane 63 get `edge`
@@ -102,10 +103,12 @@ R2L_HD R2LStaticArgsK r2l_chain_consts() {
 #endif
 }
 
-template <int DEB, int SH, int DN, int K0, int IO = R2L_IO_F32, class RWT = double>
+// EPI (r2l_static_fwd_epilogue): both store sites put the row at its augmented position, r2l_static_store_row_epi
+template <int DEB, int SH, int DN, int K0, int IO = R2L_IO_F32, bool EPI = false, class RWT = double>
 R2L_HD void r2l_chain_step(const R2LStaticArgs& a_, R2LChainState<DEB, SH, DN, RWT>& st, int q_, int y0, int y1, bool le,
                            bool re, int NW, int wave, int lane, double* ex, r2l_d2* fifo, float* outb, size_t plane,
-                           int x0, bool store_ok, double* acc = nullptr) {
+                           int x0, bool store_ok, double* acc = nullptr, const R2LEpi& ep = R2LEpi{0, 0, 0, 0}) {
+  static_assert(!EPI || IO != R2L_IO_STATS, "the statistics forms store nothing");
   constexpr int PY = K0 & 1;
   constexpr int FR = R2L_CHAIN_FIFO_ROWS(SH);
   const int H = a_.H;
@@ -298,6 +301,9 @@ R2L_HD void r2l_chain_step(const R2LStaticArgs& a_, R2LChainState<DEB, SH, DN, R
         return;
       }
       r2l_static_normalize<4>(a, x);
+      if constexpr (EPI) {
+        r2l_static_store_row_epi<IO>(outb, plane, r2l_epi_off(ep, y, x0), ep.sc < 0, x, store_ok);
+      } else
       if constexpr (IO != R2L_IO_F32) {  // 16-bit output (r2l_static_fwd_io): one 8-byte store per channel
         r2l_stream_store_row<IO>(outb, plane, (size_t)y * a_.W + x0, x, store_ok);
       } else
@@ -377,6 +383,9 @@ R2L_HD void r2l_chain_step(const R2LStaticArgs& a_, R2LChainState<DEB, SH, DN, R
       return;
     }
     r2l_static_normalize<4>(a, x);
+    if constexpr (EPI) {
+      r2l_static_store_row_epi<IO>(outb, plane, r2l_epi_off(ep, y, x0), ep.sc < 0, x, store_ok);
+    } else
     if constexpr (IO != R2L_IO_F32) {
       r2l_stream_store_row<IO>(outb, plane, (size_t)y * a_.W + x0, x, store_ok);
     } else
@@ -396,7 +405,7 @@ R2L_HD void r2l_chain_step(const R2LStaticArgs& a_, R2LChainState<DEB, SH, DN, R
 }
 
 // one band of one image: work item `bid` of B * nband
-template <int RAWK, int DEB, int SH, int DN, int IO>
+template <int RAWK, int DEB, int SH, int DN, int IO, bool EPI = false>
 R2L_BLOCKFN void r2l_static_chain_band(const R2LStaticChainArgs& ca, int bid, float* lds_f, double* acc) {
   const R2LStaticArgs& a = ca.s;
   const int NW = ca.nw;
@@ -475,7 +484,7 @@ R2L_BLOCKFN void r2l_static_chain_band(const R2LStaticChainArgs& ca, int bid, fl
     const int q = qb + K;                                                                                         \
     r2l_stream_convert_row<RAWK, LANES, RWT>(a, pf[K % PF], le, re, st.rw[(K + LA) % NR]);                           \
     if (BF || q + PF < q1) R2L_CHAIN_FETCH(q + LA + PF, pf[K % PF])                                               \
-    r2l_chain_step<DEB, SH, DN, K, IO>(a, st, q, y0, y1, le, re, NW, wave, lane, ex, fifo, outb, plane, x0, store_ok, acc); \
+    r2l_chain_step<DEB, SH, DN, K, IO, EPI>(a, st, q, y0, y1, le, re, NW, wave, lane, ex, fifo, outb, plane, x0, store_ok, acc, ca.ep); \
   }
     R2L_CHAIN_STEP(0)
     R2L_CHAIN_STEP(1)
@@ -492,7 +501,7 @@ R2L_BLOCKFN void r2l_static_chain_band(const R2LStaticChainArgs& ca, int bid, fl
 // bid + nblk, ... with its lanes' six sums running through all of them, and every wavefront stores ONE partial, double[6], at index
 // bid * nw + wave of the partials ca.s.out points to (r2l_static_stats: the workspace; r2l_sums_finish adds them up).  Between two
 // bands a barrier: the exchange area of the first steps of a band is the one the slower wavefronts may still be reading.
-template <int RAWK, int DEB, int SH, int DN, int IO = R2L_IO_F32>
+template <int RAWK, int DEB, int SH, int DN, int IO = R2L_IO_F32, bool EPI = false>
 R2L_BLOCKFN void r2l_static_chain_block(const R2LStaticChainArgs& ca, int bid, int nblk, float* lds_f) {
   if constexpr (IO == R2L_IO_STATS) {
     double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -505,7 +514,7 @@ R2L_BLOCKFN void r2l_static_chain_block(const R2LStaticChainArgs& ca, int bid, i
     r2l_stats_wave_partial(acc, tid & 63, (double*)ca.s.out + ((size_t)bid * ca.nw + (tid >> 6)) * 6);
   } else {
     (void)nblk;
-    r2l_static_chain_band<RAWK, DEB, SH, DN, IO>(ca, bid, lds_f, nullptr);
+    r2l_static_chain_band<RAWK, DEB, SH, DN, IO, EPI>(ca, bid, lds_f, nullptr);
   }
 }
 

@@ -24,6 +24,9 @@ struct R2LStaticStreamArgs {
   // fft_denoising works on the sharpened RGB image before clip and gamma: with lin_out the last pass stores that
   // image as float64 planes (B,3,H,W) instead of finishing
   double* lin_out;
+  // EPI instantiations (r2l_static_fwd_epilogue): where the output goes (R2LEpi, sc = +-1); behind everything else, so that the
+  // other instantiations read what they read
+  R2LEpi ep;
 };
 
 // raw values of columns x0-2 .. x0+5 of source row `ys` (symmetric extension at the image edges); with 16-bit
@@ -272,6 +275,41 @@ R2L_HD void r2l_stream_store_row(float* outb, size_t plane, size_t off, const fl
     if (ok) r2l_store_h4_nt((unsigned short*)outb + (size_t)k * plane + off, r2l_io_narrow4<IO>(st));
   }
 }
+// EPI instantiations (r2l_static_fwd_epilogue: the weak augmentation in the stores, R2LEpi with sc = +-1): pixel (y, x) goes to
+// element s0 + sr y + sc x of its plane.  The lane's 4 pixels of row y stay ONE store per channel: for sc = -1 the components are
+// reversed and the store is based at the image of x0 + 3 (W % 4 == 0: the same alignment).  `off` = r2l_epi_off: that base;
+// `rev` = sc < 0, a kernel argument and so the same for the whole wavefront.  Nontemporal like the stores they replace.
+R2L_HD size_t r2l_epi_off(const R2LEpi& ep, int y, int x0) {
+  const ptrdiff_t row = (ptrdiff_t)ep.s0 + (ptrdiff_t)ep.sr * y;  // wave-uniform
+  return (size_t)(ep.sc < 0 ? row - (x0 + 3) : row + x0);
+}
+template <int IO>
+R2L_HD void r2l_static_store_row_epi(float* outb, size_t plane, size_t off, bool rev, const float x[3][4], bool ok) {
+  R2L_PRAGMA_UNROLL
+  for (int k = 0; k < 3; ++k) {
+    const float x0 = x[k][0], x1 = x[k][1], x2 = x[k][2], x3 = x[k][3];
+    if constexpr (IO == R2L_IO_F32) {
+      r2l_f4 st;
+      st.x = rev ? x3 : x0;
+      st.y = rev ? x2 : x1;
+      st.z = rev ? x1 : x2;
+      st.w = rev ? x0 : x3;
+      if (ok) r2l_stream_store_f4(outb + (size_t)k * plane + off, st);
+    } else {
+      // narrowed in place, then the four 16-bit values reversed: the two words swapped, each with its halves swapped
+      r2l_f4 st;
+      st.x = x0;
+      st.y = x1;
+      st.z = x2;
+      st.w = x3;
+      r2l_h4 h = r2l_io_narrow4<IO>(st);
+      const unsigned lo = h.lo, hi = h.hi;
+      h.lo = rev ? ((hi >> 16) | (hi << 16)) : lo;
+      h.hi = rev ? ((lo >> 16) | (lo << 16)) : hi;
+      if (ok) r2l_store_h4_nt((unsigned short*)outb + (size_t)k * plane + off, h);
+    }
+  }
+}
 // IO = R2L_IO_STATS (r2l_static_stats): nothing is stored.  Where the other forms store the float32 values x[k][c] of a lane's 4
 // pixels -- under the same `ok` -- this one adds them and their squares to the lane's six float64 sums acc[k], acc[3 + k]; both
 // terms are exact in float64 (24-bit operands), so only the additions round: the row's 4 pixels pairwise, then one addition to the
@@ -310,9 +348,9 @@ R2L_HD void r2l_stats_wave_partial(const double* acc, int lane, double* part) {
   }
 }
 #endif
-template <int IO = R2L_IO_F32>
+template <int IO = R2L_IO_F32, bool EPI = false>
 R2L_HD void r2l_stream_finish_row(const R2LStaticArgs& a, const double d[4][3], float* outb, size_t plane,
-                                  size_t off, bool ok = true, double* acc = nullptr) {
+                                  size_t off, bool ok = true, double* acc = nullptr, bool rev = false) {
   float x[3][4];
   R2L_PRAGMA_UNROLL
   for (int c = 0; c < 4; ++c)
@@ -326,6 +364,11 @@ R2L_HD void r2l_stream_finish_row(const R2LStaticArgs& a, const double d[4][3], 
     return;
   }
   r2l_static_normalize<4>(a, x);
+  if constexpr (EPI) {  // (`off`: r2l_epi_off)
+    static_assert(IO != R2L_IO_STATS, "the statistics forms store nothing");
+    r2l_static_store_row_epi<IO>(outb, plane, off, rev, x, ok);
+    return;
+  }
   if constexpr (IO != R2L_IO_F32) {
     r2l_stream_store_row<IO>(outb, plane, off, x, ok);
     return;
@@ -564,9 +607,10 @@ R2L_HD void r2l_stream_malvar_rowT(const double* w0, const double* w1, const dou
 #define R2L_STREAM_PF_MALVAR 2
 #endif
 // one lane's work item: image b, column strip seg (256 columns), row band
-template <int DEB, int RAWK, bool LUMA, int IO = R2L_IO_F32>
+template <int DEB, int RAWK, bool LUMA, int IO = R2L_IO_F32, bool EPI = false>
 R2L_HD void r2l_static_stream_item(const R2LStaticStreamArgs& sa, int item, int lane, double* acc = nullptr) {
   static_assert(IO == R2L_IO_F32 || !LUMA, "the luma-plane passes store float32");
+  static_assert(!EPI || (!LUMA && IO != R2L_IO_STATS && RAWK != R2L_RAW_F64), "epilogue forms: the whole short chain, float32 / 16-bit frames");
   constexpr bool STATS = IO == R2L_IO_STATS;
   const R2LStaticArgs& a = sa.s;
   constexpr int HALO = DEB ? 2 : 1, NR = 2 * HALO + 1;
@@ -645,6 +689,8 @@ R2L_HD void r2l_static_stream_item(const R2LStaticStreamArgs& sa, int item, int 
           r2l_stream_lin_out_row(a, d, sa.luma_in + img, sa.lin_out + 3 * img, plane, (size_t)y * a.W + x0);
         else if (LUMA)
           r2l_stream_luma_in_row(a, d, sa.luma_in + img, outb, plane, (size_t)y * a.W + x0);
+        else if constexpr (EPI)
+          r2l_stream_finish_row<IO, true>(a, d, outb, plane, r2l_epi_off(sa.ep, y, x0), in_w, acc, sa.ep.sc < 0);
         else
           r2l_stream_finish_row<IO>(a, d, outb, plane, (size_t)y * a.W + x0, in_w, acc);
       }
@@ -665,7 +711,7 @@ R2L_HD void r2l_static_stream_item(const R2LStaticStreamArgs& sa, int item, int 
 #define R2L_STREAM_BF_PF_MALVAR 5
 #endif
 // (strip edges through scalar loads + lane shifts: measured slower, profiles/r04_ab_static_se.txt)
-template <int DEB, int RAWK, int IO = R2L_IO_F32>
+template <int DEB, int RAWK, int IO = R2L_IO_F32, bool EPI = false>
 R2L_HD void r2l_static_stream_item_bf(const R2LStaticStreamArgs& sa, int item, int lane, double* acc = nullptr) {
   const R2LStaticArgs& a = sa.s;
   constexpr int HALO = DEB ? 2 : 1, NR = 2 * HALO + 1;
@@ -744,7 +790,10 @@ R2L_HD void r2l_static_stream_item_bf(const R2LStaticStreamArgs& sa, int item, i
                                           win[(k + 4) % NR], d);
       }
       const int yc = y < y1 ? y : y1 - 1;  // (rows past the band's end: computed, not stored)
-      r2l_stream_finish_row<IO>(a, d, outb, plane, (size_t)yc * a.W + x0, in_w && y < y1, acc);
+      if constexpr (EPI)
+        r2l_stream_finish_row<IO, true>(a, d, outb, plane, r2l_epi_off(sa.ep, yc, x0), in_w && y < y1, acc, sa.ep.sc < 0);
+      else
+        r2l_stream_finish_row<IO>(a, d, outb, plane, (size_t)yc * a.W + x0, in_w && y < y1, acc);
     }
   }
 }
@@ -772,7 +821,7 @@ R2L_BLOCKFN void r2l_static_stream_stats_block(const R2LStaticStreamArgs& sa, in
   r2l_stats_wave_partial(acc, lane, (double*)sa.s.out + (size_t)(bid * WPB + wave) * 6);
 }
 #endif
-template <int DEB, int RAWK, bool LUMA, int IO = R2L_IO_F32>
+template <int DEB, int RAWK, bool LUMA, int IO = R2L_IO_F32, bool EPI = false>
 R2L_BLOCKFN void r2l_static_stream_block(const R2LStaticStreamArgs& sa, int bid, int nblk, float* lds) {
   (void)lds;
   (void)nblk;
@@ -789,10 +838,10 @@ R2L_BLOCKFN void r2l_static_stream_block(const R2LStaticStreamArgs& sa, int bid,
   if constexpr (!LUMA && RAWK != R2L_RAW_F64 && DEB == 1) {
     // (the wavefront index as a SCALAR: the work item and its rows must not look lane-dependent)
     const int witem = bid * (R2L_STREAM_NT / 64) + __builtin_amdgcn_readfirstlane(tid >> 6);
-    if (witem < sa.nitems) r2l_static_stream_item_bf<DEB, RAWK, IO>(sa, witem, tid & 63);
+    if (witem < sa.nitems) r2l_static_stream_item_bf<DEB, RAWK, IO, EPI>(sa, witem, tid & 63);
     return;
   }
 #endif
-  if (item < sa.nitems) r2l_static_stream_item<DEB, RAWK, LUMA, IO>(sa, item, tid & 63);
+  if (item < sa.nitems) r2l_static_stream_item<DEB, RAWK, LUMA, IO, EPI>(sa, item, tid & 63);
   R2L_PHASE_END
 }

@@ -629,8 +629,14 @@ def _check_static_names(debayer, sharpening, denoising):
 
 def static_pipeline(raw, camera_parameters, debayer='bilinear', sharpening='sharpening_filter',
                     denoising='gaussian_denoising', gamma=2.2, bits=16, mean_std=None, sharp_radius=1.0, sharp_amount=1.0,
-                    median_kernel_size=3, gaussian_sigma=0.5, fft_fraction=0.3, out_dtype=None):
+                    median_kernel_size=3, gaussian_sigma=0.5, fft_fraction=0.3, out_dtype=None, epilogue=None):
     """(B,H,W) raw on the GPU -> (B,3,H,W) float32, numpy semantics of the reference.
+
+    epilogue = (hflip, vflip, k) (opt-in; None or no move: the plain call): the result is
+    augmentation.flip_rot(plain_result, hflip, vflip, k) bit for bit, then ``.to(out_dtype)`` where a 16-bit type is set.  Where one
+    row-streaming kernel runs the chain and k is even (static_epilogue_why) that kernel stores every row at its flipped position --
+    one r2l_static_fwd_epilogue, no permutation pass; everywhere else (k odd, float64 frames, the plane-pass and tile routes) the
+    plain float32 call runs and flip_rot follows.
 
     out_dtype = torch.bfloat16 / torch.float16 (opt-in; None and torch.float32: a float32 result): the result is
     float32_result.to(out_dtype) bit for bit.  Where one row-streaming kernel runs the chain (r2l_static_io_supported:
@@ -684,13 +690,42 @@ def static_pipeline(raw, camera_parameters, debayer='bilinear', sharpening='shar
     io = IO_CODES[out_dtype]
     # a 16-bit output: written by the kernels where they have a 16-bit form of this call (NULL: served; otherwise the reason);
     # elsewhere the float32 call, narrowed by torch -- the same values
-    direct = io != IO_F32 and lib.r2l_static_io_supported(frames, H, W, *codes, ov) is None
+    # an output epilogue: stored by the kernel where ONE row-streaming kernel serves the call (k even); elsewhere the plain float32
+    # call, the permutation kernel behind it, and torch's cast behind that -- the same values
+    epi = epilogue_bits(epilogue)
+    fused = bool(epi) and lib.r2l_static_epilogue_supported(frames, H, W, *codes, ov, io, epi) is None
+    moved = bool(epi) and not fused
+    direct = io != IO_F32 and not moved and lib.r2l_static_io_supported(frames, H, W, *codes, ov) is None
     out = torch.empty((B, 3, H, W), dtype=out_dtype if direct else torch.float32, device=raw.device)
     nws = lib.r2l_static_workspace_bytes_opts(frames, B, H, W, *codes, ov)     # (a 5x5 median runs as plane passes)
     ws = torch.empty(nws, dtype=torch.uint8, device=raw.device) if nws else None      # 0: single-launch chains
+    if fused:
+        lib.check(lib.r2l_static_fwd_epilogue(ptr(raw), frames, float(denom or 1.0), ptr(out), io, B, H, W, cam, *codes,
+                                              float(gamma), ov, ms, ptr(ws), nws, stream, epi), 'r2l_static_fwd_epilogue')
+        return out
     lib.check(lib.r2l_static_fwd_io(ptr(raw), frames, float(denom or 1.0), ptr(out), io if direct else IO_F32, B, H, W, cam,
                                     *codes, float(gamma), ov, ms, ptr(ws), nws, stream), 'r2l_static_fwd_io')
+    if moved:
+        from .augmentation import flip_rot          # (augmentation imports this module)
+        out = flip_rot(out, *epilogue)
     return out if (direct or io == IO_F32) else out.to(out_dtype)
+
+
+def static_epilogue_why(raw, debayer='bilinear', sharpening='sharpening_filter', denoising='gaussian_denoising', epilogue=None,
+                        out_dtype=None, **options):
+    """why the static kernels do not store this call's output through the epilogue (hflip, vflip, k) themselves
+    (r2l_static_epilogue_supported, the predicate r2l_static_fwd_epilogue uses), or None where they do -- static_pipeline then
+    makes one launch instead of the plain call and the permutation kernel.  options: static_pipeline's numeric arguments."""
+    ov = _static_option_vector(options)
+    if raw.ndim != 3:
+        return 'needs dims (B, H, W)'
+    if out_dtype not in IO_CODES:
+        raise _lib.R2LError(f'output_dtype must be None, torch.float32, torch.bfloat16 or torch.float16, got {out_dtype!r}')
+    frames = 2 if raw.dtype == torch.float64 else (1 if raw.dtype in U16_DTYPES else 0)
+    lib, _ = _lib.library_for(raw)
+    why = lib.r2l_static_epilogue_supported(frames, raw.shape[1], raw.shape[2], _DEBAYER.get(debayer, -1), _SHARPEN.get(sharpening, 0),
+                                            _DENOISE.get(denoising, 0), ov, IO_CODES[out_dtype], epilogue_bits(epilogue))
+    return why.decode() if why is not None else None
 
 
 def static_io_why(raw, debayer='bilinear', sharpening='sharpening_filter', denoising='gaussian_denoising', **options):

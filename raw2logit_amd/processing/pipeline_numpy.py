@@ -81,10 +81,16 @@ class StaticProcessing(nn.Module):
     precision=16.  Where one row-streaming kernel runs the chain (functional.static_io_why: bilinear / Malvar2004, W % 4 == 0,
     W <= 2048, no fft_denoising, no 5x5 median, float64 frames on the short chain only) it stores the 16-bit values itself -- 6
     instead of 12 bytes per pixel, no cast pass; everywhere else the float32 kernels run and torch casts.  Anything but None or
-    those three dtypes raises R2LError."""
+    those three dtypes raises R2LError.
+
+    ``supports_output_epilogue`` -- this class pops the one-shot `_epilogue` an augmentation armed (ComposeState.arm): the next
+    call returns the flipped / rotated batch, ``flip_rot(plain_output, hflip, vflip, k)`` bit for bit.  Where one row-streaming
+    kernel runs the chain and k is even (functional.static_epilogue_why) that kernel stores the rows at their flipped positions;
+    everywhere else the plain call runs and the permutation kernel follows, right here."""
 
     raw_bits = 16
     output_dtype = None
+    supports_output_epilogue = True
 
     def __init__(self, camera_parameters, debayer='bilinear', sharpening='sharpening_filter',
                  denoising='gaussian_denoising', gamma=2.2, mean=None, std=None, **options):
@@ -109,6 +115,9 @@ class StaticProcessing(nn.Module):
     @torch.no_grad()
     def forward(self, raw):
         assert raw.ndim == 3, f"needs dims (B, H, W), got {raw.shape}"
+        # a one-shot output epilogue armed by the augmentation drop-in (ComposeState.arm); a call that raises before this pop
+        # leaves it for ComposeState.__call__ to apply
+        epilogue = self.__dict__.pop('_epilogue', None)
         self.stages = {}
         self.buffer = {}
         odt = self.output_dtype
@@ -116,6 +125,8 @@ class StaticProcessing(nn.Module):
             raise F_._lib.R2LError(f'output_dtype must be None, torch.float32, torch.bfloat16 or torch.float16, got {odt!r}')
         # (unset: exactly the call of a module without the attribute)
         io = dict(out_dtype=odt) if F_.IO_CODES[odt] != F_.IO_F32 else {}
+        if epilogue is not None and F_.epilogue_bits(epilogue):
+            io['epilogue'] = epilogue
         rgb = F_.static_pipeline(raw, self.camera_parameters, self.debayer, self.sharpening,
                                  self.denoising, self.gamma, bits=self.raw_bits, mean_std=self._mean_std_host(),
                                  **getattr(self, 'options', {}), **io)
