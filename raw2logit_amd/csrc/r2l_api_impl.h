@@ -4,770 +4,17 @@
 // tests/emul/r2l_emul.cpp (g++, R2L_EMUL: runs the same workgroup programs on host memory, for the
 // CPU-only test suite).
 #pragma once
-#include <stdlib.h>
-#include <string.h>
-
-#include <map>
-#include <mutex>
-#include <string>
-#include <utility>
-#include <vector>
-
-#include "r2l_simple_kernels.h"
-#include "r2l_param_stream.h"
-#include "r2l_param_plane_bwd.h"
-#include "r2l_static_kernels.h"
-#include "r2l_static_stream.h"
-#include "r2l_static_chain.h"
-#include "r2l_static_planes.h"
-#include "r2l_static_menon.h"
-#include "r2l_staged_kernels.h"
-#include "r2l_aux_kernels.h"
-#include "r2l_augment_strong.h"
-#include "r2l_corruptions.h"
-#include "r2l_sums_kernels.h"
-
-static thread_local std::string r2l_err;
-static int r2l_fail(int code, const std::string& msg) {
-  r2l_err = msg;
-  return code;
-}
-
-#ifdef R2L_LOCKSTEP
-// the lock-step emulation (tests/emul/r2l_lockstep_rt.h): NT host threads per workgroup, the workgroups one after the other; a
-// launch record (name -> count) stands in for the device build's event timing, so that tests can assert which kernels ran
-static std::mutex r2l_ls_record_mutex;
-static bool r2l_ls_record_on = false;
-static std::map<std::string, int> r2l_ls_record;
-static void r2l_ls_note(const char* name) {
-  std::lock_guard<std::mutex> g(r2l_ls_record_mutex);
-  if (r2l_ls_record_on) r2l_ls_record[std::string(name) + "_kernel"] += 1;
-}
-#define R2L_LS_KERNEL(name, ArgsT, NT_, LDSF, ...)                                                        \
-  static int name(const ArgsT& a, int grid, void* stream) {                                               \
-    (void)stream;                                                                                         \
-    r2l_ls_note(#name);                                                                                   \
-    r2l_ls::launch(#name, grid, (NT_), (size_t)(LDSF), &a,                                                \
-                   [&](int b_, float* lds_) { __VA_ARGS__(a, b_, grid, lds_); });                         \
-    return 0;                                                                                             \
-  }
-#define R2L_KERNEL_V(name, ArgsT, LDS_FLOATS, W, ...) R2L_LS_KERNEL(name, ArgsT, R2L_NT, LDS_FLOATS, __VA_ARGS__)
-#define R2L_KERNEL_OCC(name, ArgsT, blockfn, LDS_FLOATS, W) R2L_LS_KERNEL(name, ArgsT, R2L_NT, LDS_FLOATS, blockfn)
-#define R2L_KERNEL(name, ArgsT, blockfn, LDS_FLOATS) R2L_LS_KERNEL(name, ArgsT, R2L_NT, LDS_FLOATS, blockfn)
-#define R2L_KERNEL_NT(name, ArgsT, blockfn, NT, W) R2L_LS_KERNEL(name, ArgsT, NT, 0, blockfn)
-#define R2L_KERNEL_NT_LDS(name, ArgsT, NT, LDS_FLOATS, W, ...) R2L_LS_KERNEL(name, ArgsT, NT, LDS_FLOATS, __VA_ARGS__)
-#elif defined(R2L_EMUL)
-#define R2L_KERNEL_V(name, ArgsT, LDS_FLOATS, W, ...)                        \
-  static int name(const ArgsT& a, int grid, void* stream) {                  \
-    (void)stream;                                                            \
-    std::vector<float> buf((size_t)(LDS_FLOATS) + 8);                        \
-    float* lds = (float*)(((uintptr_t)buf.data() + 15) & ~(uintptr_t)15);    \
-    for (int b = 0; b < grid; ++b) __VA_ARGS__(a, b, grid, lds);             \
-    return 0;                                                                \
-  }
-#define R2L_KERNEL(name, ArgsT, blockfn, LDS_FLOATS) R2L_KERNEL_V(name, ArgsT, LDS_FLOATS, 1, blockfn)
-#define R2L_KERNEL_OCC(name, ArgsT, blockfn, LDS_FLOATS, W) R2L_KERNEL(name, ArgsT, blockfn, LDS_FLOATS)
-#define R2L_KERNEL_NT(name, ArgsT, blockfn, NT, W) R2L_KERNEL(name, ArgsT, blockfn, 4)
-#else
-// Optional per-kernel timing (bench.py's roofline leg): when enabled, every launch is bracketed by
-// hipEvents recorded on the stream the kernel is launched on; r2l_timing_report() synchronises the
-// events and returns "name count total_ms" lines.  Off by default; costs one branch per launch.
-#include <map>
-#include <mutex>
-struct R2LTimedLaunch {
-  const char* name;
-  hipEvent_t e0, e1;
-};
-static std::mutex r2l_timing_mutex;
-static bool r2l_timing_on = false;
-static std::vector<R2LTimedLaunch> r2l_timed;
-static void r2l_time_begin(const char* name, hipStream_t s, R2LTimedLaunch& t) {
-  t.name = name;
-  (void)hipEventCreate(&t.e0);
-  (void)hipEventCreate(&t.e1);
-  (void)hipEventRecord(t.e0, s);
-}
-static void r2l_time_end(hipStream_t s, R2LTimedLaunch& t) {
-  (void)hipEventRecord(t.e1, s);
-  std::lock_guard<std::mutex> g(r2l_timing_mutex);
-  r2l_timed.push_back(t);
-}
-// the host side of every launch wrapper `static int name(const ArgsT& a, int grid, void* stream)`: NT threads per workgroup,
-// LDS_BYTES of dynamic LDS
-#define R2L_LAUNCH(name, NT, LDS_BYTES)                                                                     \
-  {                                                                                                         \
-    R2LTimedLaunch t_;                                                                                      \
-    const bool timed_ = r2l_timing_on;                                                                      \
-    if (timed_) r2l_time_begin(#name "_kernel", (hipStream_t)stream, t_);                                   \
-    hipLaunchKernelGGL(name##_kernel, dim3(grid), dim3(NT), LDS_BYTES, (hipStream_t)stream, a);             \
-    if (timed_) r2l_time_end((hipStream_t)stream, t_);                                                      \
-    const hipError_t e = hipGetLastError();                                                                 \
-    if (e != hipSuccess) return r2l_fail(-10, std::string(#name ": ") + hipGetErrorString(e));              \
-    return 0;                                                                                               \
-  }
-// LDS-free kernels with their own workgroup size (independent wavefronts)
-#define R2L_KERNEL_NT(name, ArgsT, blockfn, NT, WAVES_PER_SIMD)                                 \
-  __global__ __launch_bounds__(NT, WAVES_PER_SIMD) void name##_kernel(const ArgsT a) {         \
-    blockfn(a, (int)blockIdx.x, (int)gridDim.x, nullptr);                                      \
-  }                                                                                            \
-  static int name(const ArgsT& a, int grid, void* stream) R2L_LAUNCH(name, NT, 0)
-// kernels with their own workgroup size AND static LDS
-#define R2L_KERNEL_NT_LDS(name, ArgsT, NT, LDS_FLOATS, WAVES_PER_SIMD, ...)                    \
-  __global__ __launch_bounds__(NT, WAVES_PER_SIMD) void name##_kernel(const ArgsT a) {         \
-    __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];                             \
-    __VA_ARGS__(a, (int)blockIdx.x, (int)gridDim.x, lds);                                      \
-  }                                                                                            \
-  static int name(const ArgsT& a, int grid, void* stream) R2L_LAUNCH(name, NT, 0)
-// ... of R2L_NT threads
-#define R2L_KERNEL_V(name, ArgsT, LDS_FLOATS, WAVES_PER_SIMD, ...) \
-  R2L_KERNEL_NT_LDS(name, ArgsT, R2L_NT, LDS_FLOATS, WAVES_PER_SIMD, __VA_ARGS__)
-#define R2L_KERNEL_OCC(name, ArgsT, blockfn, LDS_FLOATS, WAVES_PER_SIMD) \
-  R2L_KERNEL_NT_LDS(name, ArgsT, R2L_NT, LDS_FLOATS, WAVES_PER_SIMD, blockfn)
-#define R2L_KERNEL(name, ArgsT, blockfn, LDS_FLOATS) R2L_KERNEL_OCC(name, ArgsT, blockfn, LDS_FLOATS, 1)
-#endif
-
-// the serial emulation compiles the tile forms of the kernels only (r2l_common.h): no row-streaming forward, no plane passes
-#ifdef R2L_SERIAL
-#define R2L_PLANE_PASSES 0
-#else
-#define R2L_PLANE_PASSES 1
-#endif
-
-typedef R2LGeom<64, 64> GFwd;
-typedef R2LGeom<64, 64> GBwd1;
-typedef R2LGeom<64, 64> GBwd2;
-
-#define R2L_LDS3(G) (R2L_FOLDED_FLOATS + 2 * G::PAD + 3 * G::PLANE)
-#define R2L_LDS4(G) (R2L_FOLDED_FLOATS + 2 * G::PAD + 4 * G::PLANE)
-static_assert(R2L_LDS3(GFwd) >= R2L_RED_FLOATS, "reduction scratch must fit");
-static_assert(R2L_LDS3(GBwd2) >= R2L_RED_FLOATS, "reduction scratch must fit");
-
-R2L_KERNEL(r2l_launch_fold, R2LFoldArgs, r2l_fold_block, 4)
-R2L_KERNEL(r2l_launch_unfold, R2LUnfoldArgs, r2l_unfold_block, 4 + 2 * R2L_NSUMS + 2 * R2L_UNFOLD_TG + R2L_P_COUNT + 4)
-R2L_KERNEL(r2l_launch_bn_finalize, R2LBnFinalizeArgs, r2l_bn_finalize_block, 4)
-R2L_KERNEL(r2l_launch_bn_bwd_means, R2LBnBwdMeansArgs, r2l_bn_bwd_means_block, 4)
-R2L_KERNEL(r2l_launch_reduce_rows, R2LReduceRowsArgs, r2l_reduce_rows_block, 2 * R2L_NT + 64)
-#ifndef R2L_OCC_FWD
-#define R2L_OCC_FWD 4
-#endif
-#ifndef R2L_OCC_BWD1
-#define R2L_OCC_BWD1 2
-#endif
-#ifndef R2L_OCC_BWD2
-#define R2L_OCC_BWD2 4
-#endif
-// hot instantiation (frames that tile exactly, no additive layer) + the general ones; each again for 16-bit
-// container frames (compile-time, so that the float32 kernels carry no decode code)
-R2L_KERNEL_V(r2l_launch_fwd, R2LFwdArgs, R2L_LDS3(GFwd), R2L_OCC_FWD, r2l_fwd_block<GFwd, false, false, false>)
-R2L_KERNEL_V(r2l_launch_fwd_ragged, R2LFwdArgs, R2L_LDS3(GFwd), 2, r2l_fwd_block<GFwd, false, true, false>)
-// the additive layer on frames that tile exactly -- the reference's only case: its layer is 256 x 256 (pipeline_torch.py:130)
-R2L_KERNEL_V(r2l_launch_fwd_add_exact, R2LFwdArgs, R2L_LDS3(GFwd), R2L_OCC_FWD, r2l_fwd_block<GFwd, true, false, false>)
-#ifndef R2L_SERIAL
-// the forward as a row-streaming kernel (r2l_param_stream.h): NW wavefronts side by side cover 256 * NW columns
-#ifndef R2L_FS_OCC
-#define R2L_FS_OCC 3
-#endif
-#ifndef R2L_FS_MINBAND
-#define R2L_FS_MINBAND 16  // rows: shortest band of the row-streaming forward (7 halo rows of luma per band)
-#endif
-// (8 wavefronts side by side -- frames 1024 < W <= 2048 -- need 99 KB of LDS: one workgroup per CU, 2 wavefronts per SIMD)
-#define R2L_FS_OCC_NW(NW) ((NW) == 8 ? 2 : R2L_FS_OCC)
-// One spelling per family.  R2L_FS_KERNELS(pre, sfx, EPI, SONLY, IO) emits the eight kernels r2l_launch_fwd_stream<pre>_w{1,2,4,8}[_u16]<sfx>,
-// R2L_FS_ROW(pre, sfx) their row of r2l_fwd_stream_table: [16-bit container frames][wavefronts per row: 1, 2, 4, 8]
-#define R2L_FS_KERNEL(pre, NW, u16, sfx, ...)                                                                              \
-  R2L_KERNEL_NT_LDS(r2l_launch_fwd_stream##pre##_w##NW##u16##sfx, R2LFwdStreamArgs, (NW) * 64, R2L_FS_LDS_FLOATS(NW),     \
-                    R2L_FS_OCC_NW(NW), r2l_fwd_stream_block<NW, __VA_ARGS__>)
-#define R2L_FS_KERNELS(pre, sfx, ...)                  \
-  R2L_FS_KERNEL(pre, 1, , sfx, false, __VA_ARGS__)     \
-  R2L_FS_KERNEL(pre, 2, , sfx, false, __VA_ARGS__)     \
-  R2L_FS_KERNEL(pre, 4, , sfx, false, __VA_ARGS__)     \
-  R2L_FS_KERNEL(pre, 8, , sfx, false, __VA_ARGS__)     \
-  R2L_FS_KERNEL(pre, 1, _u16, sfx, true, __VA_ARGS__)  \
-  R2L_FS_KERNEL(pre, 2, _u16, sfx, true, __VA_ARGS__)  \
-  R2L_FS_KERNEL(pre, 4, _u16, sfx, true, __VA_ARGS__)  \
-  R2L_FS_KERNEL(pre, 8, _u16, sfx, true, __VA_ARGS__)
-#define R2L_FS_ROW(pre, sfx)                                                                                            \
-  {{r2l_launch_fwd_stream##pre##_w1##sfx, r2l_launch_fwd_stream##pre##_w2##sfx, r2l_launch_fwd_stream##pre##_w4##sfx,    \
-    r2l_launch_fwd_stream##pre##_w8##sfx},                                                                              \
-   {r2l_launch_fwd_stream##pre##_w1_u16##sfx, r2l_launch_fwd_stream##pre##_w2_u16##sfx,                                 \
-    r2l_launch_fwd_stream##pre##_w4_u16##sfx, r2l_launch_fwd_stream##pre##_w8_u16##sfx}}
-R2L_FS_KERNELS(, , false, false, R2L_IO_F32)
-// ... the statistics pass of train-mode BatchNorm (no output; keeps Y' when asked): its own instantiation
-R2L_FS_KERNELS(_stats, , false, true, R2L_IO_F32)
-// ... with the output epilogue (flip / flip / rot90 of the output planes as part of the stores, R2LEpi)
-R2L_FS_KERNELS(_epi, , true, false, R2L_IO_F32)
-// ... writing the output as bfloat16 / float16 (r2l_isp_step_fwd_io: R2L_IO_*; no epilogue)
-R2L_FS_KERNELS(, _bf16, false, false, R2L_IO_BF16)
-R2L_FS_KERNELS(, _f16, false, false, R2L_IO_F16)
-// ... writing it channels-last (r2l_isp_step_fwd_layout: R2L_LAYOUT_NHWC; float32 and 16 bits, no epilogue)
-R2L_FS_KERNELS(, _nhwc, false, false, R2L_IO_F32 | R2L_IO_NHWC)
-R2L_FS_KERNELS(, _bf16_nhwc, false, false, R2L_IO_BF16 | R2L_IO_NHWC)
-R2L_FS_KERNELS(, _f16_nhwc, false, false, R2L_IO_F16 | R2L_IO_NHWC)
-// The implementations' `io` = element type (R2L_IO_*) | R2L_IO_NHWC for a channels-last tensor (r2l_common.h).  Every value but
-// R2L_IO_F32 takes the routes a 16-bit call takes; its rows in their launch tables (r2l_io_check has seen the value):
-#define R2L_IO_SLOTS 5
-static int r2l_io_slot(int io) { return (io & R2L_IO_NHWC) ? 2 + R2L_IO_ELEM(io) : io - 1; }
-typedef int (*r2l_fwd_stream_launch_t)(const R2LFwdStreamArgs&, int, void*);
-enum { R2L_FS_PLAIN, R2L_FS_STATS, R2L_FS_EPI, R2L_FS_IO /* + r2l_io_slot */ };
-static const r2l_fwd_stream_launch_t r2l_fwd_stream_table[R2L_FS_IO + R2L_IO_SLOTS][2][4] = {
-    R2L_FS_ROW(, ),      R2L_FS_ROW(_stats, ), R2L_FS_ROW(_epi, ),      R2L_FS_ROW(, _bf16),
-    R2L_FS_ROW(, _f16),  R2L_FS_ROW(, _nhwc),  R2L_FS_ROW(, _bf16_nhwc), R2L_FS_ROW(, _f16_nhwc)};
-// A family of [_u16] pairs -- plain, with the output epilogue (<pre> = _epi), one per io slot (<sfx>): the kernels base<pre>[_u16]<sfx>
-// and their row of a launch table, [16-bit container frames]
-#define R2L_PAIR_KERNELS(KERNEL, base, pre, sfx, ...) \
-  KERNEL(base##pre##sfx, false, __VA_ARGS__)          \
-  KERNEL(base##pre##_u16##sfx, true, __VA_ARGS__)
-#define R2L_PAIR_ROW(base, pre, sfx) {base##pre##sfx, base##pre##_u16##sfx}
-#define R2L_PAIR_FAMILY(KERNEL, base)                                             \
-  R2L_PAIR_KERNELS(KERNEL, base, , , false, R2L_IO_F32)                           \
-  R2L_PAIR_KERNELS(KERNEL, base, _epi, , true, R2L_IO_F32)                        \
-  R2L_PAIR_KERNELS(KERNEL, base, , _bf16, false, R2L_IO_BF16)                     \
-  R2L_PAIR_KERNELS(KERNEL, base, , _f16, false, R2L_IO_F16)                       \
-  R2L_PAIR_KERNELS(KERNEL, base, , _nhwc, false, R2L_IO_F32 | R2L_IO_NHWC)        \
-  R2L_PAIR_KERNELS(KERNEL, base, , _bf16_nhwc, false, R2L_IO_BF16 | R2L_IO_NHWC)  \
-  R2L_PAIR_KERNELS(KERNEL, base, , _f16_nhwc, false, R2L_IO_F16 | R2L_IO_NHWC)
-#define R2L_PAIR_TABLE(base)                                                                                             \
-  {R2L_PAIR_ROW(base, , ),      R2L_PAIR_ROW(base, _epi, ),       R2L_PAIR_ROW(base, , _bf16),     R2L_PAIR_ROW(base, , _f16), \
-   R2L_PAIR_ROW(base, , _nhwc), R2L_PAIR_ROW(base, , _bf16_nhwc), R2L_PAIR_ROW(base, , _f16_nhwc)}
-enum { R2L_PAIR_PLAIN, R2L_PAIR_EPI, R2L_PAIR_IO /* + r2l_io_slot */ };
-// the apply pass of train-mode BatchNorm on the Y' plane the statistics pass kept: independent wavefronts, no LDS
-#ifndef R2L_FA_OCC
-#define R2L_FA_OCC 3
-#endif
-#ifndef R2L_FA_NWV
-#define R2L_FA_NWV 4  // wavefronts (= work items) per workgroup of the apply and luma passes
-#endif
-#define R2L_FA_KERNEL(name, U16, EPI, IO) \
-  R2L_KERNEL_NT_LDS(name, R2LFwdStreamArgs, 64 * R2L_FA_NWV, 4, R2L_FA_OCC, r2l_fwd_apply_block<U16, EPI, false, R2L_FA_NWV, IO>)
-R2L_PAIR_FAMILY(R2L_FA_KERNEL, r2l_launch_fwd_apply)
-static const r2l_fwd_stream_launch_t r2l_fwd_apply_table[R2L_PAIR_IO + R2L_IO_SLOTS][2] = R2L_PAIR_TABLE(r2l_launch_fwd_apply);
-// ... the same walk without output: the BatchNorm statistics from the kept plane (2 wavefronts per workgroup, each with
-// its own work items; <= R2L_MAX_BLOCKS workgroups = partials of the reduction tree)
-#define R2L_FA_STATS_NWV 4
-#ifndef R2L_FA_STATS_OCC
-#define R2L_FA_STATS_OCC 3
-#endif
-R2L_KERNEL_NT_LDS(r2l_launch_fwd_stats, R2LFwdStreamArgs, 64 * R2L_FA_STATS_NWV, R2L_FA_LDS_FLOATS(R2L_FA_STATS_NWV, true),
-                  R2L_FA_STATS_OCC, r2l_fwd_apply_block<false, false, true, R2L_FA_STATS_NWV>)
-R2L_KERNEL_NT_LDS(r2l_launch_fwd_stats_u16, R2LFwdStreamArgs, 64 * R2L_FA_STATS_NWV,
-                  R2L_FA_LDS_FLOATS(R2L_FA_STATS_NWV, true), R2L_FA_STATS_OCC,
-                  r2l_fwd_apply_block<true, false, true, R2L_FA_STATS_NWV>)
-// the luma pass in front of them: raw -> Y' (independent wavefronts, no LDS)
-#ifndef R2L_FL_OCC
-#define R2L_FL_OCC 4
-#endif
-R2L_KERNEL_NT_LDS(r2l_launch_fwd_luma, R2LFwdStreamArgs, 64 * R2L_FA_NWV, 4, R2L_FL_OCC, r2l_fwd_luma_block<false, R2L_FA_NWV>)
-R2L_KERNEL_NT_LDS(r2l_launch_fwd_luma_u16, R2LFwdStreamArgs, 64 * R2L_FA_NWV, 4, R2L_FL_OCC, r2l_fwd_luma_block<true, R2L_FA_NWV>)
-#endif
-R2L_KERNEL_V(r2l_launch_bwd1, R2LBwd1Args, R2L_LDS3(GBwd1), R2L_OCC_BWD1, r2l_bwd1_block<GBwd1, false, false, false>)
-R2L_KERNEL_V(r2l_launch_bwd1_ragged, R2LBwd1Args, R2L_LDS3(GBwd1), 2, r2l_bwd1_block<GBwd1, false, true, false>)
-// ... with Y' taken from the plane the streaming forward kept (one workgroup per CU: the second prefetch frame
-// takes the kernel past 256 VGPRs)
-#ifndef R2L_OCC_BWD1S
-#define R2L_OCC_BWD1S 1
-#endif
-R2L_KERNEL_V(r2l_launch_bwd1_saved, R2LBwd1Args, R2L_LDS3(GBwd1) + GBwd1::PAD + R2L_B1_FRAME_FLOATS, R2L_OCC_BWD1S, r2l_bwd1_block<GBwd1, false, false, false, true>)
-R2L_KERNEL_V(r2l_launch_bwd1_saved_u16, R2LBwd1Args, R2L_LDS3(GBwd1) + GBwd1::PAD + R2L_B1_FRAME_FLOATS, R2L_OCC_BWD1S, r2l_bwd1_block<GBwd1, false, false, true, true>)
-// (frames that do not tile by 64 below 4 Mi px take r2l_launch_bwd1_ragged -- Y' recomputed in LDS -- also when the forward kept
-// Y': the kept-plane form of the general instantiation needed 76 B of scratch per lane, round 6)
-R2L_KERNEL_V(r2l_launch_bwd1_add_exact, R2LBwd1Args, R2L_LDS3(GBwd1), 2, r2l_bwd1_block<GBwd1, true, false, false>)
-#ifndef R2L_SERIAL
-// kernel B1 as two passes over planes (r2l_param_plane_bwd.h): where the forward kept Y' and no epilogue / additive layer
-R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane, R2LBwd1Args, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2, r2l_bwd1_plane_block<false, false>)
-R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane_u16, R2LBwd1Args, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2, r2l_bwd1_plane_block<true, false>)
-R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane_epi, R2LBwd1Args, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2, r2l_bwd1_plane_block<false, true>)
-R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane_epi_u16, R2LBwd1Args, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2, r2l_bwd1_plane_block<true, true>)
-// ... storing the chroma gradient planes gU, gV as well, for the d/d raw pass (float32 frames, no epilogue)
-struct R2LBwd1GuvArgs {
-  R2LBwd1Args b;
-  float* guv;  // gU (B,H,W), then gV (B,H,W)
-};
-R2L_BLOCKFN void r2l_bwd1_plane_guv_block(const R2LBwd1GuvArgs& a, int bid, int nblk, float* lds) {
-  r2l_bwd1_plane_block<false, false, true>(a.b, bid, nblk, lds, a.guv);
-}
-R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane_guv, R2LBwd1GuvArgs, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2, r2l_bwd1_plane_guv_block)
-// ... reading grad_out as bfloat16 / float16 (r2l_isp_step_bwd_io: the full route, no epilogue)
-template <int IO>
-R2L_BLOCKFN void r2l_bwd1_plane_guv_io_block(const R2LBwd1GuvArgs& a, int bid, int nblk, float* lds) {
-  r2l_bwd1_plane_block<false, false, true, R2L_BPS_FULL, R2L_BPS_PF, IO>(a.b, bid, nblk, lds, a.guv);
-}
-// (16-bit container frames and the gU / gV stores: ONE row of raw / Y' in flight like the reduced routes (R2L_BPS_PF, 10 registers
-// less) -- with two, hipcc took 214 and 226 registers where the float32 siblings take 208 and 222, whatever the place of the
-// widening; the cotangent these forms wait for is half as many bytes.  profiles/half_io_resources.txt)
-#define R2L_BP_KERNELS_IO(sfx, IO)                                                                          \
-  R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane##sfx, R2LBwd1Args, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2,               \
-                    r2l_bwd1_plane_block<false, false, false, R2L_BPS_FULL, R2L_BP_PF, IO>)                 \
-  R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane_u16##sfx, R2LBwd1Args, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2,           \
-                    r2l_bwd1_plane_block<true, false, false, R2L_BPS_FULL, R2L_BPS_PF, IO>)                 \
-  R2L_KERNEL_NT_LDS(r2l_launch_bwd1_plane_guv##sfx, R2LBwd1GuvArgs, R2L_BP_NT, R2L_BP_LDS_FLOATS, 2,        \
-                    r2l_bwd1_plane_guv_io_block<IO>)
-R2L_BP_KERNELS_IO(_bf16, R2L_IO_BF16)
-R2L_BP_KERNELS_IO(_f16, R2L_IO_F16)
-R2L_BP_KERNELS_IO(_nhwc, R2L_IO_F32 | R2L_IO_NHWC)
-R2L_BP_KERNELS_IO(_bf16_nhwc, R2L_IO_BF16 | R2L_IO_NHWC)
-R2L_BP_KERNELS_IO(_f16_nhwc, R2L_IO_F16 | R2L_IO_NHWC)
-R2L_KERNEL_NT_LDS(r2l_launch_bwd1_blur, R2LBwd1Args, R2L_BP_NT, R2L_BP_RED_FLOATS, 3, r2l_bwd1_blur_block)
-R2L_KERNEL_NT_LDS(r2l_launch_bwd1_blur_hp, R2LBwd1Args, R2L_BP_NT, R2L_BP_RED_FLOATS, R2L_HB_OCC, r2l_bwd1_blur_hp_block)
-// the reduced forms r2l_isp_step_bwd_select routes to (R2L_BPS_*: what each keeps).  Without the 38 stencil accumulator pairs
-// and with one row of raw / Y' in flight instead of two the pass fits three wavefronts per SIMD (133 .. 164 VGPRs, no scratch)
-// -- except the pure map with the gU / gV stores: hipcc keeps ~250 folded weights live in scalar registers there and spills
-// them into vector lanes (3 VGPRs over at one row in flight, 17 at two), so that one stays at two wavefronts (184 VGPRs)
-#define R2L_BPS_OCC 3
-#define R2L_BPS_OCC_RAW 2
-struct R2LBwd1SelArgs {
-  R2LBwd1Args b;
-  float* guv;  // gU, gV planes (the GUV forms), else null
-  R2LBpSelect s;
-};
-template <bool U16, bool EPI, bool GUV, int SEL, int PF = R2L_BPS_PF>
-R2L_BLOCKFN void r2l_bwd1_sel_block(const R2LBwd1SelArgs& a, int bid, int nblk, float* lds) {
-  r2l_bwd1_plane_block<U16, EPI, GUV, SEL, PF>(a.b, bid, nblk, lds, a.guv, &a.s);
-}
-R2L_BLOCKFN void r2l_bwd1_blur_fin_block(const R2LBwd1SelArgs& a, int bid, int nblk, float* lds) {
-  r2l_bwd1_blur_block<true>(a.b, bid, nblk, lds, &a.s);
-}
-R2L_BLOCKFN void r2l_bwd1_blur_hp_fin_block(const R2LBwd1SelArgs& a, int bid, int nblk, float* lds) {
-  r2l_bwd1_blur_hp_block<true>(a.b, bid, nblk, lds, &a.s);
-}
-// d/d raw alone: a pure map raw + Y' + grad_out -> dL/dY'', gU, gV (no accumulator, no LDS, no tail); ... with the gamma sum
-R2L_KERNEL_NT_LDS(r2l_launch_bwd1_sel_raw, R2LBwd1SelArgs, R2L_BP_NT, 4, R2L_BPS_OCC_RAW,
-                  r2l_bwd1_sel_block<false, false, true, R2L_BPS_GYPP, R2L_BP_PF>)
-R2L_KERNEL_NT_LDS(r2l_launch_bwd1_sel_raw_gamma, R2LBwd1SelArgs, R2L_BP_NT, R2L_BPS_LDS_FLOATS, R2L_BPS_OCC,
-                  r2l_bwd1_sel_block<false, false, true, R2L_BPS_GYPP | R2L_BPS_GAMMA>)
-// gamma alone (no plane written); dL/dY'' for the blur pass; both -- float32 / 16-bit frames, with / without the output epilogue
-#define R2L_BPS_KERNELS(name, LDSF, SEL)                                                                                       \
-  R2L_KERNEL_NT_LDS(name, R2LBwd1SelArgs, R2L_BP_NT, LDSF, R2L_BPS_OCC, r2l_bwd1_sel_block<false, false, false, SEL>)         \
-  R2L_KERNEL_NT_LDS(name##_u16, R2LBwd1SelArgs, R2L_BP_NT, LDSF, R2L_BPS_OCC, r2l_bwd1_sel_block<true, false, false, SEL>)    \
-  R2L_KERNEL_NT_LDS(name##_epi, R2LBwd1SelArgs, R2L_BP_NT, LDSF, R2L_BPS_OCC, r2l_bwd1_sel_block<false, true, false, SEL>)    \
-  R2L_KERNEL_NT_LDS(name##_epi_u16, R2LBwd1SelArgs, R2L_BP_NT, LDSF, R2L_BPS_OCC, r2l_bwd1_sel_block<true, true, false, SEL>)
-R2L_BPS_KERNELS(r2l_launch_bwd1_sel_gamma, R2L_BPS_LDS_FLOATS, R2L_BPS_GAMMA)
-R2L_BPS_KERNELS(r2l_launch_bwd1_sel_gypp, 4, R2L_BPS_GYPP)
-R2L_BPS_KERNELS(r2l_launch_bwd1_sel_gypp_gamma, R2L_BPS_LDS_FLOATS, R2L_BPS_GYPP | R2L_BPS_GAMMA)
-// the blur passes whose last workgroup finishes the 25 sums into the blur gradient
-R2L_KERNEL_NT_LDS(r2l_launch_bwd1_blur_fin, R2LBwd1SelArgs, R2L_BP_NT, R2L_BP_RED_FLOATS, 3, r2l_bwd1_blur_fin_block)
-R2L_KERNEL_NT_LDS(r2l_launch_bwd1_blur_hp_fin, R2LBwd1SelArgs, R2L_BP_NT, R2L_BP_RED_FLOATS, R2L_HB_OCC, r2l_bwd1_blur_hp_fin_block)
-// kernel B2 likewise: the blur's adjoint into a plane, then the sums + the final reduction and unfold
-R2L_KERNEL_NT_LDS(r2l_launch_bwd2_hp, R2LBwd2Args, R2L_BP_NT, 4, 4, r2l_bwd2_hp_block)
-R2L_KERNEL_NT_LDS(r2l_launch_bwd2_sums, R2LBwd2Args, R2L_B2S_NT, R2L_B2S_LDS_FLOATS, 3, r2l_bwd2_sums_block<false>)
-R2L_KERNEL_NT_LDS(r2l_launch_bwd2_sums_u16, R2LBwd2Args, R2L_B2S_NT, R2L_B2S_LDS_FLOATS, 3, r2l_bwd2_sums_block<true>)
-// d/d raw: HP + gU + gV -> grad_raw (independent wavefronts, no LDS)
-#ifndef R2L_BR_OCC
-#define R2L_BR_OCC 3
-#endif
-R2L_KERNEL_NT_LDS(r2l_launch_bwd_raw_plane, R2LRawGradArgs, 64 * R2L_BR_NWV, 4, R2L_BR_OCC, r2l_bwd_raw_plane_block)
-// BatchNorm's backward sums from the raw frame, Y' and grad_out (xhat recomputed, the output not read back): r2l_bnr_planes_block
-#ifndef R2L_BNR_OCC
-#define R2L_BNR_OCC 3
-#endif
-#define R2L_BNR_NWV 4
-#define R2L_BNR_KERNEL(name, U16, EPI, IO)                                                                      \
-  R2L_KERNEL_NT_LDS(name, R2LBnrArgs, 64 * R2L_BNR_NWV, R2L_FA_LDS_FLOATS(R2L_BNR_NWV, true), R2L_BNR_OCC,      \
-                    r2l_bnr_planes_block<U16, EPI, R2L_BNR_NWV, IO>)
-R2L_PAIR_FAMILY(R2L_BNR_KERNEL, r2l_launch_bnr_planes)
-typedef int (*r2l_bnr_launch_t)(const R2LBnrArgs&, int, void*);
-static const r2l_bnr_launch_t r2l_bnr_table[R2L_PAIR_IO + R2L_IO_SLOTS][2] = R2L_PAIR_TABLE(r2l_launch_bnr_planes);
-#endif
-R2L_KERNEL_V(r2l_launch_bwd2, R2LBwd2Args, R2L_LDS3(GBwd2), R2L_OCC_BWD2, r2l_bwd2_block<GBwd2, false>)
-R2L_KERNEL_V(r2l_launch_fwd_u16, R2LFwdArgs, R2L_LDS3(GFwd), R2L_OCC_FWD, r2l_fwd_block<GFwd, false, false, true>)
-R2L_KERNEL_V(r2l_launch_fwd_ragged_u16, R2LFwdArgs, R2L_LDS3(GFwd), 2, r2l_fwd_block<GFwd, false, true, true>)
-R2L_KERNEL_V(r2l_launch_fwd_add_exact_u16, R2LFwdArgs, R2L_LDS3(GFwd), R2L_OCC_FWD, r2l_fwd_block<GFwd, true, false, true>)
-R2L_KERNEL_V(r2l_launch_bwd1_u16, R2LBwd1Args, R2L_LDS3(GBwd1), R2L_OCC_BWD1, r2l_bwd1_block<GBwd1, false, false, true>)
-R2L_KERNEL_V(r2l_launch_bwd1_ragged_u16, R2LBwd1Args, R2L_LDS3(GBwd1), 2, r2l_bwd1_block<GBwd1, false, true, true>)
-R2L_KERNEL_V(r2l_launch_bwd1_add_exact_u16, R2LBwd1Args, R2L_LDS3(GBwd1), 2, r2l_bwd1_block<GBwd1, true, false, true>)
-R2L_KERNEL_V(r2l_launch_bwd2_u16, R2LBwd2Args, R2L_LDS3(GBwd2), R2L_OCC_BWD2, r2l_bwd2_block<GBwd2, true>)
-// 14 KB of LDS instead of 68 KB: 8 workgroups' worth of loads in flight per CU instead of 2
-R2L_KERNEL_OCC(r2l_launch_bn_reduce, R2LBnReduceArgs, r2l_bn_reduce_block, R2L_RED_FLOATS_N(6), 8)
-R2L_KERNEL(r2l_launch_add_bwd, R2LAddBwdArgs, r2l_add_bwd_block, 4)
-R2L_KERNEL(r2l_launch_raw2rgb_fwd, R2LRaw2RgbArgs, r2l_raw2rgb_fwd_block, 4)
-R2L_KERNEL(r2l_launch_raw2rgb_bwd, R2LRaw2RgbArgs, r2l_raw2rgb_bwd_block, R2L_RED_FLOATS)
-R2L_KERNEL(r2l_launch_static_full, R2LStaticArgs, r2l_static_block<GStatic>, R2L_STATIC_LDS_FLOATS)
-// 3 wavefronts per SIMD with 5 rows in flight each beat 4 with 3 by 1 % (same-buffer A/B): the depth is what counts
-#ifndef R2L_STREAM_OCC_BILINEAR
-#define R2L_STREAM_OCC_BILINEAR 3
-#endif
-#ifndef R2L_STREAM_OCC_MALVAR
-#define R2L_STREAM_OCC_MALVAR 3
-#endif
-#define R2L_STREAM_KERNEL(name, DEB, RAWK, LUMA, OCC)                                                    \
-  R2L_BLOCKFN void name##_block(const R2LStaticStreamArgs& sa, int bid, int nblk, float* lds) {          \
-    r2l_static_stream_block<DEB, RAWK, LUMA>(sa, bid, nblk, lds);                                        \
-  }                                                                                                      \
-  R2L_KERNEL_NT(name, R2LStaticStreamArgs, name##_block, R2L_STREAM_NT, OCC)
-// demosaic x frame container (float32 | 16-bit | float64) x {whole short chain, luma-plane passes}
-R2L_STREAM_KERNEL(r2l_launch_static_stream_bilinear, 0, R2L_RAW_F32, false, R2L_STREAM_OCC_BILINEAR)
-R2L_STREAM_KERNEL(r2l_launch_static_stream_malvar, 1, R2L_RAW_F32, false, R2L_STREAM_OCC_MALVAR)
-R2L_STREAM_KERNEL(r2l_launch_static_stream_bilinear_u16, 0, R2L_RAW_U16, false, R2L_STREAM_OCC_BILINEAR)
-R2L_STREAM_KERNEL(r2l_launch_static_stream_malvar_u16, 1, R2L_RAW_U16, false, R2L_STREAM_OCC_MALVAR)
-R2L_STREAM_KERNEL(r2l_launch_static_stream_bilinear_f64, 0, R2L_RAW_F64, false, 3)
-R2L_STREAM_KERNEL(r2l_launch_static_stream_malvar_f64, 1, R2L_RAW_F64, false, 2)
-R2L_STREAM_KERNEL(r2l_launch_static_luma_bilinear, 0, R2L_RAW_F32, true, R2L_STREAM_OCC_BILINEAR)
-R2L_STREAM_KERNEL(r2l_launch_static_luma_malvar, 1, R2L_RAW_F32, true, R2L_STREAM_OCC_MALVAR)
-R2L_STREAM_KERNEL(r2l_launch_static_luma_bilinear_u16, 0, R2L_RAW_U16, true, R2L_STREAM_OCC_BILINEAR)
-R2L_STREAM_KERNEL(r2l_launch_static_luma_malvar_u16, 1, R2L_RAW_U16, true, R2L_STREAM_OCC_MALVAR)
-R2L_STREAM_KERNEL(r2l_launch_static_luma_bilinear_f64, 0, R2L_RAW_F64, true, 3)
-R2L_STREAM_KERNEL(r2l_launch_static_luma_malvar_f64, 1, R2L_RAW_F64, true, 2)
-#ifndef R2L_SERIAL
-// ... the whole short chain writing bfloat16 / float16 (r2l_static_fwd_io: R2L_IO_*), at their float32 siblings' occupancy
-#define R2L_STREAM_KERNEL_IO(name, DEB, RAWK, IO, OCC)                                                   \
-  R2L_BLOCKFN void name##_block(const R2LStaticStreamArgs& sa, int bid, int nblk, float* lds) {          \
-    r2l_static_stream_block<DEB, RAWK, false, IO>(sa, bid, nblk, lds);                                   \
-  }                                                                                                      \
-  R2L_KERNEL_NT(name, R2LStaticStreamArgs, name##_block, R2L_STREAM_NT, OCC)
-#define R2L_STREAM_KERNELS_IO(sfx, IO)                                                                              \
-  R2L_STREAM_KERNEL_IO(r2l_launch_static_stream_bilinear##sfx, 0, R2L_RAW_F32, IO, R2L_STREAM_OCC_BILINEAR)         \
-  R2L_STREAM_KERNEL_IO(r2l_launch_static_stream_malvar##sfx, 1, R2L_RAW_F32, IO, R2L_STREAM_OCC_MALVAR)             \
-  R2L_STREAM_KERNEL_IO(r2l_launch_static_stream_bilinear_u16##sfx, 0, R2L_RAW_U16, IO, R2L_STREAM_OCC_BILINEAR)     \
-  R2L_STREAM_KERNEL_IO(r2l_launch_static_stream_malvar_u16##sfx, 1, R2L_RAW_U16, IO, R2L_STREAM_OCC_MALVAR)         \
-  R2L_STREAM_KERNEL_IO(r2l_launch_static_stream_bilinear_f64##sfx, 0, R2L_RAW_F64, IO, 3)                           \
-  R2L_STREAM_KERNEL_IO(r2l_launch_static_stream_malvar_f64##sfx, 1, R2L_RAW_F64, IO, 2)
-R2L_STREAM_KERNELS_IO(_bf16, R2L_IO_BF16)
-R2L_STREAM_KERNELS_IO(_f16, R2L_IO_F16)
-// ... and storing nothing: the channel sums of what the float32 siblings store (r2l_static_stats)
-R2L_STREAM_KERNELS_IO(_stats, R2L_IO_STATS)
-// ... and storing every row at its augmented position (r2l_static_fwd_epilogue: R2LEpi with sc = +-1, launch arguments): float32 and
-// 16-bit-container frames x the three output types, at their siblings' occupancy
-#define R2L_STREAM_KERNEL_EPI(name, DEB, RAWK, IO, OCC)                                                  \
-  R2L_BLOCKFN void name##_block(const R2LStaticStreamArgs& sa, int bid, int nblk, float* lds) {          \
-    r2l_static_stream_block<DEB, RAWK, false, IO, true>(sa, bid, nblk, lds);                             \
-  }                                                                                                      \
-  R2L_KERNEL_NT(name, R2LStaticStreamArgs, name##_block, R2L_STREAM_NT, OCC)
-#define R2L_STREAM_KERNELS_EPI(sfx, IO)                                                                             \
-  R2L_STREAM_KERNEL_EPI(r2l_launch_static_stream_bilinear##sfx, 0, R2L_RAW_F32, IO, R2L_STREAM_OCC_BILINEAR)        \
-  R2L_STREAM_KERNEL_EPI(r2l_launch_static_stream_malvar##sfx, 1, R2L_RAW_F32, IO, R2L_STREAM_OCC_MALVAR)            \
-  R2L_STREAM_KERNEL_EPI(r2l_launch_static_stream_bilinear_u16##sfx, 0, R2L_RAW_U16, IO, R2L_STREAM_OCC_BILINEAR)    \
-  R2L_STREAM_KERNEL_EPI(r2l_launch_static_stream_malvar_u16##sfx, 1, R2L_RAW_U16, IO, R2L_STREAM_OCC_MALVAR)
-R2L_STREAM_KERNELS_EPI(_epi, R2L_IO_F32)
-R2L_STREAM_KERNELS_EPI(_bf16_epi, R2L_IO_BF16)
-R2L_STREAM_KERNELS_EPI(_f16_epi, R2L_IO_F16)
-#endif
-R2L_KERNEL(r2l_launch_plane_filter, R2LPlaneArgs, r2l_plane_filter_block, 4)
-R2L_KERNEL(r2l_launch_spec_mask, R2LSpecMaskArgs, r2l_spec_mask_block, 4)
-R2L_KERNEL(r2l_launch_static_finish, R2LStaticFinishArgs, r2l_static_finish_block, 4)
-R2L_KERNEL(r2l_launch_static_menon, R2LMenonArgs, r2l_static_menon_block, 4)
-#ifndef R2L_SERIAL
-// row-streaming luma chains (r2l_static_chain.h): NW wavefronts side by side cover frames up to 256 * NW columns
-#ifndef R2L_CHAIN_OCC
-#define R2L_CHAIN_OCC 2
-#endif
-// behind unsharp_masking the 28 KB chroma ring per strip leaves one wavefront per SIMD on 1024-wide frames anyway:
-// 512 registers instead of spills
-#ifndef R2L_CHAIN_OCC_SH
-#define R2L_CHAIN_OCC_SH 1
-#endif
-// (the workgroup size and the LDS size follow the frame width at launch time: 64 threads and 16.1 KB per strip)
-#define R2L_MAX_DEVICES 64
-#ifdef R2L_LOCKSTEP
-#define R2L_CHAIN_KERNEL_IO(name, RAWK, DEB, SH, DN, IO, EPI)                                                 \
-  static int name(const R2LStaticChainArgs& a, int grid, void* stream) {                                      \
-    (void)stream;                                                                                             \
-    r2l_ls_note(#name);                                                                                       \
-    r2l_ls::launch(#name, grid, a.nw * 64, 2 * (size_t)R2L_CHAIN_LDS_DOUBLES(a.nw, SH), &a,                   \
-                   [&](int b_, float* lds_) { r2l_static_chain_block<RAWK, DEB, SH, DN, IO, EPI>(a, b_, grid, lds_); }); \
-    return 0;                                                                                                 \
-  }
-#else
-#define R2L_CHAIN_KERNEL_IO(name, RAWK, DEB, SH, DN, IO, EPI)                                                 \
-  __global__ __launch_bounds__((SH) ? 256 : 512, (SH) ? R2L_CHAIN_OCC_SH : R2L_CHAIN_OCC) void name##_kernel(const R2LStaticChainArgs a) { \
-    extern __shared__ __attribute__((aligned(16))) float r2l_chain_lds[];                                     \
-    r2l_static_chain_block<RAWK, DEB, SH, DN, IO, EPI>(a, (int)blockIdx.x, (int)gridDim.x, r2l_chain_lds);    \
-  }                                                                                                           \
-  static int name(const R2LStaticChainArgs& a, int grid, void* stream) {                                      \
-    const size_t lds_bytes = sizeof(double) * R2L_CHAIN_LDS_DOUBLES(a.nw, SH);                                \
-    {                                                                                                         \
-      /* the attribute is per device: remember what each device of this process was granted */               \
-      static std::mutex mu_;                                                                                  \
-      static size_t lds_ok[R2L_MAX_DEVICES];                                                                  \
-      int dev_ = 0;                                                                                           \
-      (void)hipGetDevice(&dev_);                                                                              \
-      std::lock_guard<std::mutex> g_(mu_);                                                                    \
-      size_t& ok_ = lds_ok[(unsigned)dev_ % R2L_MAX_DEVICES];                                                 \
-      if (lds_bytes > (ok_ ? ok_ : (size_t)48 * 1024)) {                                                      \
-        const hipError_t ea = hipFuncSetAttribute((const void*)name##_kernel,                                 \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);\
-        if (ea != hipSuccess) return r2l_fail(-10, std::string(#name ": ") + hipGetErrorString(ea));          \
-        ok_ = lds_bytes;                                                                                      \
-      }                                                                                                       \
-    }                                                                                                         \
-    R2L_LAUNCH(name, a.nw * 64, lds_bytes)                                                                    \
-  }
-#endif
-// [16-bit / float64 frames] x [Malvar2004] x [unsharp_masking] x [median_denoising] x [16-bit output: float32 / 16-bit frames]
-// x [EPI: the output epilogue, r2l_static_fwd_epilogue: float32 / 16-bit frames, the three output types]
-#define R2L_CHAIN_KERNELS_IO_EPI(sfx, RAWK, IO, EPI)                                               \
-  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain##sfx, RAWK, 0, 0, 0, IO, EPI)                        \
-  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_median##sfx, RAWK, 0, 0, 1, IO, EPI)                 \
-  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_unsharp##sfx, RAWK, 0, 1, 0, IO, EPI)                \
-  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_unsharp_median##sfx, RAWK, 0, 1, 1, IO, EPI)         \
-  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_malvar##sfx, RAWK, 1, 0, 0, IO, EPI)                 \
-  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_malvar_median##sfx, RAWK, 1, 0, 1, IO, EPI)          \
-  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_malvar_unsharp##sfx, RAWK, 1, 1, 0, IO, EPI)         \
-  R2L_CHAIN_KERNEL_IO(r2l_launch_static_chain_malvar_unsharp_median##sfx, RAWK, 1, 1, 1, IO, EPI)
-#define R2L_CHAIN_KERNELS_IO(sfx, RAWK, IO) R2L_CHAIN_KERNELS_IO_EPI(sfx, RAWK, IO, false)
-#define R2L_CHAIN_KERNELS(sfx, RAWK) R2L_CHAIN_KERNELS_IO(sfx, RAWK, R2L_IO_F32)
-R2L_CHAIN_KERNELS(, R2L_RAW_F32)
-R2L_CHAIN_KERNELS(_u16, R2L_RAW_U16)
-R2L_CHAIN_KERNELS(_f64, R2L_RAW_F64)
-R2L_CHAIN_KERNELS_IO(_bf16, R2L_RAW_F32, R2L_IO_BF16)
-R2L_CHAIN_KERNELS_IO(_u16_bf16, R2L_RAW_U16, R2L_IO_BF16)
-R2L_CHAIN_KERNELS_IO(_f16, R2L_RAW_F32, R2L_IO_F16)
-R2L_CHAIN_KERNELS_IO(_u16_f16, R2L_RAW_U16, R2L_IO_F16)
-R2L_CHAIN_KERNELS_IO(_stats, R2L_RAW_F32, R2L_IO_STATS)
-R2L_CHAIN_KERNELS_IO(_u16_stats, R2L_RAW_U16, R2L_IO_STATS)
-R2L_CHAIN_KERNELS_IO_EPI(_epi, R2L_RAW_F32, R2L_IO_F32, true)
-R2L_CHAIN_KERNELS_IO_EPI(_u16_epi, R2L_RAW_U16, R2L_IO_F32, true)
-R2L_CHAIN_KERNELS_IO_EPI(_bf16_epi, R2L_RAW_F32, R2L_IO_BF16, true)
-R2L_CHAIN_KERNELS_IO_EPI(_u16_bf16_epi, R2L_RAW_U16, R2L_IO_BF16, true)
-R2L_CHAIN_KERNELS_IO_EPI(_f16_epi, R2L_RAW_F32, R2L_IO_F16, true)
-R2L_CHAIN_KERNELS_IO_EPI(_u16_f16_epi, R2L_RAW_U16, R2L_IO_F16, true)
-#endif
-R2L_KERNEL(r2l_launch_static_short, R2LStaticArgs, r2l_static_short_block<GStatic>,
-           R2L_STATIC_SHORT_LDS_FLOATS)
-
-R2L_KERNEL(r2l_launch_conv33_fwd, R2LStageArgs, r2l_conv33_fwd_block, 4)
-R2L_KERNEL(r2l_launch_conv33_bwd, R2LStageArgs, r2l_conv33_bwd_block, R2L_RED_FLOATS)
-R2L_KERNEL(r2l_launch_mix3_fwd, R2LStageArgs, r2l_mix3_fwd_block, 4)
-R2L_KERNEL(r2l_launch_mix3_bwd, R2LStageArgs, r2l_mix3_bwd_block, R2L_RED_FLOATS)
-R2L_KERNEL(r2l_launch_pconv_fwd, R2LStageArgs, r2l_pconv_fwd_block, 4)
-R2L_KERNEL(r2l_launch_pconv_bwd, R2LStageArgs, r2l_pconv_bwd_block, R2L_RED_FLOATS)
-R2L_KERNEL(r2l_launch_point, R2LPointArgs, r2l_point_block, R2L_RED_FLOATS)
-R2L_KERNEL(r2l_launch_aug, R2LAugArgs, r2l_aug_block, 4)
-R2L_KERNEL(r2l_launch_aug_tiled, R2LAugTiledArgs, r2l_aug_tiled_block, R2L_AUG_LDS_FLOATS)
-R2L_KERNEL(r2l_launch_axpy, R2LAxpyArgs, r2l_axpy_block, 4)
-R2L_KERNEL(r2l_launch_philox_noise, R2LPhiloxArgs, r2l_philox_noise_block, 4)
-R2L_KERNEL(r2l_launch_strong_fwd_flat, R2LStrongArgs, r2l_strong_fwd_flat_block, 4)
-R2L_KERNEL(r2l_launch_strong_fwd_sharp, R2LStrongArgs, r2l_strong_fwd_sharp_block, R2L_AUGS_LDS_FLOATS)
-R2L_KERNEL(r2l_launch_strong_bwd_sharp, R2LStrongBwdArgs, r2l_strong_bwd_sharp_block, 4)
-R2L_KERNEL(r2l_launch_strong_bwd_rot, R2LStrongBwdArgs, r2l_strong_bwd_rot_block, 4)
-R2L_KERNEL(r2l_launch_corrupt_identity, R2LCorruptArgs, r2l_corrupt_point_block<R2L_CORRUPT_IDENTITY>, 4)
-R2L_KERNEL(r2l_launch_corrupt_gaussian_noise, R2LCorruptArgs, r2l_corrupt_point_block<R2L_CORRUPT_GAUSSIAN_NOISE>, 4)
-R2L_KERNEL(r2l_launch_corrupt_shot_noise, R2LCorruptArgs, r2l_corrupt_point_block<R2L_CORRUPT_SHOT_NOISE>, 4)
-R2L_KERNEL(r2l_launch_corrupt_impulse_noise, R2LCorruptArgs, r2l_corrupt_point_block<R2L_CORRUPT_IMPULSE_NOISE>, 4)
-R2L_KERNEL(r2l_launch_corrupt_speckle_noise, R2LCorruptArgs, r2l_corrupt_point_block<R2L_CORRUPT_SPECKLE_NOISE>, 4)
-R2L_KERNEL(r2l_launch_corrupt_contrast, R2LCorruptArgs, r2l_corrupt_point_block<R2L_CORRUPT_CONTRAST>, 4)
-R2L_KERNEL(r2l_launch_corrupt_brightness, R2LCorruptArgs, r2l_corrupt_point_block<R2L_CORRUPT_BRIGHTNESS>, 4)
-R2L_KERNEL(r2l_launch_corrupt_saturate, R2LCorruptArgs, r2l_corrupt_point_block<R2L_CORRUPT_SATURATE>, 4)
-R2L_KERNEL(r2l_launch_corrupt_mean, R2LCorruptArgs, r2l_corrupt_mean_block, R2L_CMEAN_LDS_FLOATS)
-R2L_KERNEL(r2l_launch_corrupt_blur, R2LCorruptArgs, r2l_corrupt_blur_block, R2L_CBLUR_LDS_FLOATS)
-R2L_KERNEL(r2l_launch_corrupt_zoom, R2LCorruptZoomArgs, r2l_corrupt_zoom_block, 4)
-R2L_KERNEL(r2l_launch_ssim, R2LSsimArgs, r2l_ssim_block, R2L_SSIM_LDS_FLOATS)
-R2L_KERNEL(r2l_launch_ssim_bwd, R2LSsimBwdArgs, r2l_ssim_bwd_block, R2L_SSIM_BWD_LDS_FLOATS)
-R2L_KERNEL(r2l_launch_l2, R2LL2Args, r2l_l2_block, R2L_RED_FLOATS_N(1))
-R2L_KERNEL(r2l_launch_pack_fold, R2LPackFoldArgs, r2l_pack_fold_block, R2L_P_COUNT + 2)
-R2L_KERNEL(r2l_launch_channel_sums, R2LChannelSumsArgs, r2l_channel_sums_block, R2L_SUMS_LDS_FLOATS)
-R2L_KERNEL(r2l_launch_sums_finish, R2LSumsFinishArgs, r2l_sums_finish_block, R2L_SUMS_LDS_FLOATS)
-
-// ---- grid sizing ------------------------------------------------------------------------------
-static_assert(R2L_MAX_BLOCKS == 2048 && 1 + R2L_MAX_GROUPS <= R2L_NT, "partials / arrival counters are laid out for at most 2048 workgroups");
-// Launch shapes are compile-time choices of the product build.  Diagnostic builds (-DR2L_TEST_HOOKS: the host
-// emulation and tests/_build/libr2l_isp_hooks.so, never the shipped libr2l_isp.so) can override them through the
-// environment -- that is how the tests show that no result depends on the workgroup count, and how A/B runs sweep
-// band heights.
-#ifdef R2L_TEST_HOOKS
-static int r2l_env_int(const char* name, int dflt) {
-  const char* s = getenv(name);
-  if (!s || !*s) return dflt;
-  const int v = atoi(s);
-  return v > 0 ? v : dflt;
-}
-#else
-static inline int r2l_env_int(const char*, int dflt) { return dflt; }
-#endif
-// the flat grid-stride kernels (staged path, raw2rgb, the weak augmentation's permutation): min(computed grid, R2L_GRID_FLAT)
-// in diagnostic builds, so that their second and later passes run at small shapes; the computed grid in the product build
-static int r2l_flat_grid(size_t g) {
-  const size_t cap = (size_t)r2l_env_int("R2L_GRID_FLAT", 0x7fffffff);
-  if (g > cap) g = cap;
-  return g < 1 ? 1 : (int)g;
-}
-// persistent tile-walking kernels: at most `cap` workgroups (256 CUs x resident workgroups per CU),
-// a multiple of 8 when possible so that the XCD-grouped walk applies
-static int r2l_tile_grid(int ntiles, int cap) {
-  if (cap > R2L_MAX_BLOCKS) cap = R2L_MAX_BLOCKS;
-  int g = ntiles < cap ? ntiles : cap;
-  if (g >= 8) g -= g % 8;
-  return g < 1 ? 1 : g;
-}
-
-// Band height of the plane passes (r2l_param_stream.h, r2l_param_plane_bwd.h): a multiple of 6 rows (bands start on
-// multiples of 6: the ring slot of a row is the unroll position of its step), the one that needs the fewest rounds of
-// `slots` resident wavefronts x the rows a wavefront walks (+ 4 load-only warm-up steps + its start) -- 64x512x512 apply
-// pass: 24 rows = 2,816 wavefronts, one round at 3 per SIMD (65 us; 18 rows: 68.5; 12: 67.5; 36: 71.5,
-// profiles/r03_apply_kept.txt; re-swept under the progress-priority build, profiles/r04_bands.txt); 64x256x256: 6 rows.
-// `env`: override of diagnostic builds.
-static int r2l_band_rows(int B, int H, int W, long slots, const char* env) {
-  const long nstrip = (W + 255) / 256;
-  int bh = 6;
-  long best = -1;
-  for (int c = 6; c <= 48; c += 6) {
-    const long items = (long)B * nstrip * ((H + c - 1) / c);
-    const long cost = ((items + slots - 1) / slots) * (10L * c + 32);
-    if (best < 0 || cost < best) {
-      best = cost;
-      bh = c;
-    }
-  }
-  return (r2l_env_int(env, bh) + 5) / 6 * 6;
-}
-// Work items of a plane pass -- one per (image, 256-column strip, band of band_h rows) -- and its workgroups: nwv items in
-// flight per workgroup, at most `cap` workgroups and R2L_MAX_BLOCKS (the partials of the reduction trees); cap = 0: a pass
-// without partials, one workgroup per nwv items
-static long r2l_plane_items(int B, int H, int W, int band_h) {
-  return (long)B * ((W + 255) / 256) * ((H + band_h - 1) / band_h);
-}
-static int r2l_plane_grid(int B, int H, int W, int band_h, int nwv, long cap) {
-  long g = (r2l_plane_items(B, H, W, band_h) + nwv - 1) / nwv;
-  if (cap && g > cap) g = cap;
-  if (cap && g > R2L_MAX_BLOCKS) g = R2L_MAX_BLOCKS;
-  return (int)g;
-}
-
-// ---- workspace ----------------------------------------------------------------------------------
-struct R2LWorkspace {
-  R2LFolded* folded;
-  float* part_b1;
-  float* part_b2;
-  float* part_small;
-  double* sums;
-  double* gpartial;    // [R2L_MAX_GROUPS][R2L_NSUMS] group partials of the in-kernel final reductions
-  unsigned* counters;  // [1 + R2L_MAX_GROUPS] arrival counters: zeroed by the fold kernel, zero after every launch
-  float* gypp;
-  float* yp;     // (B,H,W): the sharpened luma Y' of the forward, for kernel B1 (R2L_F_KEEP_LUMA)
-  float* hp;     // (B,H,W): the blur's adjoint of dL/dY'' (plane passes of kernel B2, r2l_param_plane_bwd.h)
-  float* debug;  // 3 x [R2L_MAX_BLOCKS][8] floats: per-phase cycle stamps of diagnostic builds (fwd, bwd1, bwd2)
-  // step block (r2l_isp_step_fwd / _bwd): what one training step keeps between its launches
-  float* packed;    // [R2L_P_COUNT] the parameter values the forward saw
-  float* bn;        // [6] mean, istd
-  float* bn_bwd;    // [6] mean(g), mean(g * xhat)
-  double* stats;    // [7] this rank's statistics sums (+ pixel count)
-  double* moments;  // [7] mean, biased var, pixel count of the global batch
-  double* bsums;    // [6] this rank's BatchNorm backward sums
-  size_t total;
-};
-static size_t r2l_align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-static R2LWorkspace r2l_carve(void* base, int B, int H, int W) {
-  R2LWorkspace w;
-  size_t off = 0;
-  char* p = (char*)base;
-  w.folded = (R2LFolded*)(p + off);
-  off += r2l_align_up(sizeof(R2LFolded));
-  w.part_b1 = (float*)(p + off);
-  off += r2l_align_up(sizeof(float) * R2L_B1_NACC * R2L_MAX_BLOCKS);
-  w.part_b2 = (float*)(p + off);
-  off += r2l_align_up(sizeof(float) * R2L_B2_NACC * R2L_MAX_BLOCKS);
-  w.part_small = (float*)(p + off);
-  off += r2l_align_up(sizeof(float) * 12 * R2L_MAX_BLOCKS);
-  w.sums = (double*)(p + off);
-  off += r2l_align_up(sizeof(double) * R2L_NSUMS);
-  w.gpartial = (double*)(p + off);
-  off += r2l_align_up(sizeof(double) * R2L_NSUMS * R2L_MAX_GROUPS);
-  w.counters = (unsigned*)(p + off);
-  off += r2l_align_up(sizeof(unsigned) * (1 + R2L_MAX_GROUPS));
-  w.debug = (float*)(p + off);
-#ifdef R2L_EXP_STAMPS
-  off += r2l_align_up(sizeof(float) * 4 * 8 * R2L_MAX_BLOCKS);  // + the wavefront placement records (tests/timeline_fwd.py)
-#else
-  off += r2l_align_up(sizeof(float) * 3 * 8 * R2L_MAX_BLOCKS);
-#endif
-  w.packed = (float*)(p + off);
-  off += r2l_align_up(sizeof(float) * R2L_P_COUNT);
-  w.bn = (float*)(p + off);
-  w.bn_bwd = w.bn + 8;
-  off += r2l_align_up(sizeof(float) * 16);
-  w.stats = (double*)(p + off);
-  w.moments = w.stats + 8;
-  w.bsums = w.stats + 16;
-  off += r2l_align_up(sizeof(double) * 24);
-  w.gypp = (float*)(p + off);
-  off += r2l_align_up(sizeof(float) * (size_t)B * H * W);
-  w.yp = (float*)(p + off);
-  off += r2l_align_up(sizeof(float) * (size_t)B * H * W);
-  w.hp = (float*)(p + off);
-  off += r2l_align_up(sizeof(float) * (size_t)B * H * W);
-  w.total = off;
-  return w;
-}
-
-static int r2l_check_dims(int B, int H, int W) {
-  if (B < 1) return r2l_fail(-1, "B must be >= 1");
-  if (H < 4 || W < 4 || (H & 1) || (W & 1))
-    return r2l_fail(-1, "H and W must be even and >= 4 (Bayer quads; 5x5 mirror padding)");
-  if ((size_t)H * W > ((size_t)1 << 29)) return r2l_fail(-1, "frames above 2^29 pixels are not supported");
-  if ((size_t)B * H * W > ((size_t)1 << 40)) return r2l_fail(-1, "batch too large");
-  return 0;
-}
+#include "r2l_launch.h"
+#include "r2l_kernels_step.h"
+#include "r2l_kernels_static.h"
+#include "r2l_kernels_rest.h"
+#include "r2l_host_util.h"
 
 extern "C" {
-
-int r2l_abi_version(void) { return R2L_ABI_VERSION; }
-const char* r2l_last_error(void) { return r2l_err.c_str(); }
-int r2l_is_device_build(void) {
-#ifdef R2L_EMUL
-  return 0;
-#else
-  return 1;
-#endif
-}
-
-void r2l_timing_enable(int on) {
-#ifndef R2L_EMUL
-  std::lock_guard<std::mutex> g(r2l_timing_mutex);
-  r2l_timing_on = on != 0;
-#elif defined(R2L_LOCKSTEP)
-  std::lock_guard<std::mutex> g(r2l_ls_record_mutex);
-  r2l_ls_record_on = on != 0;
-  if (on) r2l_ls_record.clear();
-#else
-  (void)on;
-#endif
-}
-
-int r2l_timing_report(char* buf, size_t n) {
-  std::string out;
-#ifdef R2L_LOCKSTEP
-  {  // the launch record: "name count 0" lines (no clock in the emulation)
-    std::lock_guard<std::mutex> g(r2l_ls_record_mutex);
-    for (auto& kv : r2l_ls_record) out += kv.first + " " + std::to_string(kv.second) + " 0\n";
-    r2l_ls_record.clear();
-  }
-#endif
-#ifndef R2L_EMUL
-  std::vector<R2LTimedLaunch> v;
-  {
-    std::lock_guard<std::mutex> g(r2l_timing_mutex);
-    v.swap(r2l_timed);
-  }
-  std::map<std::string, std::pair<int, double>> acc;
-  for (auto& t : v) {
-    (void)hipEventSynchronize(t.e1);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, t.e0, t.e1);
-    (void)hipEventDestroy(t.e0);
-    (void)hipEventDestroy(t.e1);
-    auto& a = acc[t.name];
-    a.first += 1;
-    a.second += ms;
-  }
-  for (auto& kv : acc)
-    out += kv.first + " " + std::to_string(kv.second.first) + " " + std::to_string(kv.second.second) + "\n";
-#endif
-  if (!buf || n == 0) return (int)out.size();
-  const size_t m = out.size() < n - 1 ? out.size() : n - 1;
-  memcpy(buf, out.data(), m);
-  buf[m] = 0;
-  return (int)m;
-}
 
 size_t r2l_isp_workspace_bytes(int B, int H, int W) {
   if (B < 1 || H < 1 || W < 1) return 0;
   return r2l_carve(nullptr, B, H, W).total;
-}
-
-static int r2l_check_raw(const R2LRaw& raw, int W, const char* who) {
-  if (!raw.f32 && !raw.u16 && !raw.f64) return r2l_fail(-1, std::string(who) + ": null pointer");
-  if (raw.f64 && (W & 3)) return r2l_fail(-4, std::string(who) + ": float64 frames need W % 4 == 0");
-  if (raw.u16 && !(raw.denom >= 1.f)) return r2l_fail(-1, std::string(who) + ": denom must be >= 1 (2**bits - 1)");
-  if (raw.u16 && (W & 3)) return r2l_fail(-1, std::string(who) + ": 16-bit frames need W % 4 == 0");
-  return 0;
 }
 
 // ---- the forward: one plan, one launcher ----------------------------------------------------------------------------------
@@ -1056,7 +303,6 @@ int r2l_bn_bwd_reduce(const float* grad_out, const float* out, const double* tot
 }
 
 // ---- the backward: one plan, one launcher ---------------------------------------------------------------------------------
-#define R2L_STEP_EPI_MASK (R2L_STEP_EPI_HFLIP | R2L_STEP_EPI_VFLIP | (3 << R2L_STEP_EPI_ROT_SHIFT))
 // kernel B1 as a tile kernel (which instantiation), as the plane passes, or as a reduced plane pass (R2LBwdPlan::select)
 enum { R2L_B1_TILE_SAVED, R2L_B1_TILE_ADD, R2L_B1_TILE_EXACT, R2L_B1_TILE_RAGGED, R2L_B1_PLANES };
 // What a backward launches, decided from the shape of the call alone (r2l_bwd_plan): r2l_bwd_launch walks it, and
@@ -1391,28 +637,6 @@ int r2l_additive_bwd(const float* grad_out, const float* out, const float* bn_me
 }
 
 // ---- one training step in two calls (r2l_isp_step_fwd / r2l_isp_step_bwd) --------------------------------
-// the output epilogue travels in the bits of `phase` above R2L_STEP_KEEP_LUMA (R2L_STEP_EPI_*); the affine map of
-// R2LEpi follows from r2l_aug_map, the definition the stand-alone permutation kernel (r2l_augment) uses
-static int r2l_epi_from_phase(int phase, int H, int W, R2LEpi& ep) {
-  const int hflip = (phase & R2L_STEP_EPI_HFLIP) != 0, vflip = (phase & R2L_STEP_EPI_VFLIP) != 0;
-  const int k = (phase >> R2L_STEP_EPI_ROT_SHIFT) & 3;
-  ep = R2LEpi{0, 0, 0, 0};
-  if (!(hflip || vflip || k)) return 0;
-  if ((k & 1) && H != W) return r2l_fail(-1, "output epilogue: a rotation by 90 degrees needs square frames");
-  const int Wo = (k & 1) ? H : W;
-  int r0, c0, r1, c1, r2, c2;
-  r2l_aug_map(H, W, hflip, vflip, k, 0, 0, r0, c0);
-  r2l_aug_map(H, W, hflip, vflip, k, 1, 0, r1, c1);
-  r2l_aug_map(H, W, hflip, vflip, k, 0, 1, r2, c2);
-  ep.on = 1;
-  ep.s0 = r0 * Wo + c0;
-  ep.sr = (r1 * Wo + c1) - ep.s0;
-  ep.sc = (r2 * Wo + c2) - ep.s0;
-  return 0;
-}
-static R2LRaw r2l_raw_any(const void* raw, int raw_u16, float denom) {
-  return raw_u16 ? r2l_raw_u16((const unsigned short*)raw, denom) : r2l_raw_f32((const float*)raw);
-}
 size_t r2l_isp_step_offset(int which, int B, int H, int W) {
   if (B < 1 || H < 1 || W < 1) return 0;
   const R2LWorkspace ws = r2l_carve(nullptr, B, H, W);
@@ -1758,6 +982,65 @@ int r2l_isp_step_bwd_io(const void* raw, int raw_u16, float denom, const float* 
                       raw_grad_scratch_bytes);
 }
 
+// ---- the whole forward and backward as single calls (every r2l_isp_fwd* / r2l_isp_bwd*) -----------------------------------------
+int r2l_isp_fwd(const float* raw, const float* params, const float* additive,
+                const float* bn_mean_istd, float* out, double* stats, void* workspace,
+                size_t workspace_bytes, int B, int H, int W, int flags, void* stream) {
+  return r2l_isp_fwd_impl(R2LFwdCall{r2l_raw_f32(raw), params, additive, bn_mean_istd, out, stats, nullptr, R2LEpi{0, 0, 0, 0},
+                                     R2L_IO_F32, R2L_FWD_WHOLE, B, H, W, stream},
+                          flags, workspace, workspace_bytes);
+}
+// statistics pass + BatchNorm bookkeeping in one launch (one rank: no exchange between the two)
+static int r2l_isp_fwd_stats_bn_impl(const R2LRaw& raw, const float* params, const float* additive, double* stats,
+                                     float* bn_mean_istd, double* moments, float* running_mean, float* running_var,
+                                     long long* num_batches_tracked, double eps, double momentum, void* workspace,
+                                     size_t workspace_bytes, int B, int H, int W, void* stream) {
+  if (!stats || !bn_mean_istd) return r2l_fail(-1, "r2l_isp_fwd_stats_bn: null pointer");
+  if ((running_mean == nullptr) != (running_var == nullptr))
+    return r2l_fail(-1, "r2l_isp_fwd_stats_bn: running_mean and running_var go together");
+  R2LBnFinalizeArgs f{stats, 1, bn_mean_istd, moments, running_mean, running_var, eps, momentum, num_batches_tracked};
+  return r2l_isp_fwd_impl(R2LFwdCall{raw, params, additive, nullptr, nullptr, stats, &f, R2LEpi{0, 0, 0, 0}, R2L_IO_F32,
+                                     R2L_FWD_WHOLE, B, H, W, stream},
+                          R2L_F_STATS_ONLY, workspace, workspace_bytes);
+}
+int r2l_isp_fwd_stats_bn(const float* raw, const float* params, const float* additive, double* stats,
+                         float* bn_mean_istd, double* moments, float* running_mean, float* running_var,
+                         long long* num_batches_tracked, double eps, double momentum, void* workspace,
+                         size_t workspace_bytes, int B, int H, int W, void* stream) {
+  return r2l_isp_fwd_stats_bn_impl(r2l_raw_f32(raw), params, additive, stats, bn_mean_istd, moments, running_mean,
+                                   running_var, num_batches_tracked, eps, momentum, workspace, workspace_bytes, B,
+                                   H, W, stream);
+}
+int r2l_isp_fwd_stats_bn_u16(const unsigned short* raw, float denom, const float* params, const float* additive,
+                             double* stats, float* bn_mean_istd, double* moments, float* running_mean,
+                             float* running_var, long long* num_batches_tracked, double eps, double momentum,
+                             void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
+  return r2l_isp_fwd_stats_bn_impl(r2l_raw_u16(raw, denom), params, additive, stats, bn_mean_istd, moments,
+                                   running_mean, running_var, num_batches_tracked, eps, momentum, workspace,
+                                   workspace_bytes, B, H, W, stream);
+}
+int r2l_isp_fwd_u16(const unsigned short* raw, float denom, const float* params, const float* additive,
+                    const float* bn_mean_istd, float* out, double* stats, void* workspace,
+                    size_t workspace_bytes, int B, int H, int W, int flags, void* stream) {
+  return r2l_isp_fwd_impl(R2LFwdCall{r2l_raw_u16(raw, denom), params, additive, bn_mean_istd, out, stats, nullptr,
+                                     R2LEpi{0, 0, 0, 0}, R2L_IO_F32, R2L_FWD_WHOLE, B, H, W, stream},
+                          flags, workspace, workspace_bytes);
+}
+int r2l_isp_bwd(const float* raw, const float* params, const float* additive,
+                const float* bn_mean_istd, const float* bn_bwd, const float* grad_out,
+                float* grad_params, float* grad_raw, void* workspace, size_t workspace_bytes, int B,
+                int H, int W, int flags, void* stream) {
+  return r2l_isp_bwd_impl(r2l_raw_f32(raw), params, additive, bn_mean_istd, bn_bwd, grad_out, grad_params, grad_raw,
+                          workspace, workspace_bytes, B, H, W, flags, stream);
+}
+int r2l_isp_bwd_u16(const unsigned short* raw, float denom, const float* params, const float* additive,
+                    const float* bn_mean_istd, const float* bn_bwd, const float* grad_out,
+                    float* grad_params, void* workspace, size_t workspace_bytes, int B, int H, int W, int flags,
+                    void* stream) {
+  return r2l_isp_bwd_impl(r2l_raw_u16(raw, denom), params, additive, bn_mean_istd, bn_bwd, grad_out, grad_params,
+                          nullptr, workspace, workspace_bytes, B, H, W, flags, stream);
+}
+
 static int r2l_raw2rgb_fwd_impl(const R2LRaw& raw, const float* black_level, float* out, int B, int H, int W,
                                 int reduce_size, int out_channels, void* stream) {
   if (B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1)) return r2l_fail(-1, "raw2rgb: H and W must be even");
@@ -1918,47 +1201,6 @@ enum {
   R2L_ROUTE_STREAM,  // the short chain, row-streaming (r2l_static_stream.h)
   R2L_ROUTE_SHORT    // the short chain's tile kernel
 };
-typedef int (*R2LStreamLaunch)(const R2LStaticStreamArgs&, int, void*);
-#define R2L_STREAM_ROW(name, sfx)                                                                \
-  {{name##_bilinear##sfx, name##_malvar##sfx}, {name##_bilinear_u16##sfx, name##_malvar_u16##sfx}, \
-   {name##_bilinear_f64##sfx, name##_malvar_f64##sfx}}
-// [output: float32 | bfloat16 | float16 | none, statistics][frames: float32 | 16-bit | float64][bilinear | Malvar2004]
-static const R2LStreamLaunch r2l_static_stream_table[][3][2] = {R2L_STREAM_ROW(r2l_launch_static_stream, ),
-#ifndef R2L_SERIAL
-                                                                R2L_STREAM_ROW(r2l_launch_static_stream, _bf16),
-                                                                R2L_STREAM_ROW(r2l_launch_static_stream, _f16),
-                                                                R2L_STREAM_ROW(r2l_launch_static_stream, _stats)
-#endif
-};
-static const R2LStreamLaunch r2l_static_luma_table[3][2] = R2L_STREAM_ROW(r2l_launch_static_luma, );
-#undef R2L_STREAM_ROW
-#ifndef R2L_SERIAL
-// the epilogue forms (r2l_static_fwd_epilogue): [output: float32 | bfloat16 | float16][frames: float32 | 16-bit][bilinear | Malvar2004]
-#define R2L_STREAM_ROW_EPI(sfx)                                                                  \
-  {{r2l_launch_static_stream_bilinear##sfx, r2l_launch_static_stream_malvar##sfx},               \
-   {r2l_launch_static_stream_bilinear_u16##sfx, r2l_launch_static_stream_malvar_u16##sfx}}
-static const R2LStreamLaunch r2l_static_stream_epi_table[3][2][2] = {R2L_STREAM_ROW_EPI(_epi), R2L_STREAM_ROW_EPI(_bf16_epi),
-                                                                     R2L_STREAM_ROW_EPI(_f16_epi)};
-#undef R2L_STREAM_ROW_EPI
-#endif
-#ifndef R2L_SERIAL
-typedef int (*R2LChainLaunch)(const R2LStaticChainArgs&, int, void*);
-#define R2L_CHAIN_ROW(sfx)                                                                                          \
-  {{{r2l_launch_static_chain##sfx, r2l_launch_static_chain_median##sfx},                                            \
-    {r2l_launch_static_chain_unsharp##sfx, r2l_launch_static_chain_unsharp_median##sfx}},                           \
-   {{r2l_launch_static_chain_malvar##sfx, r2l_launch_static_chain_malvar_median##sfx},                              \
-    {r2l_launch_static_chain_malvar_unsharp##sfx, r2l_launch_static_chain_malvar_unsharp_median##sfx}}}
-// [output][frames][Malvar2004][unsharp_masking][median_denoising]; float64 frames with a 16-bit output or none (statistics): none
-static const R2LChainLaunch r2l_static_chain_table[4][3][2][2][2] = {{R2L_CHAIN_ROW(), R2L_CHAIN_ROW(_u16), R2L_CHAIN_ROW(_f64)},
-                                                                     {R2L_CHAIN_ROW(_bf16), R2L_CHAIN_ROW(_u16_bf16)},
-                                                                     {R2L_CHAIN_ROW(_f16), R2L_CHAIN_ROW(_u16_f16)},
-                                                                     {R2L_CHAIN_ROW(_stats), R2L_CHAIN_ROW(_u16_stats)}};
-// the epilogue forms: [output: float32 | bfloat16 | float16][frames: float32 | 16-bit][Malvar2004][unsharp_masking][median_denoising]
-static const R2LChainLaunch r2l_static_chain_epi_table[3][2][2][2][2] = {{R2L_CHAIN_ROW(_epi), R2L_CHAIN_ROW(_u16_epi)},
-                                                                         {R2L_CHAIN_ROW(_bf16_epi), R2L_CHAIN_ROW(_u16_bf16_epi)},
-                                                                         {R2L_CHAIN_ROW(_f16_epi), R2L_CHAIN_ROW(_u16_f16_epi)}};
-#undef R2L_CHAIN_ROW
-#endif
 
 // What a static call launches and what it needs, decided from the shape of the call alone: r2l_static_fwd_impl hands it to
 // r2l_static_launch, the workspace queries report `workspace_bytes`, r2l_static_io_supported reports `no_io`
@@ -2069,7 +1311,6 @@ static R2LStaticPlan r2l_static_plan(int frames, int B, int H, int W, int debaye
                  ? "a rotation by 90 or 270 degrees (k odd) is not part of the row-streaming kernels' stores"
                  : one_launch(2);
   const bool epi = want_epi && !p.no_epi;
-  (void)epi;
   if (B < 1 || H < 1 || W < 1) return p;
 
   const size_t px = (size_t)B * H * W;
@@ -2123,7 +1364,7 @@ static R2LStaticPlan r2l_static_plan(int frames, int B, int H, int W, int debaye
         p.nparts = (int)grid * p.nseg;
         p.workspace_bytes = sizeof(double) * 6 * (size_t)p.nparts;
       }
-      p.chain = epi ? r2l_static_chain_epi_table[out][kind][malvar][unsharp][median] : r2l_static_chain_table[out][kind][malvar][unsharp][median];
+      p.chain = r2l_static_chain_table[epi][out][kind][malvar][unsharp][median];
 #endif
       break;
     }
@@ -2157,10 +1398,7 @@ static R2LStaticPlan r2l_static_plan(int frames, int B, int H, int W, int debaye
         p.nparts = (int)grid * wpb;
         p.workspace_bytes = sizeof(double) * 6 * (size_t)p.nparts;
       }
-      p.stream = p.route == R2L_ROUTE_PLANES ? r2l_static_luma_table[kind][malvar] : r2l_static_stream_table[out][kind][malvar];
-#ifndef R2L_SERIAL
-      if (epi) p.stream = r2l_static_stream_epi_table[out][kind][malvar];
-#endif
+      p.stream = p.route == R2L_ROUTE_PLANES ? r2l_static_luma_table[kind][malvar] : r2l_static_stream_table[epi][out][kind][malvar];
       break;
     }
     default: {  // persistent 64 x 64 tile walkers
@@ -2362,63 +1600,6 @@ static int r2l_static_fwd_impl(const R2LStaticCall& c) {
   return c.io == R2L_IO_STATS ? r2l_static_sums_finish(p, c) : 0;
 }
 
-int r2l_isp_fwd(const float* raw, const float* params, const float* additive,
-                const float* bn_mean_istd, float* out, double* stats, void* workspace,
-                size_t workspace_bytes, int B, int H, int W, int flags, void* stream) {
-  return r2l_isp_fwd_impl(R2LFwdCall{r2l_raw_f32(raw), params, additive, bn_mean_istd, out, stats, nullptr, R2LEpi{0, 0, 0, 0},
-                                     R2L_IO_F32, R2L_FWD_WHOLE, B, H, W, stream},
-                          flags, workspace, workspace_bytes);
-}
-// statistics pass + BatchNorm bookkeeping in one launch (one rank: no exchange between the two)
-static int r2l_isp_fwd_stats_bn_impl(const R2LRaw& raw, const float* params, const float* additive, double* stats,
-                                     float* bn_mean_istd, double* moments, float* running_mean, float* running_var,
-                                     long long* num_batches_tracked, double eps, double momentum, void* workspace,
-                                     size_t workspace_bytes, int B, int H, int W, void* stream) {
-  if (!stats || !bn_mean_istd) return r2l_fail(-1, "r2l_isp_fwd_stats_bn: null pointer");
-  if ((running_mean == nullptr) != (running_var == nullptr))
-    return r2l_fail(-1, "r2l_isp_fwd_stats_bn: running_mean and running_var go together");
-  R2LBnFinalizeArgs f{stats, 1, bn_mean_istd, moments, running_mean, running_var, eps, momentum, num_batches_tracked};
-  return r2l_isp_fwd_impl(R2LFwdCall{raw, params, additive, nullptr, nullptr, stats, &f, R2LEpi{0, 0, 0, 0}, R2L_IO_F32,
-                                     R2L_FWD_WHOLE, B, H, W, stream},
-                          R2L_F_STATS_ONLY, workspace, workspace_bytes);
-}
-int r2l_isp_fwd_stats_bn(const float* raw, const float* params, const float* additive, double* stats,
-                         float* bn_mean_istd, double* moments, float* running_mean, float* running_var,
-                         long long* num_batches_tracked, double eps, double momentum, void* workspace,
-                         size_t workspace_bytes, int B, int H, int W, void* stream) {
-  return r2l_isp_fwd_stats_bn_impl(r2l_raw_f32(raw), params, additive, stats, bn_mean_istd, moments, running_mean,
-                                   running_var, num_batches_tracked, eps, momentum, workspace, workspace_bytes, B,
-                                   H, W, stream);
-}
-int r2l_isp_fwd_stats_bn_u16(const unsigned short* raw, float denom, const float* params, const float* additive,
-                             double* stats, float* bn_mean_istd, double* moments, float* running_mean,
-                             float* running_var, long long* num_batches_tracked, double eps, double momentum,
-                             void* workspace, size_t workspace_bytes, int B, int H, int W, void* stream) {
-  return r2l_isp_fwd_stats_bn_impl(r2l_raw_u16(raw, denom), params, additive, stats, bn_mean_istd, moments,
-                                   running_mean, running_var, num_batches_tracked, eps, momentum, workspace,
-                                   workspace_bytes, B, H, W, stream);
-}
-int r2l_isp_fwd_u16(const unsigned short* raw, float denom, const float* params, const float* additive,
-                    const float* bn_mean_istd, float* out, double* stats, void* workspace,
-                    size_t workspace_bytes, int B, int H, int W, int flags, void* stream) {
-  return r2l_isp_fwd_impl(R2LFwdCall{r2l_raw_u16(raw, denom), params, additive, bn_mean_istd, out, stats, nullptr,
-                                     R2LEpi{0, 0, 0, 0}, R2L_IO_F32, R2L_FWD_WHOLE, B, H, W, stream},
-                          flags, workspace, workspace_bytes);
-}
-int r2l_isp_bwd(const float* raw, const float* params, const float* additive,
-                const float* bn_mean_istd, const float* bn_bwd, const float* grad_out,
-                float* grad_params, float* grad_raw, void* workspace, size_t workspace_bytes, int B,
-                int H, int W, int flags, void* stream) {
-  return r2l_isp_bwd_impl(r2l_raw_f32(raw), params, additive, bn_mean_istd, bn_bwd, grad_out, grad_params, grad_raw,
-                          workspace, workspace_bytes, B, H, W, flags, stream);
-}
-int r2l_isp_bwd_u16(const unsigned short* raw, float denom, const float* params, const float* additive,
-                    const float* bn_mean_istd, const float* bn_bwd, const float* grad_out,
-                    float* grad_params, void* workspace, size_t workspace_bytes, int B, int H, int W, int flags,
-                    void* stream) {
-  return r2l_isp_bwd_impl(r2l_raw_u16(raw, denom), params, additive, bn_mean_istd, bn_bwd, grad_out, grad_params,
-                          nullptr, workspace, workspace_bytes, B, H, W, flags, stream);
-}
 int r2l_raw2rgb_fwd(const float* raw, const float* black_level, float* out, int B, int H, int W,
                     int reduce_size, int out_channels, void* stream) {
   return r2l_raw2rgb_fwd_impl(r2l_raw_f32(raw), black_level, out, B, H, W, reduce_size, out_channels, stream);

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 LLVM=/opt/rocm/lib/llvm/bin
 W=/tmp/r2l_asm_$1; rm -rf $W; mkdir -p $W tests/_build/ab
 FLAGS="-O3 -std=c++17 -fno-slp-vectorize --offload-arch=gfx950 -DR2L_TEST_HOOKS"
-if [ ! -f /tmp/r2l_asm_dev.s ] || [ raw2logit_amd/csrc/r2l_api_impl.h -nt /tmp/r2l_asm_dev.s ]; then
+if [ ! -f /tmp/r2l_asm_dev.s ] || [ -n "$(find raw2logit_amd/csrc -type f -newer /tmp/r2l_asm_dev.s)" ]; then
   hipcc $FLAGS --cuda-device-only -S raw2logit_amd/csrc/r2l_api.hip -o /tmp/r2l_asm_dev.s 2>/dev/null
 fi
 if [ -n "$2" ]; then sed -E "$2" /tmp/r2l_asm_dev.s > $W/dev.s; else cp /tmp/r2l_asm_dev.s $W/dev.s; fi

@@ -1,5 +1,5 @@
 // r2l_driver_util.h -- what the stand-alone drivers of r2l_lockstep_drivers.cpp share.  TEST INFRASTRUCTURE: included once, behind
-// r2l_lockstep.cpp (it uses the C ABI's enums and the launch record of r2l_api_impl.h), in front of the drivers.
+// r2l_lockstep.cpp (it uses the C ABI's enums and the launch record of r2l_launch.h), in front of the drivers.
 #pragma once
 
 #include <stdio.h>
@@ -80,7 +80,7 @@ inline void fill_raw(Lcg& lcg, void* raw, size_t px, int frames, float lo, float
   }
 }
 
-// The launch record of r2l_api_impl.h (kernel -> launches), emptied and switched on
+// The launch record of r2l_launch.h (kernel -> launches), emptied and switched on
 inline void record_begin() {
   std::lock_guard<std::mutex> g(r2l_ls_record_mutex);
   r2l_ls_record.clear();

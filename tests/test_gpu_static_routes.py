@@ -67,3 +67,18 @@ def test_route_launches_what_the_record_says(name, recorded):
     assert bool(torch.isfinite(out.float()).all())
     if nws:
         assert call(nws - 1) == -2 and b'workspace too small' in lib.r2l_last_error()
+
+
+def test_chain_kernel_dynamic_lds_grant():
+    """The luma-chain kernel's dynamic LDS follows the frame width (16.1 KiB per 256-column strip), and above 48 KiB the launch
+    wrapper has to raise the kernel's limit on the device first (r2l_launch.h: r2l_lds_grant) -- code that neither emulation runs.
+    tests/static_chain_grant_child.py makes the four calls that reach its four branches (1x8x260, 1x8x516, 1x8x1028, 1x8x516), each
+    against orc.static_batch at 1e-5 with the launch record naming r2l_launch_static_chain_kernel once, the two W = 516 outputs
+    bit-identical.  In a process of its own, because what a kernel was granted lasts as long as the process: here, behind the
+    tests above, the branches would depend on what ran before."""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(HERE, 'static_chain_grant_child.py')], capture_output=True, text=True, timeout=300,
+                       cwd=os.path.dirname(HERE))
+    print(r.stdout)
+    assert r.returncode == 0, (r.returncode, (r.stdout + r.stderr)[-3000:])
+    assert r.stdout.strip().endswith('ok') and r.stdout.count('dynamic LDS grant') >= 4
